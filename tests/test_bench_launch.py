@@ -13,7 +13,7 @@ import pytest
 import helpers as H
 
 BENCH = os.path.join(H.ROOT, "bench.py")
-ARGS = ["--n", "64", "--steps", "2", "--warmup", "1", "--depth", "2", "--quick"]
+ARGS = ["--n", "64", "--steps", "2", "--warmup", "1", "--depth", "2", "--full", "--quick"]  # --full: the serving line
 
 
 def _run(extra_env, args, timeout=600):
@@ -39,6 +39,27 @@ def test_bench_gpus_n_spawns_n_ranks(world):
     assert d["all_valid"] and d["pcie_inclusive_serving"]["all_valid"]
     assert d["value"] > 0 and "host simulation" in d["library"]
     assert all(f"[rank {r}]" in p.stderr for r in range(world))
+
+
+@pytest.mark.timeout(300)
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the headline only (nothing measured beside the timed steps), and
+    --dump-outputs writes the last timed step's verdicts and reason codes as float32 arrays."""
+    import numpy as np
+    out = tmp_path / "dump"
+    p = _run({}, ["--gpus", "1", "--n", "64", "--steps", "3", "--warmup", "1", "--depth", "2",
+                  "--dump-outputs", str(out)])
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["all_valid"] and d["full"] is False
+    assert d["value"] == pytest.approx(64 / (d["ms_per_step"] * 1e-3), rel=1e-2)
+    for k in ("pcie_inclusive_serving", "configs", "wire", "latency", "roofline", "serial_ms_per_step"):
+        assert d[k] is None, k
+    assert "cpu_baseline" not in d
+    assert sorted(f.name for f in out.iterdir()) == ["reason.npy", "verdict.npy"]
+    verdict, reason = np.load(out / "verdict.npy"), np.load(out / "reason.npy")
+    assert verdict.dtype == reason.dtype == np.float32 and verdict.shape == reason.shape == (64,)
+    assert (verdict == 1).all() and (reason == 0).all()  # every synthetic update is valid
 
 
 @pytest.mark.timeout(300)

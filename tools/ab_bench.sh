@@ -11,7 +11,7 @@ trap 'cp gpurun_out/.liblcv_orig.so $LIB' EXIT  # the original library is back w
 for i in ${ROUNDS:-1 2}; do
   for v in A B; do
     cp ab/liblcv_$v.so $LIB &&
-    timeout -k 10 240 python -u bench.py --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline --no-configs \
+    timeout -k 10 240 python -u bench.py --full --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline --no-configs \
       > gpurun_out/ab_${v}_$i.json 2> gpurun_out/ab_${v}_$i.err || exit 1
     python -c "
 import json; d=json.load(open('gpurun_out/ab_${v}_$i.json'))

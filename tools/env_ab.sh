@@ -8,7 +8,7 @@ mkdir -p gpurun_out
 for i in ${ROUNDS:-1 2}; do
   for val in ${VALUES}; do
     if [ "$val" = "-" ]; then unset $VAR; else export $VAR=$val; fi
-    timeout -k 10 240 python -u bench.py --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline --no-configs \
+    timeout -k 10 240 python -u bench.py --full --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline --no-configs \
       > gpurun_out/env_${val}_$i.json 2> gpurun_out/env_${val}_$i.err || exit 1
     python -c "
 import json; d=json.load(open('gpurun_out/env_${val}_$i.json'))

@@ -17,7 +17,7 @@ fi
 for i in ${ROUNDS:-1 2 3}; do
   for v in ${VARIANTS:-A B}; do
     cp abp/liblcv_$v.so $LIB &&
-    timeout -k 10 240 python -u bench.py --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline --no-configs \
+    timeout -k 10 240 python -u bench.py --full --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline --no-configs \
       > $OUT/ab_${v}_$i.json 2> $OUT/ab_${v}_$i.err || exit 1
     python -c "
 import json; d=json.load(open('$OUT/ab_${v}_$i.json')); s=d.get('stage_kernel_ms_per_step', {})

@@ -12,7 +12,7 @@ trap 'cp $OUT/.liblcv_orig.so $LIB' EXIT
 for i in ${ROUNDS:-1 2}; do
   for v in ${VARIANTS:-A B}; do
     cp abp/liblcv_$v.so $LIB &&
-    timeout -k 10 300 python -u bench.py --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline \
+    timeout -k 10 300 python -u bench.py --full --steps ${STEPS:-20} --warmup 2 --no-cpu-baseline \
       > $OUT/bench_${v}_$i.json 2> $OUT/bench_${v}_$i.err || exit 1
     python -c "
 import json; d=json.load(open('$OUT/bench_${v}_$i.json')); c=d['configs']

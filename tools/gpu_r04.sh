@@ -12,7 +12,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 240 --timeout
 echo "pytest ok" &&
 timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 &&
 echo "smoke ok" &&
-timeout -k 10 500 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err &&
+timeout -k 10 500 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err &&
 echo "bench ok" &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --depth 1 --steps 3 --warmup 1 --quick > $OUT/bench_prof.json 2> $OUT/bench_prof.err &&
 echo "rocprof ok" &&

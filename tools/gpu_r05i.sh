@@ -14,7 +14,7 @@ timeout -k 10 200 python -u tools/latency_breakdown.py > $OUT/latency.json 2> $O
 echo "latency ok" &&
 timeout -k 10 120 python -u tools/pow_timing.py > $OUT/pow_timing.json 2> $OUT/pow_timing.err &&
 echo "pow ok" &&
-timeout -k 10 500 python -u bench.py --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err &&
+timeout -k 10 500 python -u bench.py --full --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err &&
 echo "bench ok" &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --depth 1 --steps 3 --warmup 1 --quick > $OUT/bench_prof.json 2> $OUT/bench_prof.err &&
 echo "rocprof ok" &&

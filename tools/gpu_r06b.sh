@@ -13,7 +13,7 @@ timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/s
 echo "smoke ok" &&
 timeout -k 10 200 python -u tools/latency_breakdown.py > $OUT/latency.json 2> $OUT/latency.err &&
 echo "latency ok" &&
-timeout -k 10 500 python -u bench.py --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err &&
+timeout -k 10 500 python -u bench.py --full --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err &&
 echo "bench ok" &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- python3 bench.py --depth 1 --steps 3 --warmup 1 --quick > $OUT/bench_prof.json 2> $OUT/bench_prof.err &&
 echo "rocprof ok" &&
