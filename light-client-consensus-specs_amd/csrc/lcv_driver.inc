@@ -147,11 +147,8 @@ struct F_pair_direct { Work W; LCV_HD void operator()(uint32_t i) const { item_p
 static bool fan_on(const lcv_ctx* ctx, uint64_t rows) { return rows > 0 && rows <= ctx->fan_max; }
 // one-lane-per-item kernels: latency-mode batches take the inlined twins of the SSWU maps and the signature
 // decoding (lcv_k_lat.hip), identical results
-#ifndef LCV_LAT_INLINE
-#define LCV_LAT_INLINE 1
-#endif
 template <class F> static int launch_items(lcv_ctx* ctx, const F& f, uint32_t n, uint64_t rows) {
-  const bool twin = LCV_LAT_INLINE && fan_on(ctx, rows);
+  const bool twin = fan_on(ctx, rows);
   ctx->eng_count[twin ? 2 : 3] += 1;
   if constexpr (std::is_same<F, F_h2c_map>::value) {
     if (twin) return be_launch(ctx, F_h2c_map_lat{f.W}, n);
@@ -327,10 +324,7 @@ static int pairing_check(lcv_ctx* ctx, const Work& W, uint32_t n) {
 
 // latency mode: both walks and the accumulation as one fan-engine program (F_sop_miller), then the final
 // exponentiation; the signature's G2 subgroup check happens inside (W.sig_status)
-#ifndef LCV_FUSED_MILLER
-#define LCV_FUSED_MILLER 1
-#endif
-static bool fused_miller(const lcv_ctx* ctx, uint64_t rows) { return LCV_FUSED_MILLER && fan_on(ctx, rows); }
+static bool fused_miller(const lcv_ctx* ctx, uint64_t rows) { return fan_on(ctx, rows); }
 static int fused_pairing(lcv_ctx* ctx, const Work& W, uint32_t n) {
   be_stage_begin(ctx, ST_MILLER);
   ctx->eng_count[0] += 1;
@@ -444,10 +438,7 @@ static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint3
   // SSWU -> hash_to_G2 chain, the longer one (one update: 2.4 ms against 2.2 on this stream with the
   // committee hashed) — unless the slice hashes a large pool of distinct committees (configs[3]: one per
   // update), which makes this stream the longer one: then it stays on the main stream, after EV_PRE
-#ifndef LCV_AGG_SIDE
-#define LCV_AGG_SIDE 1  // 0: always on the main stream (round 4's placement; A/B)
-#endif
-  const bool agg_side = LCV_AGG_SIDE && (nsc == nullptr || nsc->npool < 64);
+  const bool agg_side = nsc == nullptr || nsc->npool < 64;
   if (agg_side) LCV_TRY(agg_stage(ctx, B, C, W, n, agg_items));
   LCV_TRY(be_mark(ctx, EV_PRE, 1));
   be_use_stream(ctx, 0);
@@ -924,10 +915,7 @@ int lcv_slot_wait(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint
 
 int lcv_validate_updates(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t current_slot, const uint8_t* gvr,
                          uint8_t* verdict_out, uint8_t* reason_out) {
-#ifndef LCV_SYNC_STAGED
-#define LCV_SYNC_STAGED 1  // 0: a device batch per call (lcv_batch_upload / lcv_batch_free; A/B)
-#endif
-  if (LCV_SYNC_STAGED && ctx && hb && gvr && ctx->store_set && hb->n > 0 && hb->n <= ctx->chunk) {
+  if (ctx && hb && gvr && ctx->store_set && hb->n > 0 && hb->n <= ctx->chunk) {
     // one chunk (the reference's per-update call shape among them): the columns go through a reused pinned
     // staging buffer and ONE DMA into a reused device copy (lcv_validate_async's path, waited for here)
     // instead of a device allocation, one copy per column and a free per call
@@ -950,6 +938,7 @@ int lcv_validate_updates(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t curr
     bind_batch(&h.db, (uint8_t*)h.dev, c);
     return validate_impl(ctx, &h.db, current_slot, gvr, verdict_out, reason_out, nullptr);  // returns synced
   }
+  // larger batches (and invalid arguments, reported by the upload): a device batch per call
   lcv_dbatch* db = nullptr;
   LCV_TRY(lcv_batch_upload(ctx, hb, &db));
   int rc = validate_impl(ctx, db, current_slot, gvr, verdict_out, reason_out, nullptr);
@@ -1474,7 +1463,7 @@ int lcv_debug_fp(lcv_ctx* ctx, const uint8_t* a48, const uint8_t* b48, uint64_t 
 int lcv_debug_fp_pow(lcv_ctx* ctx, const uint8_t* a48, uint64_t n, uint8_t* out96) {
   if (!ctx || !a48 || !out96) return fail(ctx, LCV_EINVAL, "debug_fp_pow: null argument");
   return simple_call(ctx, n, {{a48, 48 * n}}, {{out96, 96 * n}}, [&](std::vector<uint8_t*>& d) {
-    if (LCV_LAT_INLINE && fan_on(ctx, n)) return be_launch(ctx, F_dbg_pow_lat{{d[0], d[1]}}, (uint32_t)n);
+    if (fan_on(ctx, n)) return be_launch(ctx, F_dbg_pow_lat{{d[0], d[1]}}, (uint32_t)n);
     return be_launch(ctx, F_dbg_pow{d[0], d[1]}, (uint32_t)n);
   });
 }

@@ -109,94 +109,9 @@ LCV_FN void fp_mul_impl(uint32_t r[12], const uint32_t a[12], const uint32_t b[1
   fp_reduce_once(r, t);
 }
 
-// Device: product-scanning (FIPS) Montgomery multiplication on a 96-bit column accumulator.  One
-// multiply-accumulate = v_mad_u64_u32 (64-bit addend, carry-out to an SGPR pair) + v_addc_co_u32
-// into the top word: 2 instructions per 32x32 product instead of CIOS's mad + carry fix-ups.
-// Operands may be <= 2p (the engine's lazily reduced combinations): ab + mp < 2^384 * 3p.
-#ifndef LCV_FP_PS
-#define LCV_FP_PS 1
-#endif
-#if LCV_FP_PS && !defined(LCV_HOSTSIM)
-LCV_FN void mac_vv(uint64_t& acc, uint32_t& hi, uint32_t x, uint32_t y) {
-  uint64_t cc;
-  asm("v_mad_u64_u32 %0, %1, %3, %4, %0\n\tv_addc_co_u32 %2, %1, %2, 0, %1"
-      : "+v"(acc), "=&s"(cc), "+v"(hi)
-      : "v"(x), "v"(y));
-}
-LCV_FN void mac_vs(uint64_t& acc, uint32_t& hi, uint32_t x, uint32_t y) {
-  uint64_t cc;
-  asm("v_mad_u64_u32 %0, %1, %3, %4, %0\n\tv_addc_co_u32 %2, %1, %2, 0, %1"
-      : "+v"(acc), "=&s"(cc), "+v"(hi)
-      : "v"(x), "s"(y));
-}
-LCV_FN void fp_mul_ps(uint32_t r[12], const uint32_t a[12], const uint32_t b[12]) {
-  constexpr uint32_t PL[12] = LCV_P_INIT;
-  uint32_t m[12], t[12];
-  uint64_t acc = 0;
-  uint32_t hi = 0;
-  LCV_UNROLL for (int k = 0; k < 12; ++k) {
-    LCV_UNROLL for (int i = 0; i < k; ++i) mac_vs(acc, hi, m[i], PL[k - i]);
-    LCV_UNROLL for (int i = 0; i <= k; ++i) mac_vv(acc, hi, a[i], b[k - i]);
-    m[k] = (uint32_t)acc * LCV_NP0;
-    mac_vs(acc, hi, m[k], PL[0]);  // low word becomes 0
-    acc = (acc >> 32) | ((uint64_t)hi << 32);
-    hi = 0;
-  }
-  LCV_UNROLL for (int k = 12; k < 23; ++k) {
-    LCV_UNROLL for (int i = k - 11; i < 12; ++i) {
-      mac_vv(acc, hi, a[i], b[k - i]);
-      mac_vs(acc, hi, m[i], PL[k - i]);
-    }
-    t[k - 12] = (uint32_t)acc;
-    acc = (acc >> 32) | ((uint64_t)hi << 32);
-    hi = 0;
-  }
-  t[11] = (uint32_t)acc;
-  fp_reduce_once(r, t);
-}
-// Squaring, product scanning: the cross products a_i a_j (i < j) of a column are accumulated once and
-// doubled (78 + 12 multiply-accumulates for the square instead of 144) — the windowed square-root
-// exponentiations of signature decoding and SSWU are ~80% squarings.
-LCV_FN void fp_sqr_ps(uint32_t r[12], const uint32_t a[12]) {
-  constexpr uint32_t PL[12] = LCV_P_INIT;
-  uint32_t m[12], t[12];
-  uint64_t acc = 0;
-  uint32_t hi = 0;
-  LCV_UNROLL for (int k = 0; k < 23; ++k) {
-    // cross terms of column k, doubled: 2 * sum_{i < j, i + j = k} a_i a_j
-    uint64_t x = 0;
-    uint32_t xh = 0;
-    LCV_UNROLL for (int i = (k > 11 ? k - 11 : 0); 2 * i < k; ++i) mac_vv(x, xh, a[i], a[k - i]);
-    {  // (xh:x) <<= 1, then acc += it
-      const uint32_t x0 = (uint32_t)x, x1 = (uint32_t)(x >> 32);
-      const uint32_t d2 = (xh << 1) | (x1 >> 31), d1 = (x1 << 1) | (x0 >> 31), d0 = x0 << 1;
-      uint32_t lo = (uint32_t)acc, mid = (uint32_t)(acc >> 32), c;
-      lo = addc32(lo, d0, 0u, c);
-      mid = addc32(mid, d1, c, c);
-      hi = hi + d2 + c;
-      acc = ((uint64_t)mid << 32) | lo;
-    }
-    if ((k & 1) == 0) mac_vv(acc, hi, a[k >> 1], a[k >> 1]);
-    if (k < 12) {
-      LCV_UNROLL for (int i = 0; i < k; ++i) mac_vs(acc, hi, m[i], PL[k - i]);
-      m[k] = (uint32_t)acc * LCV_NP0;
-      mac_vs(acc, hi, m[k], PL[0]);  // low word becomes 0
-    } else {
-      LCV_UNROLL for (int i = k - 11; i < 12; ++i) mac_vs(acc, hi, m[i], PL[k - i]);
-      t[k - 12] = (uint32_t)acc;
-    }
-    acc = (acc >> 32) | ((uint64_t)hi << 32);
-    hi = 0;
-  }
-  t[11] = (uint32_t)acc;
-  fp_reduce_once(r, t);
-}
-// Round 3: the same Montgomery product / square through the 28-bit column engine (lcv_col28.hpp): no
-// carry chain, one subtractive Karatsuba level, independent columns for a lone wave's issue
-#ifndef LCV_FP_C28
-#define LCV_FP_C28 1
-#endif
-#if LCV_FP_C28
+// Device: the Montgomery product / square through the 28-bit column engine (lcv_col28.hpp): no carry chain,
+// one subtractive Karatsuba level, independent columns for a lone wave's issue
+#if !defined(LCV_HOSTSIM)
 LCV_FN void fp_mul_c28r(uint32_t r[12], const uint32_t a[12], const uint32_t b[12]) {
   uint32_t t[13];
   fp_mul_c28(t, a, b);
@@ -209,10 +124,6 @@ LCV_FN void fp_sqr_c28r(uint32_t r[12], const uint32_t a[12]) {
 }
 #define LCV_SQR_IMPL fp_sqr_c28r
 #define LCV_MUL_IMPL fp_mul_c28r
-#else
-#define LCV_SQR_IMPL fp_sqr_ps
-#define LCV_MUL_IMPL fp_mul_ps
-#endif
 
 #elif defined(LCV_CPU_FAST)
 // CPU-baseline build only (liblcv_cpu.so, bench.py's cpu_baseline leg): the same Montgomery product
@@ -356,11 +267,9 @@ LCV_DEF_POW(fp_inv_fermat, LCV_EXP_P_MINUS_2, LCV_EXP_P_MINUS_2_BITS)    // a^(p
 // limb value < 2p squares to < 2p), so a product is its multiply-adds and quotient chain only.  In: a R ->
 // a 2^392 (one product with the raw constant 2^392 mod p); out: the chain's a^e 2^392 -> a^e R (one product
 // with 2^376) after packing and one subtraction.  Results equal the word-form walk's (both are fully reduced).
-// LCV_POW_LF 1 (the host simulation; the latency-mode twins until round 5 v6, now LCV_POW_LF 3 below): 4-bit
-// window, table in LDS — a lone wave's SSWU maps 1.55 -> 1.13 ms; at full batches the 28 KB LDS table per block crowds the co-resident final exponentiation
-// (LDS- and VGPR-bound at 12 waves per CU) and the serving loop measured 0.5-1 % slower.  LCV_POW_LF 2 (the
-// batch kernels): 3-bit window, four table entries in registers (the 4-bit register table spilled 624 B per
-// lane): serving loop +1.3 %, one batch at a time -3.7 % (profiles/r05_v5/pow_ab.txt).  0: the word form.
+// LCV_POW_LF 1 (the host simulation): 4-bit window.  LCV_POW_LF 2 (the batch kernels): 3-bit window, four table
+// entries in registers (the 4-bit register table spilled 624 B per lane): serving loop +1.3 %, one batch at a
+// time -3.7 % (profiles/r05_v5/pow_ab.txt).  LCV_POW_LF 3 (the latency-mode twins): below.  0: the word form.
 #ifndef LCV_POW_LF
 #if defined(LCV_CPU_FAST)
 #define LCV_POW_LF 0  // the CPU baseline: its 64-bit limb products beat 28-bit columns on a scalar core
@@ -391,21 +300,9 @@ LCV_FN void fp_lf_out(fp& r, const uint32_t L[14]) {
   LCV_FP_SET(c, LCV_2E376_RAW_INIT);
   fp_mul(r, t, c);
 }
-// the window table a^1, a^3, .., a^15 (8 x 14 limbs per lane): in LDS on the device — one 28 KB buffer per
-// 64-lane block of a per-item kernel (k_items; every caller of these chains is one), lane-interleaved, read at a
-// wave-uniform index (the exponent is public) — instead of 112 VGPRs and a select chain per window
-#if defined(__HIP_DEVICE_COMPILE__) && LCV_POW_LF == 1
-LCV_FN uint32_t* pow_lf_table() {
-  __shared__ uint32_t t[8 * 14 * 64];
-  return t + (threadIdx.x & 63u);
-}
-#define LCV_POW_WB 4
-#define LCV_POW_TAB(k, q) tabp[((k) * 14 + (q)) * 64]
-#define LCV_POW_TAB_DECL uint32_t* tabp = pow_lf_table();
-#define LCV_POW_TAB_GET(m, idx) LCV_UNROLL for (int q = 0; q < 14; ++q) m[q] = LCV_POW_TAB(idx, q);
-#else
-// registers (LCV_POW_LF 2: a 3-bit window, four entries, for the batch kernels' register budget; the host
-// simulation: 4 bits); the entry is picked by wave-uniform branches (the exponent is public)
+// the window table a^1, a^3, .. in registers (LCV_POW_LF 2: a 3-bit window, four entries, for the batch kernels'
+// register budget; the host simulation: 4 bits, eight entries); the entry is picked by wave-uniform branches (the
+// exponent is public)
 #define LCV_POW_WB (LCV_POW_LF == 2 ? 3 : 4)
 #define LCV_POW_TAB(k, q) tabh[k][q]
 #define LCV_POW_TAB_DECL uint32_t tabh[1 << (LCV_POW_WB - 1)][14];
@@ -413,7 +310,6 @@ LCV_FN uint32_t* pow_lf_table() {
   LCV_UNROLL for (int q = 0; q < 14; ++q) m[q] = tabh[0][q];                              \
   LCV_UNROLL for (int k = 1; k < (1 << (LCV_POW_WB - 1)); ++k)                             \
     if ((idx) == (uint32_t)k) LCV_UNROLL for (int q = 0; q < 14; ++q) m[q] = tabh[k][q];
-#endif
 #define LCV_DEF_POW_LF(fname, EXPARR, NBITS)                                              \
   LCV_FN void fname(fp& r, const fp& a_) {                                                \
     uint32_t a[14], t[14], a2[14], acc[14];                                               \

@@ -13,35 +13,22 @@
 #include "lcv_sop_fan.hpp"
 #include "lcv_sop_row.hpp"
 #endif
-// the fan engine's lanes per product (lcv_sop_fan.hpp; also known to lcv_launch.hpp): 3 = Karatsuba parts split
-#ifndef LCV_FAN_SPLIT
-#define LCV_FAN_SPLIT 1
-#endif
-#ifndef LCV_FAN_PARTS
-#define LCV_FAN_PARTS (LCV_FAN_SPLIT ? 3u : 1u)
-#endif
 
 enum { SOP_LINE_VALS = 6 * LCV_SOP_LINES_NSTEPS, SOP_LINE_WORDS = 2 * SOP_LINE_VALS * 12 };
 // W.lines: item i's two pairings' line values (pairing k at + k * SOP_LINE_VALS * 12 words)
 LCV_HDFN size_t lines_index(size_t i) { return i * (size_t)SOP_LINE_WORDS; }
-// per-item LDS pitch = 12 * slots + SOP_PITCH_PAD words: 4 keeps every value 16-byte aligned for the
-// b128 LDS accesses (LCV_SOP_B128, lcv_sop.hpp); 1 (odd) staggers the teams' banks for 32-bit accesses
-enum { SOP_PITCH_PAD = LCV_SOP_B128 ? 4 : 1 };
-
-// Round 2 padded the pitch to an odd word count so the teams of a wave start on different LDS banks for
-// 32-bit accesses (a bank model: 1.3-1.4x the conflict-free LDS cycles instead of 2.7-3.4x); since r03
-// v13 the pitch is 4 mod 8 words and values move as 16-byte accesses, three instead of six LDS
-// instructions per value: 1.448 -> 1.472 M updates/s in a same-box A/B (profiles/r03_v13)
-// the SOP kernels' VGPR budget in waves per SIMD (3 = 168 VGPRs, no spills; an experiment knob)
-#ifndef LCV_SOP_WAVES
-#define LCV_SOP_WAVES 3
-#endif
+// per-item LDS pitch = 12 * slots + SOP_PITCH_PAD words: 4 mod 8 words, so every value is 16-byte aligned and
+// moves as 16-byte LDS accesses (lcv_sop.hpp sop_ld12 / sop_st12), three instead of six LDS instructions per
+// value: 1.448 -> 1.472 M updates/s in a same-box A/B against round 2's odd pitch (profiles/r03_v13)
+enum { SOP_PITCH_PAD = 4 };
+// the SOP kernels' VGPR budget in waves per SIMD (3 = 168 VGPRs, no spills)
+constexpr uint32_t LCV_SOP_WAVES = 3;
 struct F_sop_lines {
   Work W; SopView P;
   uint32_t mode;  // 0: items t = 2i + k (both pairings); 1: t = i, k = 1 (signature); 2: t = i, k = 0 (message)
   static constexpr uint32_t WAVES = LCV_SOP_WAVES;  // waves per SIMD the kernel's VGPR budget targets
   static constexpr uint32_t MAXK = LCV_SOP_LINES_MAXK;  // the fan engine's lanes per op
-  static constexpr uint32_t FAN_PARTS = LCV_FAN_PARTS;    // the fan engine's lanes per product
+  static constexpr uint32_t FAN_PARTS = 3;  // the fan engine's lanes per product
   static constexpr uint32_t TEAM = LCV_SOP_LINES_TEAM, LDS_WORDS = LCV_SOP_LINES_SLOTS * 12 + SOP_PITCH_PAD,
                             SHARED_WORDS = LCV_SOP_LINES_NCONST * 12;
   // pairing k of update i: k = 0 e(PK_agg, H(m)), k = 1 e(-G1, signature)
@@ -114,7 +101,7 @@ struct F_sop_acc {
   Work W; SopView P;
   static constexpr uint32_t WAVES = LCV_SOP_WAVES;  // waves per SIMD the kernel's VGPR budget targets
   static constexpr uint32_t MAXK = LCV_SOP_MILLER_ACC_MAXK;  // the fan engine's lanes per op
-  static constexpr uint32_t FAN_PARTS = LCV_FAN_PARTS;         // the fan engine's lanes per product
+  static constexpr uint32_t FAN_PARTS = 3;  // the fan engine's lanes per product
   static constexpr uint32_t TEAM = LCV_SOP_MILLER_ACC_TEAM, LDS_WORDS = LCV_SOP_MILLER_ACC_SLOTS * 12 + SOP_PITCH_PAD,
                             SHARED_WORDS = LCV_SOP_MILLER_ACC_NCONST * 12;
   static_assert(LCV_SOP_MILLER_ACC_SLOT_F0_0 == 0 && LCV_SOP_MILLER_ACC_SLOT_F5_1 == 11, "f in slots 0..11");
@@ -227,7 +214,7 @@ struct F_sop_fexp {
   Work W; SopView P;
   static constexpr uint32_t WAVES = LCV_SOP_WAVES;  // waves per SIMD the kernel's VGPR budget targets
   static constexpr uint32_t MAXK = LCV_SOP_FEXP_MAXK;  // the fan engine's lanes per op
-  static constexpr uint32_t FAN_PARTS = LCV_FAN_PARTS;   // the fan engine's lanes per product
+  static constexpr uint32_t FAN_PARTS = 3;  // the fan engine's lanes per product
   static constexpr uint32_t TEAM = LCV_SOP_FEXP_TEAM, LDS_WORDS = LCV_SOP_FEXP_SLOTS * 12 + SOP_PITCH_PAD,
                             SHARED_WORDS = LCV_SOP_FEXP_NCONST * 12;
   static_assert(LCV_SOP_FEXP_SLOT_F0_0 == 0 && LCV_SOP_FEXP_SLOT_F5_1 == 11, "f in slots 0..11");
@@ -273,7 +260,7 @@ struct F_sop_h2c {
   Work W; SopView P;
   static constexpr uint32_t WAVES = LCV_SOP_WAVES;  // waves per SIMD the kernel's VGPR budget targets
   static constexpr uint32_t MAXK = LCV_SOP_H2C_MAXK;  // the fan engine's lanes per op
-  static constexpr uint32_t FAN_PARTS = LCV_FAN_PARTS;  // the fan engine's lanes per product
+  static constexpr uint32_t FAN_PARTS = 3;  // the fan engine's lanes per product
   static constexpr uint32_t TEAM = LCV_SOP_H2C_TEAM, LDS_WORDS = LCV_SOP_H2C_SLOTS * 12 + SOP_PITCH_PAD,
                             SHARED_WORDS = LCV_SOP_H2C_NCONST * 12;
   static_assert(LCV_SOP_H2C_SLOT_M0X0 == 0 && LCV_SOP_H2C_SLOT_M1Y1 == 7, "SSWU points in slots 0..7");
@@ -310,7 +297,7 @@ template <class F>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(F::WAVES))) void k_sop(F f, uint32_t n, uint32_t g) {
   constexpr uint32_t T = F::TEAM, G = 64 / F::TEAM;
   if (g == 0 || g > G) g = G;
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];  // 16-byte aligned values (LCV_SOP_B128)
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];  // 16-byte aligned values (sop_ld12 / sop_st12)
   const uint32_t team = threadIdx.x / T, lane = threadIdx.x % T;
   const uint32_t item = blockIdx.x * g + team;
   const bool active = team < g && item < n;
@@ -357,32 +344,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(F::WAVES))) 
 }
 
 // The fan engine's round loop (lcv_sop_fan.hpp; latency mode): ONE item per block of TEAM x MAXK x S lanes
-// (S = LCV_FAN_PARTS, 3 when the products' Karatsuba parts are split; lcv_hip_launch_sop_fan sizes it to
-// whole waves), lane (k S + part) TEAM + o computes part `part` of product k of op o, so the ops'
-// product-0 part-0 lanes — which also run the reductions and tails — are lanes 0 .. TEAM - 1 of the first
-// wave, whose lockstep orders every tail's reads before any store; a round of K products keeps its
-// K x S x TEAM busy lanes in the first waves.  The products' columns meet in the op's 28-column LDS
-// accumulator by 64-bit LDS atomic adds (ds_add_u64); the op's tail lane reads the sums and zeroes the
-// accumulator for the next round.  Two block barriers per round: after the products (the sums are
-// complete) and after the stores (the next round reads them).
-// LCV_FAN_X_TIMING (experiments only): per-phase clock sums of the first and the last wave, printed.
-#ifndef LCV_FAN_X_TIMING
-#define LCV_FAN_X_TIMING 0
-#endif
-#ifndef LCV_FAN_FLAT_COLS
-#define LCV_FAN_FLAT_COLS 1
-#endif
-#ifndef LCV_FAN_FLAT_FETCH
-#define LCV_FAN_FLAT_FETCH 1
-#endif
-#ifndef LCV_FAN_LATE_FETCH
-#define LCV_FAN_LATE_FETCH 1
-#endif
-#ifndef LCV_FAN_X_NOATOMIC
-#define LCV_FAN_X_NOATOMIC 0
-#endif
-// LCV_FAN_ROW (lcv_launch.hpp, the default) for the programs of at most LCV_FAN_ROW_MAX_TEAM ops a round
-// (lcv_fan_rows<F>: the final exponentiation and hash_to_G2's tail): op o's tail runs on the 16-lane row of lanes
+// (S = F::FAN_PARTS: 3 lanes per product, one per Karatsuba part, or 1 for the fused Miller program;
+// lcv_hip_launch_sop_fan sizes the block to whole waves), lane (k S + part) TEAM + o computes part `part` of
+// product k of op o; a round of K products keeps its K x S x TEAM busy lanes in the first waves.  The products'
+// columns meet in the op's 28-column LDS accumulator by 64-bit LDS atomic adds (ds_add_u64); the op's tail reads
+// the sums and zeroes the accumulator for the next round.  Two block barriers per round: after the products (the
+// sums are complete) and after the stores (the next round reads them).
+// One-lane tails (the fused Miller program): op o's reduction and tail run on its product-0 part-0 lane, lane o of
+// the first wave, whose lockstep orders every tail's reads before any store.
+// Row tails, for the programs of at most LCV_FAN_ROW_MAX_TEAM ops a round (lcv_fan_rows<F>: the lines, the
+// accumulation, the final exponentiation and hash_to_G2's tail): op o's tail runs on the 16-lane row of lanes
 // 16 o .. 16 o + 15 (lcv_sop_row.hpp: the reduction as two column passes, one column pair per lane; the add-ins,
 // the quotient step and the store with a limb or word per lane), instead of on one lane of the first wave.  The
 // tails then sit in several waves, so a row reads its add-in terms at the top of the round, before any tail of
@@ -393,7 +364,9 @@ __global__ __launch_bounds__(lcv_fan_threads<F>()) void k_sop_fan(F f, uint32_t 
   constexpr uint32_t T = F::TEAM, KM = F::MAXK, S = F::FAN_PARTS, NT = lcv_fan_threads<F>();
   constexpr bool ROWS = lcv_fan_rows<F>();
   constexpr uint32_t ITEM_WORDS = (F::LDS_WORDS + 1u) & ~1u;  // 8-byte aligned scratch after the slots
-  static_assert(T <= 64, "every op's tail lane in the first wave");
+  // (row tails, T <= LCV_FAN_ROW_MAX_TEAM, span several waves: one 16-lane row per op)
+  static_assert(T <= 64, "the ops of a round fit one wave: one-lane tails run on lanes 0 .. T - 1 of the first");
+  static_assert(lcv_fan_threads<F>() <= 1024, "one item per block: its lanes fit one workgroup");
   static_assert(S == 1 || S == 3, "one lane per product, or one per Karatsuba part");
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const uint32_t L = threadIdx.x, k = L / (S * T), part = (L / T) % S, o = L % T;
@@ -443,7 +416,6 @@ __global__ __launch_bounds__(lcv_fan_threads<F>()) void k_sop_fan(F f, uint32_t 
     c.w = f.P.rec + off + __umul24(o, words);  // (o < 64, words < 2^10: the full-rate 24-bit multiply)
     const uint32_t* wt = f.P.rec + off + __umul24(to < T ? to : 0u, words);  // the tail's op's record
     const uint32_t K = c.h0 & 15u;
-#if LCV_FAN_FLAT_FETCH
     // branch-free: every lane loads (a lone wave pays each exec-mask region and branch in series).  Product k is
     // clamped into op o's record (4 + 3 K words: its first words when K = 0); the values are used only by the lanes
     // they belong to (active, k < K; a row's add-in words only when the header counts them)
@@ -456,34 +428,11 @@ __global__ __launch_bounds__(lcv_fan_threads<F>()) void k_sop_fan(F f, uint32_t 
     if constexpr (ROWS) {
       c.d0 = wt[0]; c.d1 = wt[1]; c.a0 = wt[2]; c.a1 = wt[3];
     }
-#else
-    c.x = c.y = c.m = 0;
-    if (active && k < K) {
-      const uint32_t* pw = c.w + 4 + 3 * k;
-      c.x = pw[0]; c.y = pw[1]; c.m = pw[2];
-    }
-    c.pre = lcv::SopPre{0, 0, 0, 0, 0};
-    c.a0 = c.a1 = c.d0 = c.d1 = 0;
-    if (tail_lane && !ROWS) c.pre = lcv::sop_pre(c.h0, wt);  // (rows: the dst / io words are d0 / d1 below)
-    if (rowact) {
-      const uint32_t nadd = (c.h0 >> 4) & 3u;
-      c.d0 = wt[0];
-      c.d1 = wt[1];
-      if (nadd > 0) c.a0 = wt[2];
-      if (nadd > 1) c.a1 = wt[3];
-    }
-#endif
     return c;
   };
   Hdr hn = load_hdr(0);
   Rec nx = fetch(hn);
   if (R > 1) hn = load_hdr(1);
-#if LCV_FAN_X_TIMING
-  uint64_t tq[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, tp = clock64();
-#define LCV_FAN_T(i) do { const uint64_t tn = clock64(); tq[i] += tn - tp; tp = tn; } while (0)
-#else
-#define LCV_FAN_T(i) ((void)0)
-#endif
   // round r reads its record `cur` and fetches round r + 1's into `nxr` (unconditionally: past the last round it
   // re-reads the last round's record).  The loop runs two rounds a trip with the two records swapping roles, so
   // no record is copied at the back edge: such a copy waits on the record's loads, issued only a round earlier
@@ -492,28 +441,22 @@ __global__ __launch_bounds__(lcv_fan_threads<F>()) void k_sop_fan(F f, uint32_t 
     hn = load_hdr(r + 2 < R ? r + 2 : R - 1);
   };
   auto round = [&](const uint32_t r, const Rec& cur, Rec& nxr) __attribute__((always_inline)) {
-    if (!LCV_FAN_LATE_FETCH) prefetch(r, nxr);
     const uint32_t h0 = cur.h0, K = h0 & 15u;
-    LCV_FAN_T(0);
     if (active && k < K) {
-      if constexpr (S == 3) {
-      int64_t c13[13];
-      lcv::sop_fan_part(c13, cur.x, cur.y, cur.m, k, cur.h3, (h0 >> 6) & 1u, part, base);
-      const uint32_t at = part == 0 ? 0u : (part == 1 ? 14u : 7u);
-#if LCV_FAN_X_NOATOMIC  // timing experiment only (wrong results): one atomic per lane instead of 13 or 26
-      { uint64_t xs = 0; LCV_UNROLL for (int c = 0; c < 13; ++c) xs ^= (uint64_t)c13[c];
-        __hip_atomic_fetch_add(acc + at, xs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-      if (false)
-#endif
-      LCV_UNROLL for (int c = 0; c < 13; ++c)
-        __hip_atomic_fetch_add(acc + at + c, (uint64_t)c13[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (part != 2 && !LCV_FAN_X_NOATOMIC)
+      if constexpr (S == 3) {  // part 0 into columns 0 and 7, part 1 into 14 and 7, part 2 into 7 (lcv_sop_fan.hpp)
+        int64_t c13[13];
+        lcv::sop_fan_part(c13, cur.x, cur.y, cur.m, k, cur.h3, (h0 >> 6) & 1u, part, base);
+        const uint32_t at = part == 0 ? 0u : (part == 1 ? 14u : 7u);
         LCV_UNROLL for (int c = 0; c < 13; ++c)
-          __hip_atomic_fetch_add(acc + 7 + c, (uint64_t)c13[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      } else {
-      uint64_t col[28];
-      lcv::sop_fan_product(col, cur.x, cur.y, cur.m, k, cur.h3, (h0 >> 6) & 1u, base);
-      LCV_UNROLL for (int c = 0; c < 28; ++c) __hip_atomic_fetch_add(acc + c, col[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          __hip_atomic_fetch_add(acc + at + c, (uint64_t)c13[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (part != 2)
+          LCV_UNROLL for (int c = 0; c < 13; ++c)
+            __hip_atomic_fetch_add(acc + 7 + c, (uint64_t)c13[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      } else {  // one lane per product (the fused Miller program)
+        uint64_t col[28];
+        lcv::sop_fan_product(col, cur.x, cur.y, cur.m, k, cur.h3, (h0 >> 6) & 1u, base);
+        LCV_UNROLL for (int c = 0; c < 28; ++c)
+          __hip_atomic_fetch_add(acc + c, col[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       }
     }
     // a row's add-in terms are read now (the two words holding a lane's limb): after the products' operand reads and
@@ -524,52 +467,26 @@ __global__ __launch_bounds__(lcv_fan_threads<F>()) void k_sop_fan(F f, uint32_t 
       if (nadd > 0) lcv::rw_limb_words(lcv::sop_src(cur.a0 & 0xFFFu, my, lds, ns), tw[0], tw[1]);
       if (nadd > 1) lcv::rw_limb_words(lcv::sop_src(cur.a1 & 0xFFFu, my, lds, ns), tw[2], tw[3]);
     }
-    // LCV_FAN_LATE_FETCH: round r + 1's record loads (and round r + 2's header) are issued here, while the column
-    // atomics drain before the barrier (it waits on LDS only), instead of at the top of the round, where a lone wave
-    // pays their issue in series with its products; they are still a whole tail ahead of their use
-    if (LCV_FAN_LATE_FETCH) prefetch(r, nxr);
-    LCV_FAN_T(1);
+    // round r + 1's record loads (and round r + 2's header) are issued late: here, while the column atomics drain
+    // before the barrier (it waits on LDS only), not at the top of the round, where a lone wave would pay their issue
+    // in series with its products; they are still a whole tail ahead of their use
+    prefetch(r, nxr);
     __syncthreads();
-    LCV_FAN_T(2);
     if constexpr (ROWS) {
       if (rowact) {  // K and the header flags are wave-uniform: the whole row takes one branch
         uint32_t rl = 0;  // r = REDC(T): limb j on lane j (partly normalised)
         if (K != 0) {
           const uint32_t jj = L & 15u;
-          uint64_t lo = 0, hi = 0;
-#if LCV_FAN_FLAT_COLS
-          {  // branch-free: lanes 14, 15 read and zero lane 13's pair again (the reads precede the writes in the wave)
-            const uint32_t jc = jj < 14u ? jj : 13u;
-            const uint64_t cl = racc[jc], ch = racc[jc + 14];
-            racc[jc] = 0;
-            racc[jc + 14] = 0;
-            lo = jj < 14u ? cl : 0ull;
-            hi = jj < 14u ? ch : 0ull;
-          }
-#else
-          if (jj < 14u) {
-            lo = racc[jj];
-            hi = racc[jj + 14];
-            racc[jj] = 0;
-            racc[jj + 14] = 0;
-          }
-#endif
-#if LCV_FAN_X_TIMING > 1
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          LCV_FAN_T(5);
-#endif
+          // branch-free: lanes 14, 15 read and zero lane 13's pair again (the reads precede the writes in the wave)
+          const uint32_t jc = jj < 14u ? jj : 13u;
+          const uint64_t cl = racc[jc], ch = racc[jc + 14];
+          racc[jc] = 0;
+          racc[jc + 14] = 0;
+          const uint64_t lo = jj < 14u ? cl : 0ull, hi = jj < 14u ? ch : 0ull;
           rl = lcv::rw_redc_limbs(lo, hi, rtabs);
-#if LCV_FAN_X_TIMING > 1
-          asm volatile("" :: "v"(rl));
-          LCV_FAN_T(6);
-#endif
         }
         const uint32_t vl = lcv::rw_value(rl, (h0 >> 4) & 3u, cur.a0, cur.a1, lcv::rw_limb_of(tw[0], tw[1]),
                                           lcv::rw_limb_of(tw[2], tw[3]), (h0 >> 16) & 31u, rtabs);
-#if LCV_FAN_X_TIMING > 1
-        asm volatile("" :: "v"(vl));
-        LCV_FAN_T(7);
-#endif
         if (h0 & ((1u << 10) | (1u << 11) | (1u << 12))) {  // inversion, side-load and emit rounds: on lane 0
           uint32_t w[13];
           lcv::rw_gather(w, lcv::rw_word(vl));
@@ -592,44 +509,19 @@ __global__ __launch_bounds__(lcv_fan_threads<F>()) void k_sop_fan(F f, uint32_t 
         uint64_t col[28];
         LCV_UNROLL for (int c = 0; c < 28; ++c) col[c] = acc[c];
         LCV_UNROLL for (int c = 0; c < 28; ++c) acc[c] = 0;
-#if LCV_FAN_X_TIMING > 1  // sub-phases of the tail (the sums wait for their reads: the clock reads data)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        LCV_FAN_T(5);
-#endif
         lcv::sop_redc28(res, col);
-#if LCV_FAN_X_TIMING > 1
-        asm volatile("" :: "v"(res[12]));
-        LCV_FAN_T(6);
-#endif
       }
       lcv::fp v;
       lcv::sop_tail_value(v, h0, cur.w, cur.pre, my, lds, ns, res, qp);
-#if LCV_FAN_X_TIMING > 1
-      asm volatile("" :: "v"(v.v[11]));
-      LCV_FAN_T(7);
-#endif
       lcv::sop_tail_store(h0, cur.pre, my, io_in, io_out, v);
     }
-    LCV_FAN_T(3);
-#if LCV_FAN_X_TIMING > 1
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    LCV_FAN_T(8);
-#endif
     __syncthreads();
-    LCV_FAN_T(4);
   };
   Rec rb = nx;
   for (uint32_t r = 0; r < R; r += 2) {
     round(r, nx, rb);
     if (r + 1 < R) round(r + 1, rb, nx);
   }
-#if LCV_FAN_X_TIMING
-  if (item == 0 && (L == 0 || L == NT - 64))
-    printf("fan T=%u KM=%u S=%u R=%u rows=%d wave=%u: fetch %lu products %lu barrier1 %lu tail %lu barrier2 %lu | "
-           "tail: columns %lu redc %lu value %lu store %lu\n", T, KM, S, R, (int)ROWS, L / 64, tq[0], tq[1], tq[2], tq[3],
-           tq[4], tq[5], tq[6], tq[7], tq[8]);
-#endif
-#undef LCV_FAN_T
   if (L < T && item < n) f.epilogue(item, L, my);
 }
 #endif

@@ -11,11 +11,6 @@ template <class F> hipError_t lcv_hip_launch(const F& f, uint32_t n, hipStream_t
 template <class F> hipError_t lcv_hip_launch_team(const F& f, uint32_t n, hipStream_t s);
 template <class F> hipError_t lcv_hip_launch_sop(const F& f, uint32_t n, hipStream_t s, uint32_t g = 0);
 template <class F> hipError_t lcv_hip_launch_sop_fan(const F& f, uint32_t n, hipStream_t s);
-// the fan engine's lanes per product: 3 (its Karatsuba sub-products split, lcv_sop_fan.hpp) or 1
-#ifndef LCV_FAN_SPLIT
-#define LCV_FAN_SPLIT 1
-#endif
-#define LCV_FAN_PARTS (LCV_FAN_SPLIT ? 3u : 1u)
 
 #ifdef LCV_KERNEL_UNIT
 template <class F>
@@ -76,15 +71,11 @@ template <class F> hipError_t lcv_hip_launch_sop(const F& f, uint32_t n, hipStre
   return hipGetLastError();
 }
 // the fan engine (latency mode, lcv_sop_fan.hpp): one item per block of TEAM x MAXK x F::FAN_PARTS lanes
-// (whole waves), and at least 16 lanes per op when the ops' reductions run on rows of 16 lanes (LCV_FAN_ROW,
-// lcv_sop_row.hpp)
-#ifndef LCV_FAN_ROW
-#define LCV_FAN_ROW 1
-#endif
-#ifndef LCV_FAN_ROW_MAX_TEAM  // row tails for programs of at most this many ops a round (fexp 12, h2c 8; the
-#define LCV_FAN_ROW_MAX_TEAM 16  // fused Miller program's 32 rows would fill 8 waves: slower, profiles/r06_ab)
-#endif
-template <class F> constexpr bool lcv_fan_rows() { return LCV_FAN_ROW && F::TEAM <= LCV_FAN_ROW_MAX_TEAM; }
+// (whole waves), and at least 16 lanes per op when the ops' reductions run on rows of 16 lanes (lcv_sop_row.hpp).
+// Row tails for programs of at most LCV_FAN_ROW_MAX_TEAM ops a round (lines 10, acc 12, fexp 12, h2c 8); the fused Miller program
+// stays on one-lane tails: its 32 rows would fill 8 waves, which is slower (profiles/r06_ab)
+constexpr uint32_t LCV_FAN_ROW_MAX_TEAM = 16;
+template <class F> constexpr bool lcv_fan_rows() { return F::TEAM <= LCV_FAN_ROW_MAX_TEAM; }
 template <class F> constexpr uint32_t lcv_fan_threads() {
   constexpr uint32_t a = ((F::TEAM * F::MAXK * F::FAN_PARTS + 63) / 64) * 64;
   constexpr uint32_t b = lcv_fan_rows<F>() ? ((16 * F::TEAM + 63) / 64) * 64 : 0;

@@ -1,5 +1,5 @@
 // lcv_sop_row.hpp — the fan engine's Montgomery reduction spread over a row of 16 lanes (latency mode,
-// lcv_functors_sop.hpp k_sop_fan with LCV_FAN_ROW): one op's 28 column sums, lane j holding columns j and
+// lcv_functors_sop.hpp k_sop_fan where lcv_fan_rows<F>()): one op's 28 column sums, lane j holding columns j and
 // j + 14, instead of one lane running sop_redc28's 196 multiply-adds back to back.
 //
 // A lone wave is bound by instruction issue in sop_redc28 (4.2-4.8 shader cycles per wave64 instruction at one wave

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B helper: liblcv.so variants that differ only in one unit (UNIT, default the fan engine's
 # csrc/lcv_k_fan.hip; lcv_hip for the driver) compiled with extra -D flags:
-# VARIANTS="A: B:-DLCV_FAN_SPLIT=0 ..." -> abp/liblcv_<name>.so (after `make`).
+# VARIANTS="A: B:-DLCV_SOP_MARKERS ..." -> abp/liblcv_<name>.so (after `make`).
 set -e
 cd "$(dirname "$0")/../light-client-consensus-specs_amd"
 mkdir -p ../abp

@@ -297,28 +297,6 @@ class Program:
         self.zero = self.base_const + self.consts[0]
         assert self.base_const + len(self.consts) < SLOT_MASK
 
-    def relabel(self, perm):
-        """Renumber the program's slots (perm: old slot -> new slot, a permutation of range(nslots)),
-        after finalize: every op's destination / shadow / side-load slot, add-in and product terms and the
-        named slots move together, so the program computes the same values (tools/bank_model.py picks
-        perm to lower the modelled LDS bank conflicts)."""
-        assert sorted(perm) == list(range(self.nslots))
-
-        def m(s):
-            return perm[s] if isinstance(s, int) and 0 <= s < self.nslots else s
-        for ops in self.rounds:
-            for o in ops:
-                o.dst = None if o.dst is None else m(o.dst)
-                o.dst_shadow = None if o.dst_shadow is None else m(o.dst_shadow)
-                o.load_shadow = None if o.load_shadow is None else m(o.load_shadow)
-                if o.load:
-                    o.load = (m(o.load[0]), o.load[1])
-                o.adds = [(m(a), c) for a, c in o.adds]
-                for x, y, _ in o.prods:  # new term objects: one T may sit in several places
-                    x[:] = [T(m(t.slot), t.neg) for t in x]
-                    y[:] = [T(m(t.slot), t.neg) for t in y]
-        self.named = {k: m(v) for k, v in self.named.items()}
-
     def pterm(self, s):
         """Product-term halfword of slot or constant s: PCONST (constant) | the value's byte offset in its
         LDS table; the device address is lds + offset + (flag ? constants - lds : 0) (lcv_sop.hpp
@@ -979,121 +957,7 @@ def frob_ops(p, a, k, out):
     return ops
 
 
-def fexp_program_r03(team=12):
-    """f^((p^12 - 1)/r) * 3 (result e^3): easy part
-    (p^6 - 1)(p^2 + 1) with a team-parallel Fp12 inversion, hard part (x-1)^2 (x+p)(x^2+p^2-1) + 3."""
-    scaled = FEXP_SCALED if scaled is None else scaled
-    p = Program("fexp", team)
-    f = fp12_slots(p, "f")
-    c0 = [f[0], f[2], f[4]]   # Fp6 halves in the v basis
-    c1 = [f[1], f[3], f[5]]
-    # ---- t = c0^2 - v c1^2
-    t = [slots2(p) for _ in range(3)]
-    ops = []
-    for comp in range(2):
-        a, b = c0, c1
-        ops.append(Op(dst_of(t[0][comp]), fp2_sqr(a[0], comp) + fp2_prod(a[1], a[2], comp, True, 2) +
-                      fp2_sqr(b[1], comp, True, -1) + fp2_prod(b[0], b[2], comp, True, -2)))
-        ops.append(Op(dst_of(t[1][comp]), fp2_prod(a[0], a[1], comp, False, 2) + fp2_sqr(a[2], comp, True) +
-                      fp2_sqr(b[0], comp, False, -1) + fp2_prod(b[1], b[2], comp, True, -2)))
-        ops.append(Op(dst_of(t[2][comp]), fp2_sqr(a[1], comp) + fp2_prod(a[0], a[2], comp, False, 2) +
-                      fp2_prod(b[0], b[1], comp, False, -2) + fp2_sqr(b[2], comp, True, -1)))
-    p.round(ops)
-    # ---- s = adj(t): s0 = t0^2 - xi t1 t2, s1 = xi t2^2 - t0 t1, s2 = t1^2 - t0 t2
-    s = [slots2(p) for _ in range(3)]
-    ops = []
-    for comp in range(2):
-        ops.append(Op(dst_of(s[0][comp]), fp2_sqr(t[0], comp) + fp2_prod(t[1], t[2], comp, True, -1)))
-        ops.append(Op(dst_of(s[1][comp]), fp2_sqr(t[2], comp, True) + fp2_prod(t[0], t[1], comp, False, -1)))
-        ops.append(Op(dst_of(s[2][comp]), fp2_sqr(t[1], comp) + fp2_prod(t[0], t[2], comp, False, -1)))
-    p.round(ops)
-    # ---- d = t0 s0 + xi (t2 s1 + t1 s2)
-    d = slots2(p)
-    p.round([Op(dst_of(d[c]), fp2_prod(t[0], s[0], c) + fp2_prod(t[2], s[1], c, True) +
-                fp2_prod(t[1], s[2], c, True)) for c in range(2)])
-    # ---- n = d0^2 + d1^2 ; ninv
-    n = T(p.alloc())
-    p.round([Op(n.slot, [([d[0]], [d[0]], 1), ([d[1]], [d[1]], 1)])])
-    ninv = T(p.alloc())
-    p.round([Op(ninv.slot, [], [(n.slot, 1)], kind="inv")])
-    # ---- dinv = (d0 ninv, -d1 ninv) ; tinv = s * dinv
-    dinv = slots2(p)
-    p.round([Op(dst_of(dinv[0]), [([d[0]], [ninv], 1)]), Op(dst_of(dinv[1]), [([d[1]], [ninv], -1)])])
-    ti = [slots2(p) for _ in range(3)]
-    p.round([Op(dst_of(ti[i][c]), fp2_prod(s[i], dinv, c)) for i in range(3) for c in range(2)])
-    # ---- finv = (c0 * ti, -c1 * ti)   (Fp6 products)
-    fi = fp12_slots(p)
-    fi0 = [fi[0], fi[2], fi[4]]
-    fi1 = [fi[1], fi[3], fi[5]]
-    ops = []
-    for half, src, sign in ((fi0, c0, 1), (fi1, c1, -1)):
-        for k in range(3):
-            for comp in range(2):
-                prods = []
-                for i in range(3):
-                    j = (k - i) % 3
-                    prods += fp2_prod(src[i], ti[j], comp, xi=(i + j >= 3), m=sign)
-                ops.append(Op(dst_of(half[k][comp]), prods))
-    p.round(ops)
-    # ---- t1 = conj(f) * finv (in place over finv) ; m = frob2(t1) * t1 (frob2 into f's slots, m in place)
-    p.round(fp12_mul_ops(conj12(f), fi, fi))
-    t1 = fi
-    p.round(frob_ops(p, t1, 2, f))
-    p.round(fp12_mul_ops(f, t1, t1))
-    m = t1
-    for i in range(6):
-        for c in range(2):
-            p.named[f"m{i}_{c}"] = m[i][c].slot
-    dead = flat12(f) + [x for v in t + s + ti for x in v] + list(d) + list(dinv) + [n, ninv]
-    p.release([x.slot for x in dead])
-    acc = fp12_slots(p)
-    tmp = fp12_slots(p)
-
-    def exp_x(a, out):
-        """out = a^|x| (a cyclotomic; `out` must differ from a's slots)."""
-        firstsq = True
-        for bit in bin(X_ABS)[3:]:
-            p.round(cyclo_sqr_ops(a if firstsq else out, out))
-            firstsq = False
-            if bit == "1":
-                p.round(fp12_mul_ops(out, a, out))
-
-    # A = conj(exp_x(m) * m)          (A in tmp)
-    exp_x(m, acc)
-    p.round(fp12_mul_ops(acc, m, tmp))
-    A = conj12(tmp)
-    # A2 = conj(exp_x(A) * A)         (A2 in a fresh Fp12; A's slots become the next scratch)
-    exp_x(A, acc)
-    A2s = fp12_slots(p)
-    p.round(fp12_mul_ops(acc, A, A2s))
-    A2 = conj12(A2s)
-    # Bv = conj(exp_x(A2)) * frob1(A2)  (frob1 into tmp, Bv in place over tmp)
-    exp_x(A2, acc)
-    p.round(frob_ops(p, A2, 1, tmp))
-    p.round(fp12_mul_ops(conj12(acc), tmp, tmp))
-    Bv = tmp
-    # t = exp_x(exp_x(Bv))             (t in A2's slots)
-    exp_x(Bv, acc)
-    exp_x(acc, A2s)
-    # C = t * frob2(Bv) * conj(Bv)     (frob2 into acc, C in place over A2s)
-    p.round(frob_ops(p, Bv, 2, acc))
-    p.round(fp12_mul_ops(A2s, acc, A2s))
-    p.round(fp12_mul_ops(A2s, conj12(Bv), A2s))
-    C = A2s
-    # r = C * (cyclo_sqr(m) * m)       (r over m's slots)
-    p.round(cyclo_sqr_ops(m, acc))
-    p.round(fp12_mul_ops(acc, m, acc))
-    p.round(fp12_mul_ops(C, acc, m))
-    for i in range(6):
-        for c in range(2):
-            p.named[f"r{i}_{c}"] = m[i][c].slot
-    return p
-
-
-FEXP_SCALED = os.environ.get("LCV_SOP_FEXP_SCALED", "1") == "1"   # A/B: 0 = round 5's m-scaled chains
-
-
-def fexp_program(team=12, scaled=None):
+def fexp_program(team=12):
     """f^((p^12 - 1)/r) * 3 (result e^3), three live Fp12 values in the hard part (r04): easy part
     (p^6 - 1)(p^2 + 1) with a team-parallel Fp12 inversion whose temporaries are released as soon as
     they die, then with m = f^((p^6 - 1)(p^2 + 1)), x < 0, e() = exponentiation by |x| (e(a) = a^-x):
@@ -1102,11 +966,10 @@ def fexp_program(team=12, scaled=None):
         A2 = conj(e(A) A) = m^((x - 1)^2)               (in place)
         Bv = conj(e(A2)) frob1(A2) = A2^(x + p)          (frob1 in place, then the product)
         F2 = F2 frob2(Bv) conj(Bv);  F3 = e(Bv);  F1 = e(F3)
-        r  = F1 F2 = Bv^(x^2 + p^2 - 1) m^3              (the r03 order's value, fexp_program_r03)
+        r  = F1 F2 = Bv^(x^2 + p^2 - 1) m^3              (round 3's order gave the same value)
     Every product reads negated values only on its x side (fp2_prod negx, the exponentiation's running
     value), so the chains' bases need no shadow slots: LDS per item 79 -> fewer slots, a third wave per
     SIMD."""
-    scaled = FEXP_SCALED if scaled is None else scaled
     p = Program("fexp", team)
     f = fp12_slots(p, "f")
     c0 = [f[0], f[2], f[4]]   # Fp6 halves in the v basis
@@ -1179,7 +1042,7 @@ def fexp_program(team=12, scaled=None):
     F2 = fp12_slots(p)
     F3 = fp12_slots(p)
 
-    # Scaled chains (scaled = FEXP_SCALED, r06): each exponentiation's running value is stored as 3 z, so its
+    # Scaled chains: each exponentiation's running value is stored as 3 z, so its
     # 62 squarings after the first are Granger-Scott with m = 1 (products) and 2 (folded into a doubled
     # operand): no m-scaled product rounds (the device's m X costs 12 multiply-adds and as many moves per
     # product).  The first squaring reads the unscaled base (m = 9), the multiplications 3 z * a keep the
@@ -1188,21 +1051,16 @@ def fexp_program(team=12, scaled=None):
     inv3 = pow(3, -1, P)
 
     def exp_x(a, out):
-        """out = a^|x| (a cyclotomic; `out` must differ from a's slots); negated reads on out only.
-        scaled: out holds 3 a^|x|."""
+        """out = 3 a^|x| (a cyclotomic; `out` must differ from a's slots); negated reads on out only."""
         firstsq = True
         for bit in bin(X_ABS)[3:]:
-            if scaled:
-                p.round(cyclo_sqr_ops(a if firstsq else out, out, 1 if firstsq else 3, 3))
-            else:
-                p.round(cyclo_sqr_ops(a if firstsq else out, out))
+            p.round(cyclo_sqr_ops(a if firstsq else out, out, 1 if firstsq else 3, 3))
             firstsq = False
             if bit == "1":
                 p.round(fp12_mul_ops(out, a, out, negx=True))
 
     def unscale(v):
-        if scaled:
-            p.round(scale_ops(p, v, v, inv3))
+        p.round(scale_ops(p, v, v, inv3))
 
     # F2 = m^3 (negated reads on m, whose shadows the squarings need anyway)
     p.round(cyclo_sqr_ops(F1, F2))
@@ -1633,13 +1491,6 @@ def build():
     hp = h2c_program()
     mp = miller_program()
     progs = (lp, ap, fp, hp, mp)
-    perms = os.environ.get("LCV_SOP_SLOT_PERMS")  # experiment: JSON {program: perm}
-    if perms:
-        import json
-        for p, perm in json.load(open(perms)).items():
-            prog = {q.name: q for q in progs}[p]
-            prog.finalize()
-            prog.relabel(perm)
     return progs
 
 

@@ -11,6 +11,14 @@
 #include "lcv_field.hpp"
 using namespace lcv;
 
+// (hi:acc) += x y on a 96-bit accumulator: v_mad_u64_u32 (64-bit addend, carry-out to an SGPR pair) and
+// v_addc_co_u32 into the top word
+__device__ __forceinline__ void mac_vv(uint64_t& acc, uint32_t& hi, uint32_t x, uint32_t y) {
+  uint64_t cc;
+  asm("v_mad_u64_u32 %0, %1, %3, %4, %0\n\tv_addc_co_u32 %2, %1, %2, 0, %1"
+      : "+v"(acc), "=&s"(cc), "+v"(hi)
+      : "v"(x), "v"(y));
+}
 // (hi:acc) += (hi1:acc1)
 __device__ __forceinline__ void acc_merge(uint64_t& acc, uint32_t& hi, uint64_t acc1, uint32_t hi1) {
   uint32_t lo = (uint32_t)acc, mid = (uint32_t)(acc >> 32), c;
