@@ -6,13 +6,13 @@ subtraction then fully reduces it).  The host simulation itself runs the 64-bit-
 functions are otherwise only exercised on the GPU."""
 import ctypes
 import os
-import random
 import subprocess
 import tempfile
 
 import pytest
 
 import helpers as H
+import sop_vectors as V
 
 P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
 R = 1 << 384
@@ -45,16 +45,15 @@ def _v(w):
 
 
 def test_mul_sqr_lazy_operands(lib):
-    rng = random.Random(28)
-    edge = [0, 1, 2, P - 1, P, P + 1, 2 * P - 2, 2 * P - 1, (1 << 381) - 1, (1 << 381), 2 * P - (1 << 200)]
-    vals = edge + [rng.randrange(P, 2 * P) for _ in range(60)] + [rng.randrange(P) for _ in range(20)]
-    for i, a in enumerate(vals):
-        for b in (vals[(7 * i + 3) % len(vals)], vals[(5 * i + 1) % len(vals)], a):
-            r = (ctypes.c_uint32 * 13)()
-            lib.t_mul(r, _w(a), _w(b))
-            got = _v(r)
-            assert got < 2 * P, (hex(a), hex(b))
-            assert got % P == a * b * RINV % P, (hex(a), hex(b))
+    """The vectors: sop_vectors.c28_cases (shared with the device run, test_sop_arith_gpu.py)."""
+    cases = V.c28_cases()
+    assert len(cases) >= 3 * 91
+    for a, b in cases:
+        r = (ctypes.c_uint32 * 13)()
+        lib.t_mul(r, _w(a), _w(b))
+        got = _v(r)
+        assert got < 2 * P, (hex(a), hex(b))
+        assert got % P == a * b * RINV % P, (hex(a), hex(b))
         r = (ctypes.c_uint32 * 13)()
         lib.t_sqr(r, _w(a))
         got = _v(r)

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+import sop_vectors as V
 from oracle import bls12_381 as B
 
 pytestmark = pytest.mark.gpu
@@ -16,12 +17,23 @@ def _ints(row, k):
 
 
 def test_fp_ops(gpu_verifier):
+    """256 random pairs, then every pair of the values whose Montgomery representation (the value the device
+    computes on) is a limb pattern of sop_vectors.limb_patterns below p (saturated limbs, limb and word boundaries,
+    p less a limb unit, alternating limbs), then edge values for the inversion (paired with the patterns in turn)."""
     rng = np.random.default_rng(1)
     n = 256
     A = [int.from_bytes(rng.bytes(48), "big") % B.P for _ in range(n)]
     Bv = [int.from_bytes(rng.bytes(48), "big") % B.P for _ in range(n)]
     A[0], Bv[0] = 0, 0
     A[1], Bv[1] = B.P - 1, B.P - 1
+    edge = [m * V.RINV % B.P for m in V.limb_patterns() if m < B.P]
+    assert len(edge) >= 40
+    A += [x for x in edge for _ in edge]
+    Bv += [y for _ in edge for y in edge]
+    inv = [1, 2, B.P - 1, B.P - 2, (B.P + 1) // 2, (B.P - 1) // 2] + [1 << k for k in range(2, 381)]
+    A += inv
+    Bv += [edge[i % len(edge)] for i in range(len(inv))]
+    n = len(A)
     a = np.frombuffer(b"".join(x.to_bytes(48, "big") for x in A), np.uint8)
     b = np.frombuffer(b"".join(x.to_bytes(48, "big") for x in Bv), np.uint8)
     out, ok = gpu_verifier.debug_fp(a, b)

@@ -8,7 +8,8 @@ sop_kara_join / sop_redc28), checked two ways:
     middle column reaches 2^63, and tools/gen_sop.py's Program.col_bound / kara_bound (which set the
     round flags the device trusts) are at least the exact maxima.
 The host simulation runs the C++ itself on real data (test_tools_hostsim.py, the parity tests); this
-test covers the extreme operands the data never reaches."""
+test covers the extreme operands the data never reaches (test_sop_arith_cpu.py / test_sop_arith_gpu.py put the
+C++ itself through them, on the CPU and on the device)."""
 import os
 import random
 import sys

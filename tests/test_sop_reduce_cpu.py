@@ -6,13 +6,13 @@ correct only if the estimate is never above q, at most one below, and the skip t
 sit on and around every multiple of p up to 2^red p and around the skip threshold, where that matters."""
 import ctypes
 import os
-import random
 import subprocess
 import tempfile
 
 import pytest
 
 import helpers as H
+import sop_vectors as V
 
 P = 0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB
 CSRC = os.path.join(H.ROOT, "light-client-consensus-specs_amd", "csrc")
@@ -49,25 +49,10 @@ def _v(w, n=12):
 def test_sop_reduce_exact(lib, red):
     """Every multiple k p (and its neighbourhood) for red <= 5; for red 6..10 (tools/gen_sop.py allows
     red <= 10, the error analysis needs q < 2^15) sampled multiples: the smallest and the largest 24, and
-    100 random k."""
-    rng = random.Random(100 + red)
-    top = (1 << red) * P
-    vals = [0, 1, P - 1, top - 1, top - P]
-    ks = range(1, 1 << red)
-    if red > 5:
-        ks = sorted(set(list(range(1, 25)) + list(range((1 << red) - 24, 1 << red)) +
-                        [rng.randrange(1, 1 << red) for _ in range(100)]))
-    for k in ks:
-        vals += [k * P - 1, k * P, k * P + 1, k * P + (1 << 320) - 1, k * P - (1 << 320),
-                 k * P + rng.randrange(1 << 64), k * P - rng.randrange(1, 1 << 64)]
-        # around the device's skip threshold (fractional part of the estimate within ~2^-29 of 1)
-        for f in (27, 28, 29, 30, 31, 32, 36):
-            vals += [(k + 1) * P - (P >> f), k * P + (P >> f), (k + 1) * P - (P >> f) - 1]
-    vals += [rng.randrange(top) for _ in range(300)]
-    for use_table in ((0, 1) if red <= 3 else (0,)):
-        for v in vals:
-            if not 0 <= v < top:
-                continue
-            r = _w(v)
-            lib.t_reduce(r, red, use_table)
-            assert _v(r) == v % P and int(r[12]) == 0, (red, use_table, hex(v))
+    100 random k.  The vectors: sop_vectors.reduce_cases (shared with the device run, test_sop_arith_gpu.py)."""
+    cases = [c for c in V.reduce_cases() if c[1] == red]
+    assert len(cases) > 300
+    for v, _, use_table in cases:
+        r = _w(v)
+        lib.t_reduce(r, red, use_table)
+        assert _v(r) == v % P and int(r[12]) == 0, (red, use_table, hex(v))
