@@ -112,6 +112,40 @@ int lcv_set_store(lcv_ctx* ctx, uint64_t finalized_slot, const uint8_t* current_
 /* host batch in, verdict (1 = valid) and reason code (lcv_reason) out, one byte per update */
 int lcv_validate_updates(lcv_ctx* ctx, const lcv_update_batch* batch, uint64_t current_slot,
                          const uint8_t* genesis_validators_root, uint8_t* verdict_out, uint8_t* reason_out);
+/* ---- a store per update: the store table.  lcv_set_store holds ONE snapshot, and every row of a batch is
+ * validated against it.  Two uses of the reference do not fit that: catching up over sync-committee periods
+ * (light-client.md step 4.2, p2p-interface.md LightClientUpdatesByRange: one update per period, each meeting the
+ * store the previous one left, whose committees have rotated), and serving light clients whose stores differ.
+ * The table form: `committees` are the distinct SSZ SyncCommittee values (any order, duplicates allowed), a store
+ * row s is (finalized_slot[s], current[s], next[s]) with the committees given as rows of that table, and update i
+ * is validated against store row store_index[i].  next[s] = LCV_STORE_NEXT_UNKNOWN, or a committee row whose
+ * 24624 bytes are all zero, means "not known" (sync-protocol.md:316-317), as lcv_set_store's all-zero next does.
+ * lcv_set_store_table copies the committees to the device, decodes and KeyValidates all ncomm x 512 keys once
+ * (key_status_out, optional, ncomm x 512: 0 valid key, 2 invalid; kernel time in lcv_last_timings' "setup"
+ * stage) and keeps the store columns device resident.  It is independent of lcv_set_store: neither call touches
+ * what the other set.  Both calls check every index on the host before any kernel is launched — current[s] <
+ * ncomm, next[s] < ncomm or the sentinel, ncomm <= LCV_STORE_TABLE_MAX_COMMITTEES, store_index[i] < nstore — and
+ * return LCV_EINVAL naming the first offending index; lcv_validate_updates_stores before a table is set returns
+ * LCV_ESTATE.
+ * lcv_validate_updates_stores is synchronous, host buffers in and out, like lcv_validate_updates: batches above
+ * the chunk size are cut the same way, and batches of at most lcv_set_latency_mode's rows run on the fan engine.
+ * It always runs the serial shape: lcv_set_pipeline does not apply to it.  Verdicts and reasons are those of
+ * lcv_set_store(store row) + lcv_validate_updates(update), row by row.  There is no async, resident or sharded
+ * form of it. */
+#define LCV_STORE_NEXT_UNKNOWN 0xFFFFFFFFu
+#define LCV_STORE_TABLE_MAX_COMMITTEES 4096
+typedef struct lcv_store_table {
+  const uint8_t* committees;      /* ncomm x 24624 SSZ SyncCommittee, any order, duplicates allowed */
+  uint64_t ncomm;
+  const uint64_t* finalized_slot; /* nstore: store.finalized_header.beacon.slot */
+  const uint32_t* current;        /* nstore: committee row of store.current_sync_committee */
+  const uint32_t* next;           /* nstore: committee row of store.next_sync_committee, or LCV_STORE_NEXT_UNKNOWN */
+  uint64_t nstore;
+} lcv_store_table;
+int lcv_set_store_table(lcv_ctx* ctx, const lcv_store_table* table, uint8_t* key_status_out);
+int lcv_validate_updates_stores(lcv_ctx* ctx, const lcv_update_batch* batch, const uint32_t* store_index,
+                                uint64_t current_slot, const uint8_t* genesis_validators_root,
+                                uint8_t* verdict_out, uint8_t* reason_out);
 /* device-resident batches: upload once, validate many times (timed region excludes the upload) */
 int lcv_batch_upload(lcv_ctx* ctx, const lcv_update_batch* batch, lcv_dbatch** out);
 void lcv_batch_free(lcv_ctx* ctx, lcv_dbatch* b);

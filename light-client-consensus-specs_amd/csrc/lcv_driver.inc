@@ -67,6 +67,13 @@ struct lcv_ctx {
   NetConfig cfg = net_config_mainnet();  // lcv_set_config
   CommitteeBufs store;
   CommitteeBufs adhoc;  // committee tables of FastAggregateVerify calls
+  // store table (lcv_set_store_table): its committees, decoded and summed like the store's, and the per-store
+  // columns (finalized slot, current row, next row or STORE_NEXT_UNKNOWN), one device allocation
+  bool table_set = false;
+  CommitteeBufs table;
+  void* table_mem = nullptr;
+  size_t table_store_cap = 0;
+  StoreDev table_dev = {nullptr, nullptr, nullptr, 0};
   std::vector<uint8_t> adhoc_src;  // the bytes `adhoc` was built from (reused while calls repeat them)
   // work space
   // work spaces: slot 0 serves every synchronous call; slots 0 and 1 alternate under
@@ -196,7 +203,8 @@ static int ensure_work(lcv_ctx* ctx, size_t cap, size_t pool_cap, int slot = 0) 
   const size_t C = cap, Pc = pool_cap;
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_msg = take(32 * C), o_pre = take(C), o_comm = take(4 * C), o_nroot = take(32 * Pc), o_nfl = take(Pc),
+  const size_t o_msg = take(32 * C), o_pre = take(C), o_comm = take(4 * C), o_nsceq = take(C),
+               o_nroot = take(32 * Pc), o_nfl = take(Pc),
                o_qmap = take(384 * C), o_qh = take(192 * C), o_qhinf = take(C), o_qs = take(192 * C), o_sst = take(C), o_pk = take(96 * C),
                o_ast = take(C), o_f = take(576 * C), o_pok = take(C), o_ver = take(C),
                o_rea = take(C), o_lines = take((size_t)4 * SOP_LINE_WORDS * C);
@@ -213,6 +221,7 @@ static int ensure_work(lcv_ctx* ctx, size_t cap, size_t pool_cap, int slot = 0) 
   W.comm_id = (uint32_t*)(m + o_comm);
   W.nsc_root = (uint32_t*)(m + o_nroot);
   W.nsc_flags = m + o_nfl;
+  W.nsc_eq = m + o_nsceq;
   W.qmap = (uint32_t*)(m + o_qmap);
   W.qh = (uint32_t*)(m + o_qh);
   W.qh_inf = m + o_qhinf;
@@ -301,7 +310,7 @@ static int upload_sop(lcv_ctx* ctx) {
 // same layout with the pointers advanced by `base` (the committee-pool arrays are not per item)
 static Work work_view(const Work& W, size_t base) {
   Work v = W;
-  v.msg += base; v.pre_reason += base; v.comm_id += base; v.qmap += base; v.qh += base; v.qh_inf += base;
+  v.msg += base; v.pre_reason += base; v.comm_id += base; v.nsc_eq += base; v.qmap += base; v.qh += base; v.qh_inf += base;
   v.qs += base; v.sig_status += base; v.pk += base; v.agg_status += base; v.pair_ok += base;
   v.verdict += base; v.reason += base;
   v.f += base * 144;  // item-major (lcv_items.hpp f12_st_coeff)
@@ -375,6 +384,16 @@ static int agg_stage(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, con
   return LCV_OK;
 }
 
+// the non-BLS asserts of items [0, n): against the context's store, or (S: lcv_validate_updates_stores) each update
+// against its own row of the store table — the per-update committee equality (item_nsc_eq_team) then runs ahead
+// of the table form of item_pre on the same stream
+static int pre_stage(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, const Params& P, const StoreDev* S,
+                     const Work& W, uint32_t n) {
+  if (!S) return be_launch(ctx, F_pre{B, C, P, W}, n);
+  LCV_TRY(be_launch_team(ctx, F_nsc_eq_team{B, C, *S, P, W}, n));
+  return be_launch(ctx, F_pre_table{B, *S, P, W}, n);
+}
+
 // The BLS half of the pipeline for items [0, n) on two streams of the active slot (a main stream and a
 // side stream), ordered by events:
 //   side: [HTR(next_sync_committee)] [item_pre: reasons, committee ids], signature decode, [masked
@@ -388,15 +407,15 @@ static int agg_stage(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, con
 // updates/s).  P (validate) adds item_pre and the signing root; nsc (first chunk) adds the committee
 // roots; FastAggregateVerify passes neither (its W.msg / W.comm_id are set by the caller).
 // agg_items > n (FastAggregateVerify of > 512 keys, n == 1): the aggregation runs over agg_items
-// slices and item_agg_fold sums them into item 0.
+// slices and item_agg_fold sums them into item 0.  S: the store table of lcv_validate_updates_stores (pre_stage).
 static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint32_t n, uint32_t agg_items = 0,
-                   const Params* P = nullptr, const BatchDev* nsc = nullptr) {
+                   const Params* P = nullptr, const BatchDev* nsc = nullptr, const StoreDev* S = nullptr) {
   const Work& W = ctx->W;
 #if defined(LCV_CPU_FAST)
   if (!W.msg_b0) {  // CPU-baseline build: direct per-update code (lcv_cpu_direct.hpp), one core per update
     if (nsc) LCV_TRY(be_launch_team(ctx, F_nsc_team{*nsc, C, W}, nsc->npool));
     if (P) {
-      LCV_TRY(be_launch(ctx, F_pre{B, C, *P, W}, n));
+      LCV_TRY(pre_stage(ctx, B, C, *P, S, W, n));
       LCV_TRY(be_launch(ctx, F_sigroot{B, *P, W}, n));
     }
     be_stage_begin(ctx, ST_SIG);
@@ -428,7 +447,7 @@ static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint3
   }
   if (P) {
     be_stage_begin(ctx, ST_PRE);
-    LCV_TRY(be_launch(ctx, F_pre{B, C, *P, W}, n));
+    LCV_TRY(pre_stage(ctx, B, C, *P, S, W, n));
     be_stage_end(ctx, ST_PRE);
   }
   be_stage_begin(ctx, ST_SIG);
@@ -538,7 +557,8 @@ int lcv_init(int device, lcv_ctx** out) {
 
 void lcv_destroy(lcv_ctx* ctx) {
   if (!ctx) return;
-  for (CommitteeBufs* cb : {&ctx->store, &ctx->adhoc}) {
+  if (ctx->table_mem) be_free(ctx, ctx->table_mem);
+  for (CommitteeBufs* cb : {&ctx->store, &ctx->adhoc, &ctx->table}) {
     if (cb->raw) { be_free(ctx, cb->raw); be_free(ctx, cb->pts); be_free(ctx, cb->sum_all); be_free(ctx, cb->badmask); be_free(ctx, cb->key_status); }
   }
   for (int k = 0; k < LCV_SLOTS; ++k)
@@ -577,26 +597,29 @@ int lcv_set_store(lcv_ctx* ctx, uint64_t finalized_slot, const uint8_t* cur, con
 
 }  // extern "C"
 
-// the 13 columns of a packed batch, each at a 256-byte aligned offset of one device allocation
+// the 13 columns of a packed batch, and the per-update store-table rows of lcv_validate_updates_stores (column
+// 13: empty otherwise), each at a 256-byte aligned offset of one device allocation
+enum { BATCH_COLS = 14 };
 struct BatchCols {
-  const void* src[13];
-  size_t bytes[13], off[13];
+  const void* src[BATCH_COLS];
+  size_t bytes[BATCH_COLS], off[BATCH_COLS];
   size_t total = 0, n = 0, np = 0;
 };
 
-static int batch_cols(lcv_ctx* ctx, const lcv_update_batch* hb, BatchCols& c, const char* who) {
+static int batch_cols(lcv_ctx* ctx, const lcv_update_batch* hb, BatchCols& c, const char* who,
+                      const uint32_t* store_index = nullptr) {
   const size_t n = hb->n, np = hb->npool;
   if (n == 0 || np == 0 || n > 0xffffffffull || np > 0xffffffffull)
     return fail(ctx, LCV_EINVAL, std::string(who) + ": need 0 < n, 0 < npool < 2^32");
-  const void* src[13] = {hb->attested.beacon, hb->attested.execution, hb->attested.exec_branch,
+  const void* src[BATCH_COLS] = {hb->attested.beacon, hb->attested.execution, hb->attested.exec_branch,
                          hb->finalized.beacon, hb->finalized.execution, hb->finalized.exec_branch,
                          hb->nsc_pool, hb->nsc_index, hb->nsc_branch, hb->finality_branch,
-                         hb->sync_bits, hb->sync_signature, hb->signature_slot};
-  const size_t bytes[13] = {112 * n, 832 * n, 128 * n, 112 * n, 832 * n, 128 * n, (size_t)K_SC * np, 4 * n,
-                            160 * n, 192 * n, 64 * n, 96 * n, 8 * n};
+                         hb->sync_bits, hb->sync_signature, hb->signature_slot, store_index};
+  const size_t bytes[BATCH_COLS] = {112 * n, 832 * n, 128 * n, 112 * n, 832 * n, 128 * n, (size_t)K_SC * np, 4 * n,
+                                    160 * n, 192 * n, 64 * n, 96 * n, 8 * n, store_index ? 4 * n : 0};
   c.total = 0;
-  for (int k = 0; k < 13; ++k) {
-    if (!src[k]) return fail(ctx, LCV_EINVAL, std::string(who) + ": null column");
+  for (int k = 0; k < BATCH_COLS; ++k) {
+    if (!src[k] && k < 13) return fail(ctx, LCV_EINVAL, std::string(who) + ": null column");
     c.src[k] = src[k];
     c.bytes[k] = bytes[k];
     c.off[k] = c.total;
@@ -617,6 +640,7 @@ static void bind_batch(lcv_dbatch* db, uint8_t* m, const BatchCols& c) {
   B.nsc_pool = m + c.off[6]; B.nsc_index = (const uint32_t*)(m + c.off[7]); B.nsc_branch = m + c.off[8];
   B.finality_branch = m + c.off[9]; B.bits = m + c.off[10]; B.sig = m + c.off[11];
   B.sig_slot = (const uint64_t*)(m + c.off[12]);
+  B.store_index = c.bytes[13] ? (const uint32_t*)(m + c.off[13]) : nullptr;
   B.n = (uint32_t)c.n;
   B.npool = (uint32_t)c.np;
   db->n = c.n;
@@ -625,17 +649,17 @@ static void bind_batch(lcv_dbatch* db, uint8_t* m, const BatchCols& c) {
 
 extern "C" {
 
-int lcv_batch_upload(lcv_ctx* ctx, const lcv_update_batch* hb, lcv_dbatch** out) {
+static int batch_upload(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index, lcv_dbatch** out) {
   if (!ctx || !hb || !out) return fail(ctx, LCV_EINVAL, "lcv_batch_upload: null argument");
   *out = nullptr;
   BatchCols c;
-  LCV_TRY(batch_cols(ctx, hb, c, "lcv_batch_upload"));
+  LCV_TRY(batch_cols(ctx, hb, c, "lcv_batch_upload", store_index));
   lcv_dbatch* db = new (std::nothrow) lcv_dbatch();
   if (!db) return LCV_ENOMEM;
   int rc = be_alloc(ctx, &db->mem, c.total);
   if (rc != LCV_OK) { delete db; return rc; }
   uint8_t* m = (uint8_t*)db->mem;
-  for (int k = 0; k < 13; ++k) {
+  for (int k = 0; k < BATCH_COLS; ++k) {
     rc = be_h2d(ctx, m + c.off[k], c.src[k], c.bytes[k]);
     if (rc != LCV_OK) { be_free(ctx, db->mem); delete db; return rc; }
   }
@@ -644,6 +668,10 @@ int lcv_batch_upload(lcv_ctx* ctx, const lcv_update_batch* hb, lcv_dbatch** out)
   if (rc != LCV_OK) { be_free(ctx, db->mem); delete db; return rc; }
   *out = db;
   return LCV_OK;
+}
+
+int lcv_batch_upload(lcv_ctx* ctx, const lcv_update_batch* hb, lcv_dbatch** out) {
+  return batch_upload(ctx, hb, nullptr, out);
 }
 
 void lcv_batch_free(lcv_ctx* ctx, lcv_dbatch* b) {
@@ -658,6 +686,7 @@ static BatchDev chunk_view(const BatchDev& B, size_t base, uint32_t n) {
   c.fin_beacon += 112 * base; c.fin_exec += 832 * base; c.fin_branch += 128 * base;
   c.nsc_index += base; c.nsc_branch += 160 * base; c.finality_branch += 192 * base;
   c.bits += 64 * base; c.sig += 96 * base; c.sig_slot += base;
+  if (c.store_index) c.store_index += base;
   c.n = n;
   return c;
 }
@@ -665,9 +694,14 @@ static BatchDev chunk_view(const BatchDev& B, size_t base, uint32_t n) {
 // out_host: verdict/reason to host memory; out_dev: verdicts to a device buffer
 static int host_alloc_grow(lcv_ctx* ctx, uint8_t** p, size_t* cap, size_t bytes);
 static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, const uint8_t* gvr, uint8_t* verdict_host,
-                         uint8_t* reason_host, uint8_t* verdict_dev, int slot = -1) {
+                         uint8_t* reason_host, uint8_t* verdict_dev, int slot = -1, bool table = false) {
   if (!ctx || !db || !gvr) return fail(ctx, LCV_EINVAL, "validate: null argument");
-  if (!ctx->store_set) return fail(ctx, LCV_ESTATE, "validate: lcv_set_store has not been called");
+  // table: every update against its own row of the store table (db->B.store_index, checked by the caller)
+  if (table) {
+    if (!ctx->table_set || !db->B.store_index) return fail(ctx, LCV_ESTATE, "validate: lcv_set_store_table has not been called");
+  } else if (!ctx->store_set) {
+    return fail(ctx, LCV_ESTATE, "validate: lcv_set_store has not been called");
+  }
   const bool async = slot >= 0;  // lcv_validate_resident_async: enqueue on the slot's streams, no wait
   const size_t n = db->n;
   if (async && n > ctx->chunk) return fail(ctx, LCV_EINVAL, "lcv_validate_resident_async: at most 65536 updates per call");
@@ -684,10 +718,12 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
   P.store_fin_slot = ctx->store_fin_slot;
   P.next_known = ctx->next_known;
   for (int k = 0; k < 8; ++k) P.gvr[k] = host_be32(gvr + 4 * k);
-  CommitteeDev C = committee_view(ctx->store, ctx->store.raw + K_SC);
+  // (the table path never reads the pool rows' store-equality flag: item_nsc_team gets a valid row to compare)
+  CommitteeDev C = table ? committee_view(ctx->table, ctx->table.raw) : committee_view(ctx->store, ctx->store.raw + K_SC);
+  const StoreDev* S = table ? &ctx->table_dev : nullptr;
   if (!async) be_reset_timings(ctx);
   const int ns = ctx->pipe_streams < 4 ? ctx->pipe_streams : 4;  // lcv_set_pipeline: min(streams, 4)
-  const bool piped = !async && ns > 1 && ctx->pipe_chunks > 1;
+  const bool piped = !async && !table && ns > 1 && ctx->pipe_chunks > 1;  // (the table path: serial shape)
   bool pinned_out = false;
   auto body = [&]() -> int {
     if (piped) {  // sliced chains on `ns` streams (lcv_set_pipeline): the committee roots come first
@@ -717,7 +753,7 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
         const size_t base = c * cap;
         const uint32_t m = (uint32_t)((n - base) < cap ? (n - base) : cap);
         // every slot's first chunk also hashes the committee pool into that slot's work space
-        LCV_TRY(run_bls(ctx, chunk_view(db->B, base, m), C, m, 0, &P, c < (size_t)LCV_SLOTS ? &db->B : nullptr));
+        LCV_TRY(run_bls(ctx, chunk_view(db->B, base, m), C, m, 0, &P, c < (size_t)LCV_SLOTS ? &db->B : nullptr, S));
       }
       for (size_t c = nchunks > (size_t)LCV_SLOTS ? nchunks - LCV_SLOTS : 0; c < nchunks; ++c) LCV_TRY(finish(c));
       LCV_TRY(be_sync(ctx));
@@ -744,7 +780,7 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
         be_use_stream(ctx, 0);
         for (int k = 1; k < ns; ++k) LCV_TRY(be_join_from(ctx, k));
       } else {
-        LCV_TRY(run_bls(ctx, B, C, m, 0, &P, (!piped && base == 0) ? &db->B : nullptr));
+        LCV_TRY(run_bls(ctx, B, C, m, 0, &P, (!piped && base == 0) ? &db->B : nullptr, S));
       }
       if (!async && n <= cap && (verdict_host || reason_host)) {
         // one chunk: both arrays into pinned memory without a wait each, handed out after the sync below
@@ -821,7 +857,7 @@ static void stage_columns(uint8_t* dst, const BatchCols& c) {
   struct Piece { uint8_t* d; const uint8_t* s; size_t b; };
   std::vector<Piece> pieces;
   const size_t kPiece = (size_t)1 << 20;
-  for (int k = 0; k < 13; ++k)
+  for (int k = 0; k < BATCH_COLS; ++k)
     for (size_t o = 0; o < c.bytes[k]; o += kPiece)
       pieces.push_back({dst + c.off[k] + o, (const uint8_t*)c.src[k] + o, c.bytes[k] - o < kPiece ? c.bytes[k] - o : kPiece});
   const size_t nt = c.total >= ((size_t)8 << 20) ? 4 : 1;
@@ -913,14 +949,17 @@ int lcv_slot_wait(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint
   return rc;
 }
 
-int lcv_validate_updates(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t current_slot, const uint8_t* gvr,
-                         uint8_t* verdict_out, uint8_t* reason_out) {
-  if (ctx && hb && gvr && ctx->store_set && hb->n > 0 && hb->n <= ctx->chunk) {
+// host batch in, verdicts out, synchronous: against the context's store (store_index null) or, row by row,
+// against the store table
+static int validate_host(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index, uint64_t current_slot,
+                         const uint8_t* gvr, uint8_t* verdict_out, uint8_t* reason_out) {
+  const bool table = store_index != nullptr;
+  if (ctx && hb && gvr && (table ? ctx->table_set : ctx->store_set) && hb->n > 0 && hb->n <= ctx->chunk) {
     // one chunk (the reference's per-update call shape among them): the columns go through a reused pinned
     // staging buffer and ONE DMA into a reused device copy (lcv_validate_async's path, waited for here)
     // instead of a device allocation, one copy per column and a free per call
     BatchCols c;
-    LCV_TRY(batch_cols(ctx, hb, c, "lcv_validate_updates"));
+    LCV_TRY(batch_cols(ctx, hb, c, "lcv_validate_updates", store_index));
     HostSlot& h = ctx->hsync;
     be_set_slot(ctx, 0);
     int rc = host_alloc_grow(ctx, &h.pinned, &h.pinned_cap, c.total);
@@ -936,14 +975,96 @@ int lcv_validate_updates(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t curr
     be_set_slot(ctx, 0);
     LCV_TRY(be_h2d(ctx, h.dev, h.pinned, c.total));
     bind_batch(&h.db, (uint8_t*)h.dev, c);
-    return validate_impl(ctx, &h.db, current_slot, gvr, verdict_out, reason_out, nullptr);  // returns synced
+    return validate_impl(ctx, &h.db, current_slot, gvr, verdict_out, reason_out, nullptr, -1, table);  // returns synced
   }
   // larger batches (and invalid arguments, reported by the upload): a device batch per call
   lcv_dbatch* db = nullptr;
-  LCV_TRY(lcv_batch_upload(ctx, hb, &db));
-  int rc = validate_impl(ctx, db, current_slot, gvr, verdict_out, reason_out, nullptr);
+  LCV_TRY(batch_upload(ctx, hb, store_index, &db));
+  int rc = validate_impl(ctx, db, current_slot, gvr, verdict_out, reason_out, nullptr, -1, table);
   lcv_batch_free(ctx, db);
   return rc;
+}
+
+int lcv_validate_updates(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t current_slot, const uint8_t* gvr,
+                         uint8_t* verdict_out, uint8_t* reason_out) {
+  return validate_host(ctx, hb, nullptr, current_slot, gvr, verdict_out, reason_out);
+}
+
+// ---- store table: a store snapshot per update (a catch-up over several sync-committee periods, whose updates
+// each meet the store the previous ones left; or the updates of many light clients in one batch).  Every index
+// a kernel follows is checked here, on the host, before anything is launched.
+int lcv_set_store_table(lcv_ctx* ctx, const lcv_store_table* t, uint8_t* key_status_out) {
+  if (!ctx || !t || !t->committees || !t->finalized_slot || !t->current || !t->next)
+    return fail(ctx, LCV_EINVAL, "lcv_set_store_table: null argument");
+  if (t->ncomm == 0 || t->ncomm > LCV_STORE_TABLE_MAX_COMMITTEES)
+    return fail(ctx, LCV_EINVAL, "lcv_set_store_table: ncomm " + std::to_string(t->ncomm) + " is not in 1.." +
+                                     std::to_string(LCV_STORE_TABLE_MAX_COMMITTEES));
+  if (t->nstore == 0 || t->nstore > 0xffffffffull) return fail(ctx, LCV_EINVAL, "lcv_set_store_table: need 0 < nstore < 2^32");
+  const size_t nc = t->ncomm, ns = t->nstore;
+  for (size_t s = 0; s < ns; ++s) {
+    if (t->current[s] >= nc)
+      return fail(ctx, LCV_EINVAL, "lcv_set_store_table: current[" + std::to_string(s) + "] = " +
+                                       std::to_string(t->current[s]) + " is not a committee row (ncomm " + std::to_string(nc) + ")");
+    if (t->next[s] >= nc && t->next[s] != LCV_STORE_NEXT_UNKNOWN)
+      return fail(ctx, LCV_EINVAL, "lcv_set_store_table: next[" + std::to_string(s) + "] = " + std::to_string(t->next[s]) +
+                                       " is neither a committee row (ncomm " + std::to_string(nc) + ") nor LCV_STORE_NEXT_UNKNOWN");
+  }
+  // an all-zero committee as `next` means "not known" (is_next_sync_committee_known, sync-protocol.md:316-317):
+  // decided once per committee row, here
+  std::vector<uint8_t> zero_row(nc, 0);
+  for (size_t c = 0; c < nc; ++c) {
+    const uint8_t* row = t->committees + (size_t)K_SC * c;
+    uint32_t any = 0;
+    for (int k = 0; k < K_SC; ++k) any |= row[k];
+    zero_row[c] = any ? 0 : 1;
+  }
+  const size_t o_cur = (8 * ns + 255) & ~(size_t)255, o_next = o_cur + ((4 * ns + 255) & ~(size_t)255),
+               bytes = o_next + ((4 * ns + 255) & ~(size_t)255);
+  std::vector<uint32_t> next(ns);
+  for (size_t s = 0; s < ns; ++s)
+    next[s] = (t->next[s] == LCV_STORE_NEXT_UNKNOWN || zero_row[t->next[s]]) ? (uint32_t)STORE_NEXT_UNKNOWN : t->next[s];
+  ctx->table_set = false;
+  be_set_slot(ctx, 0);
+  auto body = [&]() -> int {
+    LCV_TRY(ensure_committees(ctx, ctx->table, nc, K_SC));
+    if (ns > ctx->table_store_cap || !ctx->table_mem) {
+      if (ctx->table_mem) be_free(ctx, ctx->table_mem);
+      ctx->table_mem = nullptr;
+      ctx->table_store_cap = 0;
+      LCV_TRY(be_alloc(ctx, &ctx->table_mem, bytes));
+      ctx->table_store_cap = ns;
+    }
+    uint8_t* m = (uint8_t*)ctx->table_mem;
+    LCV_TRY(be_h2d(ctx, ctx->table.raw, t->committees, (size_t)K_SC * nc));
+    LCV_TRY(be_h2d(ctx, m, t->finalized_slot, 8 * ns));
+    LCV_TRY(be_h2d(ctx, m + o_cur, t->current, 4 * ns));
+    LCV_TRY(be_h2d(ctx, m + o_next, next.data(), 4 * ns));
+    ctx->table_dev = StoreDev{(const uint64_t*)m, (const uint32_t*)(m + o_cur), (const uint32_t*)(m + o_next), (uint32_t)ns};
+    be_reset_timings(ctx);
+    LCV_TRY(build_committees(ctx, ctx->table));
+    if (key_status_out) LCV_TRY(be_d2h(ctx, key_status_out, ctx->table.key_status, 512 * nc));
+    return LCV_OK;
+  };
+  int rc = body();
+  const int rs = be_sync(ctx);  // (also after a failure: `next` leaves scope with no copy pending)
+  if (rc == LCV_OK) rc = rs;
+  if (rc != LCV_OK) return rc;
+  be_collect_timings(ctx);  // the table build's kernel time: lcv_last_timings' setup stage
+  ctx->table_set = true;
+  return LCV_OK;
+}
+
+int lcv_validate_updates_stores(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index,
+                                uint64_t current_slot, const uint8_t* gvr, uint8_t* verdict_out, uint8_t* reason_out) {
+  if (!ctx || !hb || !store_index || !gvr) return fail(ctx, LCV_EINVAL, "lcv_validate_updates_stores: null argument");
+  if (!ctx->table_set) return fail(ctx, LCV_ESTATE, "lcv_validate_updates_stores: lcv_set_store_table has not been called");
+  if (hb->n == 0 || hb->n > 0xffffffffull) return fail(ctx, LCV_EINVAL, "lcv_validate_updates_stores: need 0 < n < 2^32");
+  for (uint64_t i = 0; i < hb->n; ++i)
+    if (store_index[i] >= ctx->table_dev.nstore)
+      return fail(ctx, LCV_EINVAL, "lcv_validate_updates_stores: store_index[" + std::to_string(i) + "] = " +
+                                       std::to_string(store_index[i]) + " is not a store row (nstore " +
+                                       std::to_string(ctx->table_dev.nstore) + ")");
+  return validate_host(ctx, hb, store_index, current_slot, gvr, verdict_out, reason_out);
 }
 
 // The communication buffer never blocks a collective call: lcv_comm_init sizes it for every slot's largest
@@ -1131,6 +1252,7 @@ static int work_fields(const Work& W, FieldRef* f) {
   f[n++] = {"msg", (const uint8_t*)W.msg, 4, 8, 0};
   f[n++] = {"pre_reason", W.pre_reason, 1, 1, 0};
   f[n++] = {"comm_id", (const uint8_t*)W.comm_id, 4, 1, 0};
+  f[n++] = {"nsc_eq", W.nsc_eq, 1, 1, 0};
   f[n++] = {"qmap", (const uint8_t*)W.qmap, 4, 96, 0};
   f[n++] = {"qh", (const uint8_t*)W.qh, 4, 48, 0};
   f[n++] = {"qh_inf", W.qh_inf, 1, 1, 0};

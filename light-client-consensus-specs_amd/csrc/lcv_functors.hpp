@@ -13,6 +13,17 @@ struct F_nsc_team {
   LCV_HD void operator()(uint32_t j, uint32_t lane, uint32_t r, uint32_t* lds, uint32_t*) const { item_nsc_team(j, lane, r, lds, B, C, W); }
 };
 struct F_pre { BatchDev B; CommitteeDev C; Params P; Work W; LCV_HD void operator()(uint32_t i) const { item_pre(i, B, C, P, W); } };
+// store-table path (lcv_validate_updates_stores): the pre-checks against each update's own store row, after the
+// per-update next_sync_committee == store.next_sync_committee test (one wave per update, item_nsc_eq_team)
+struct F_pre_table { BatchDev B; StoreDev S; Params P; Work W; LCV_HD void operator()(uint32_t i) const { item_pre_table(i, B, S, P, W); } };
+struct F_nsc_eq_team {
+  BatchDev B; CommitteeDev C; StoreDev S; Params P; Work W;
+  static constexpr uint32_t TEAM = NSCEQ_TEAM, LDS_WORDS = NSCEQ_LDS, SHARED_WORDS = 0;
+  LCV_HD uint32_t rounds() const { return NSCEQ_ROUNDS; }
+  LCV_HD void operator()(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, uint32_t*) const {
+    item_nsc_eq_team(i, lane, r, lds, B, C, S, P, W);
+  }
+};
 struct F_sigroot { BatchDev B; Params P; Work W; LCV_HD void operator()(uint32_t i) const { item_sigroot(i, B, P, W); } };
 struct F_h2c_map { Work W; LCV_HD void operator()(uint32_t t) const { item_h2c_map(t, W); } };
 struct F_sig { BatchDev B; Work W; LCV_HD void operator()(uint32_t i) const { item_sig(i, B, W); } };

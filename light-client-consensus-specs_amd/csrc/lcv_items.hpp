@@ -39,6 +39,7 @@ struct BatchDev {
   const uint64_t* sig_slot;
   uint32_t n;
   uint32_t npool;
+  const uint32_t* store_index;  // [n] row of the store table update i is validated against (lcv_validate_updates_stores), else null
 };
 
 struct Params {
@@ -60,6 +61,17 @@ struct CommitteeDev {
   uint32_t ncomm;
 };
 
+// Store table (lcv_set_store_table): one row per store snapshot, its committees as rows of the committee table
+// (CommitteeDev).  `next` holds STORE_NEXT_UNKNOWN where the store's next committee is not known (the caller's
+// sentinel, or an all-zero committee row: decided on the host when the table is set)
+enum : uint32_t { STORE_NEXT_UNKNOWN = 0xFFFFFFFFu };
+struct StoreDev {
+  const uint64_t* fin_slot;  // [nstore] store.finalized_header.beacon.slot
+  const uint32_t* cur;       // [nstore] committee row of store.current_sync_committee
+  const uint32_t* next;      // [nstore] committee row of store.next_sync_committee, or STORE_NEXT_UNKNOWN
+  uint32_t nstore;
+};
+
 struct Work {
   uint32_t cap;
   uint32_t pool_cap;
@@ -68,6 +80,7 @@ struct Work {
   uint32_t* comm_id;     // [cap] committee used for the signature (0 current, 1 next)
   uint32_t* nsc_root;    // [8][pool_cap]
   uint8_t* nsc_flags;    // [pool_cap] bit0: all-zero, bit1: equals store.next_sync_committee
+  uint8_t* nsc_eq;       // [cap] store-table path: update i's next_sync_committee equals ITS store's (item_nsc_eq_team)
   uint32_t* qmap;        // [96][cap] the two SSWU outputs on E2' (affine, 8 Fp: x0,x1,y0,y1 per map)
   uint32_t* qh;          // [48][cap] H(m) affine (x0,x1,y0,y1)
   uint8_t* qh_inf;       // [cap]
@@ -208,8 +221,13 @@ LCV_FN uint32_t popcount_bits(const uint8_t* bits) {
   return pc;
 }
 
-LCV_FN void item_pre(uint32_t i, const BatchDev& B, const CommitteeDev& C, const Params& P, const Work& W) {
-  (void)C;
+// The non-BLS asserts of one update against one store snapshot: finalized slot `store_fin_slot`, next committee
+// known or not, and the committee-table rows the signature is checked against (`cur_row`, or `next_row` for a
+// signature of the next period).  Two front ends: item_pre (the context's single store: the :442 equality is a
+// flag of the update's pool row) and item_pre_table (a store per update: the equality is the row's own flag).
+template <bool TABLE>
+LCV_FN void item_pre_body(uint32_t i, const BatchDev& B, const Params& P, const Work& W, uint64_t store_fin_slot,
+                          bool next_known, uint32_t cur_row, uint32_t next_row) {
   const uint8_t* ab = B.att_beacon + (size_t)K_BEACON * i;
   const uint8_t* ae = B.att_exec + (size_t)K_EXEC * i;
   const uint8_t* abr = B.att_branch + (size_t)K_EXEC_BRANCH * i;
@@ -230,9 +248,8 @@ LCV_FN void item_pre(uint32_t i, const BatchDev& B, const CommitteeDev& C, const
   if (!lc_header_valid(ab, ae, abr, P.cfg)) LCV_FAIL(2);
   // :398 slot ordering
   if (!(P.current_slot >= sig_slot && sig_slot > att_slot && att_slot >= fin_slot)) LCV_FAIL(3);
-  const uint64_t store_period = period_of_slot(P.store_fin_slot, P.cfg);
+  const uint64_t store_period = period_of_slot(store_fin_slot, P.cfg);
   const uint64_t sig_period = period_of_slot(sig_slot, P.cfg);
-  const bool next_known = P.next_known != 0;
   if (next_known) {
     if (!(sig_period == store_period || sig_period == store_period + 1)) LCV_FAIL(4);  // :402
   } else {
@@ -242,7 +259,7 @@ LCV_FN void item_pre(uint32_t i, const BatchDev& B, const CommitteeDev& C, const
   const uint64_t att_period = period_of_slot(att_slot, P.cfg);
   const bool is_sc = !bytes_all_zero(nbr, K_NSC_BRANCH / 4);
   const bool has_next = !next_known && is_sc && att_period == store_period;
-  if (!(att_slot > P.store_fin_slot || has_next)) LCV_FAIL(6);
+  if (!(att_slot > store_fin_slot || has_next)) LCV_FAIL(6);
   // :419-434 finality
   h256 state_root;
   ld_chunk(state_root, ab + 48);
@@ -267,15 +284,81 @@ LCV_FN void item_pre(uint32_t i, const BatchDev& B, const CommitteeDev& C, const
   if (!is_sc) {
     if (!(nflags & 1u)) LCV_FAIL(11);
   } else {
-    if (att_period == store_period && next_known && !(nflags & 2u)) LCV_FAIL(12);
+    if (att_period == store_period && next_known && !(TABLE ? W.nsc_eq[i] != 0 : (nflags & 2u) != 0)) LCV_FAIL(12);
     h256 leaf;
     soa_ld_h256(leaf, W.nsc_root, W.pool_cap, pool);
     if (!merkle_branch_ok(leaf, nbr, 5, 23, state_root)) LCV_FAIL(13);
   }
 #undef LCV_FAIL
   // :452-459 committee selection (the signing root is item_sigroot's)
-  W.comm_id[i] = sig_period != store_period ? 1u : 0u;
+  W.comm_id[i] = sig_period != store_period ? next_row : cur_row;
   W.pre_reason[i] = (uint8_t)reason;
+}
+
+LCV_FN void item_pre(uint32_t i, const BatchDev& B, const CommitteeDev& C, const Params& P, const Work& W) {
+  (void)C;
+  item_pre_body<false>(i, B, P, W, P.store_fin_slot, P.next_known != 0, 0u, 1u);
+}
+
+// the same asserts against the update's own row of the store table.  Where the next committee is unknown a
+// next-period signature already fails (:404, reason 5); its committee id then falls back to the current row, so
+// the aggregation stays inside the table.
+LCV_FN void item_pre_table(uint32_t i, const BatchDev& B, const StoreDev& S, const Params& P, const Work& W) {
+  const uint32_t s = B.store_index[i];
+  const uint32_t cur = S.cur[s], nxt = S.next[s];
+  const bool known = nxt != STORE_NEXT_UNKNOWN;
+  item_pre_body<true>(i, B, P, W, S.fin_slot[s], known, cur, known ? nxt : cur);
+}
+
+// :442 with a store per update: next_sync_committee == store.next_sync_committee is no property of the pool row
+// (one pool row can equal one update's store.next and differ from another's), so one 64-lane team per update
+// compares the 24,624 bytes of its pool row with its store's next row of the committee table — 1,539 16-byte
+// words, lane l taking words l, l + 64, ... — and folds the lanes' differences with one wave ballot into W.nsc_eq[i],
+// which item_pre_table reads.  Only rows that reach the test (is_sync_committee_update, next committee known,
+// attested period == store period) load anything.  Byte equality, as the reference's SSZ `==`.
+#if defined(__HIP_DEVICE_COMPILE__)
+enum { NSCEQ_TEAM = 64, NSCEQ_ROUNDS = 1, NSCEQ_LDS = 64 };
+#else  // host simulation: the lanes run one after another, lane 0 folds their LDS words in a second round
+enum { NSCEQ_TEAM = 64, NSCEQ_ROUNDS = 2, NSCEQ_LDS = 64 };
+#endif
+enum { SC_WORDS16 = K_SC / 16 };
+static_assert(K_SC % 16 == 0, "a SyncCommittee is a whole number of 16-byte words");
+LCV_FN uint32_t diff16(const uint8_t* a, const uint8_t* b, uint32_t k) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4 x = ((const uint4*)a)[k], y = ((const uint4*)b)[k];
+  return (x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w);
+#else
+  uint32_t d = 0;
+  for (int j = 0; j < 16; ++j) d |= (uint32_t)(a[16 * (size_t)k + j] ^ b[16 * (size_t)k + j]);
+  return d;
+#endif
+}
+LCV_FN void item_nsc_eq_team(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, const BatchDev& B,
+                             const CommitteeDev& C, const StoreDev& S, const Params& P, const Work& W) {
+  if (r == 0) {
+    const uint32_t s = B.store_index[i];
+    const uint32_t nxt = S.next[s];
+    const bool need = nxt != STORE_NEXT_UNKNOWN && !bytes_all_zero(B.nsc_branch + (size_t)K_NSC_BRANCH * i, K_NSC_BRANCH / 4) &&
+                      period_of_slot(ld_le64(B.att_beacon + (size_t)K_BEACON * i), P.cfg) == period_of_slot(S.fin_slot[s], P.cfg);
+    uint32_t dif = 1;  // rows that never reach the test: flag 0, nothing loaded
+    if (need) {
+      const uint8_t* a = B.nsc_pool + (size_t)K_SC * B.nsc_index[i];
+      const uint8_t* b = C.raw + (size_t)C.raw_stride * nxt;
+      dif = 0;
+      for (uint32_t k = lane; k < (uint32_t)SC_WORDS16; k += NSCEQ_TEAM) dif |= diff16(a, b, k);
+    }
+#if defined(__HIP_DEVICE_COMPILE__)
+    (void)lds;
+    const unsigned long long differ = __ballot(dif != 0);  // one team = one wave (k_team, TEAM = 64)
+    if (lane == 0) W.nsc_eq[i] = differ == 0ull ? 1 : 0;
+#else
+    lds[lane] = dif;
+#endif
+  } else if (lane == 0) {
+    uint32_t dif = 0;
+    for (uint32_t k = 0; k < NSCEQ_TEAM; ++k) dif |= lds[k];
+    W.nsc_eq[i] = dif == 0 ? 1 : 0;
+  }
 }
 
 // :460-463 fork version, domain and signing root of the attested header -> W.msg.  A kernel of its own

@@ -49,6 +49,20 @@ class UpdateBatch(C.Structure):
     ]
 
 
+class StoreTable(C.Structure):
+    _fields_ = [
+        ("committees", u8p),
+        ("ncomm", C.c_uint64),
+        ("finalized_slot", u64p),
+        ("current", u32p),
+        ("next", u32p),
+        ("nstore", C.c_uint64),
+    ]
+
+
+STORE_NEXT_UNKNOWN = 0xFFFFFFFF
+STORE_TABLE_MAX_COMMITTEES = 4096
+
 # name -> (restype, argtypes); must match include/lcv.h exactly (tests/test_abi.py checks it)
 SIGNATURES = {
     "lcv_device_count": (C.c_int, [C.POINTER(C.c_int)]),
@@ -57,6 +71,8 @@ SIGNATURES = {
     "lcv_last_error": (C.c_char_p, [C.c_void_p]),
     "lcv_set_store": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u8p, u8p]),
     "lcv_validate_updates": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), C.c_uint64, u8p, u8p, u8p]),
+    "lcv_set_store_table": (C.c_int, [C.c_void_p, C.POINTER(StoreTable), u8p]),
+    "lcv_validate_updates_stores": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), u32p, C.c_uint64, u8p, u8p, u8p]),
     "lcv_batch_upload": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), C.POINTER(C.c_void_p)]),
     "lcv_batch_free": (None, [C.c_void_p, C.c_void_p]),
     "lcv_validate_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u8p, u8p, u8p]),

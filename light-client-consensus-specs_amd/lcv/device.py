@@ -8,7 +8,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from . import config as _config
-from ._native import Lib, LcvError, UpdateBatch, HeaderCols, as_u8, load, ptr
+from ._native import (Lib, LcvError, UpdateBatch, HeaderCols, StoreTable, STORE_NEXT_UNKNOWN, as_u8, load, ptr)
 
 SYNC_COMMITTEE_BYTES = 24624
 EXEC_RECORD_BYTES = 832
@@ -188,6 +188,39 @@ class Verifier:
         r = np.zeros(batch.n, np.uint8)
         self._check(self.lib.lcv_validate_updates(self.ctx, C.byref(b), int(current_slot), ptr(gvr), ptr(v), ptr(r)),
                     "lcv_validate_updates")
+        return v.astype(bool), r
+
+    def set_store_table(self, committees: np.ndarray, finalized_slot, current, next) -> np.ndarray:
+        """A store snapshot per row (lcv_set_store_table): `committees` (ncomm, 24624) distinct SSZ SyncCommittee
+        values; store s = (finalized_slot[s], committee row current[s], committee row next[s] or
+        STORE_NEXT_UNKNOWN — an all-zero committee row means the same).  Every key is decoded and KeyValidated
+        once, device resident; returns the key status (ncomm, 512): 0 valid key, 2 invalid.  Independent of
+        set_store."""
+        com = np.ascontiguousarray(committees, np.uint8).reshape(-1, SYNC_COMMITTEE_BYTES)
+        fin = np.ascontiguousarray(finalized_slot, np.uint64).reshape(-1)
+        cur = np.ascontiguousarray(current, np.uint32).reshape(-1)
+        nxt = np.ascontiguousarray(next, np.uint32).reshape(-1)
+        if not (fin.shape == cur.shape == nxt.shape):
+            raise ValueError("finalized_slot, current and next need one entry per store")
+        t = StoreTable(ptr(com), com.shape[0], ptr(fin, C.c_uint64), ptr(cur, C.c_uint32), ptr(nxt, C.c_uint32),
+                       fin.shape[0])
+        ks = np.zeros((com.shape[0], 512), np.uint8)
+        self._store_table_key = None  # (lcv.runtime.ensure_store_table's memo of the table's content)
+        self._check(self.lib.lcv_set_store_table(self.ctx, C.byref(t), ptr(ks)), "lcv_set_store_table")
+        return ks
+
+    def validate_stores(self, batch: PackedUpdates, store_index, current_slot: int, genesis_validators_root: bytes):
+        """validate_light_client_update of update i against row store_index[i] of the store table
+        (lcv_validate_updates_stores) -> (verdicts, reason codes): what set_store(that store) + validate gives."""
+        b, keep = batch.to_c()
+        six = np.ascontiguousarray(store_index, np.uint32).reshape(-1)
+        if six.shape[0] != batch.n:
+            raise ValueError("store_index needs one entry per update")
+        gvr = as_u8(bytes(genesis_validators_root))
+        v = np.zeros(batch.n, np.uint8)
+        r = np.zeros(batch.n, np.uint8)
+        self._check(self.lib.lcv_validate_updates_stores(self.ctx, C.byref(b), ptr(six, C.c_uint32), int(current_slot),
+                                                         ptr(gvr), ptr(v), ptr(r)), "lcv_validate_updates_stores")
         return v.astype(bool), r
 
     def upload(self, batch: PackedUpdates) -> ResidentBatch:

@@ -57,3 +57,14 @@ def ensure_store(v: Verifier, finalized_slot: int, current: bytes, nxt: bytes) -
     v.set_store(finalized_slot, current, nxt)
     v._store_key = key
     _store_key[id(v)] = key
+
+
+def ensure_store_table(v: Verifier, key: bytes, committees, finalized_slot, current, nxt) -> bool:
+    """The store table of `v` becomes the given one unless `key` (a digest of its content) says it already is;
+    True if it was uploaded."""
+    if getattr(v, "_store_table_key", None) == key:
+        return False
+    v._store_table_key = None
+    v.set_store_table(committees, finalized_slot, current, nxt)
+    v._store_table_key = key
+    return True

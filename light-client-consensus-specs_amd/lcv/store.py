@@ -21,11 +21,17 @@ when `apply_light_client_update` changes what validation reads (finalized slot, 
 sync committee) are the remaining updates re-validated, again as one batch.  The store mutation
 itself is scalar and order-dependent, so it stays on the host.
 
+`sync_light_client_updates` is the same loop for the case where (nearly) every update moves the store —
+catching up over sync-committee periods, one LightClientUpdate per period (light-client.md step 4.2,
+p2p-interface.md LightClientUpdatesByRange): the store each update will meet is predicted on the host and all
+updates are validated in one device call, each against its own predicted store (the store table).
+
 Store / update objects are duck-typed: any objects with the reference's field names (the spec
 containers, or the lightweight defaults below for the finality / optimistic conversions).
 """
 from __future__ import annotations
 
+import copy
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Any, Optional, Sequence
@@ -36,7 +42,7 @@ from . import config
 from . import layout as L
 from . import runtime
 from .device import Verifier
-from .sync_protocol import REASONS, validate_light_client_updates
+from .sync_protocol import REASONS, validate_light_client_updates, validate_under_store_keys
 
 # SLOTS_PER_EPOCH * EPOCHS_PER_SYNC_COMMITTEE_PERIOD and UPDATE_TIMEOUT (sync-protocol.md:89) come from the
 # active network configuration (lcv.config.active(); mainnet unless set)
@@ -195,6 +201,62 @@ def process_light_client_updates(store, updates: Sequence, current_slot: int, ge
         start = k
     if reasons_out is not None:
         reasons_out.extend(int(r) for r in reasons)
+    return accepted
+
+
+def sync_light_client_updates(store, updates: Sequence, current_slot: int, genesis_validators_root: bytes,
+                              verifier: Optional[Verifier] = None, reasons_out: Optional[list] = None,
+                              stats_out: Optional[dict] = None) -> np.ndarray:
+    """`process_light_client_updates` — the same accept flags, reason codes and final store — with the device
+    validations of a multi-period catch-up collapsed into (normally) one.
+
+    process_light_client_updates validates the pending updates against the store as it is and starts over
+    whenever an accepted update changes what validation reads, which an update per sync-committee period does
+    every time: K periods cost K store uploads and K device calls.  Here the store every pending update will meet
+    is predicted instead: on a shallow copy of the store (the store logic only assigns fields) each update is
+    applied as if it were valid, the copy's validation key recorded before each.  All pending updates are then
+    validated in ONE call, each under its predicted key (lcv.sync_protocol.validate_under_store_keys: the store
+    table).  The rows are walked in order against the real store; a row's verdict counts only if the real store's
+    validation key is the one the row was validated under.  It is not after an invalid update whose acceptance
+    would have moved the store: from that row on the rest is planned and validated again.
+
+    stats_out (optional dict) receives validate_calls and rows_validated."""
+    v = verifier if verifier is not None else runtime.default_verifier()
+    if v.config != config.active():
+        raise ValueError(f"sync_light_client_updates: the verifier validates under network configuration "
+                         f"{v.config.name!r} but lcv.config.active() is {config.active().name!r}; call "
+                         f"lcv.config.set_active() (or Verifier.set_config) so both sides agree")
+    n = len(updates)
+    accepted = np.zeros(n, bool)
+    reasons = np.zeros(n, np.uint8)
+    calls = rows = 0
+    start = 0
+    while start < n:
+        sim = copy.copy(store)
+        keys = []
+        for u in updates[start:]:
+            keys.append(_validation_key(sim))
+            try:
+                _apply_valid(sim, u)
+            except AssertionError:
+                break  # apply_light_client_update's own assert: only an invalid update gets here; plan ends with it
+        pending = updates[start:start + len(keys)]
+        ok, rs = validate_under_store_keys(keys, pending, current_slot, genesis_validators_root, v)
+        calls += 1
+        rows += len(keys)
+        k = start
+        while k < start + len(keys) and _validation_key(store) == keys[k - start]:
+            reasons[k] = rs[k - start]
+            if ok[k - start]:
+                accepted[k] = True
+                _apply_valid(store, updates[k])
+            k += 1
+        start = k  # (k > start: the first row's key is the real store's)
+    if reasons_out is not None:
+        reasons_out.extend(int(r) for r in reasons)
+    if stats_out is not None:
+        stats_out["validate_calls"] = calls
+        stats_out["rows_validated"] = rows
     return accepted
 
 

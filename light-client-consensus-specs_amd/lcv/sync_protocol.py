@@ -8,6 +8,9 @@
         semantics: [validate_light_client_update(store, u, ...) for u in updates] against ONE
         immutable store snapshot; `updates` is a sequence of update objects or a PackedUpdates
         batch (the throughput path: no per-update Python work).
+    validate_light_client_updates_multi(stores, updates, current_slot, genesis_validators_root)
+        the same with a store per update — [validate_light_client_update(s, u, ...) for s, u in
+        zip(stores, updates)] — in one device call (the store table of include/lcv.h).
 
 Every check — Merkle branches, SSZ hash_tree_root, committee selection, signing root and
 `bls.FastAggregateVerify` — runs in the HIP kernels of liblcv.so; this module only packs bytes.
@@ -22,6 +25,7 @@ import numpy as np
 
 from . import layout as L
 from . import runtime
+from ._native import STORE_NEXT_UNKNOWN
 from .device import PackedUpdates, Verifier
 
 # reason code -> (reference line, description); reason k = the k-th assert of the function
@@ -101,6 +105,71 @@ def validate_light_client_updates(store, updates: Union[Sequence, PackedUpdates]
         return np.zeros(0, bool), np.zeros(0, np.uint8)
     runtime.ensure_store(v, *_store_args(store))
     return v.validate(batch, int(current_slot), bytes(genesis_validators_root))
+
+
+def validate_under_store_keys(keys: Sequence[Tuple[int, bytes, bytes]], updates: Union[Sequence, PackedUpdates],
+                               current_slot: int, genesis_validators_root: bytes, verifier: Optional[Verifier] = None
+                               ) -> Tuple[np.ndarray, np.ndarray]:
+    """Update i against the store snapshot keys[i] = (finalized slot, current_sync_committee bytes,
+    next_sync_committee bytes) — what validate_light_client_update reads from a store — in one device call.
+    Stores and committees are deduplicated by content into one store table, which is uploaded (its keys decoded
+    and KeyValidated) only when its content differs from the table the verifier already holds."""
+    v = verifier if verifier is not None else runtime.default_verifier()
+    batch = updates if isinstance(updates, PackedUpdates) else pack_updates(updates)
+    if len(keys) != batch.n:
+        raise ValueError("need one store per update")
+    if batch.n == 0:
+        return np.zeros(0, bool), np.zeros(0, np.uint8)
+    rows, row_of, stores, store_of = [], {}, [], {}
+    digest_of = {}  # committee bytes object -> digest (the same bytes object usually repeats from row to row)
+
+    def digest(sc: bytes) -> bytes:
+        d = digest_of.get(id(sc))
+        if d is None:
+            if len(sc) != L.SYNC_COMMITTEE_BYTES:
+                raise ValueError("committees must be 24624-byte SSZ SyncCommittee values")
+            d = digest_of[id(sc)] = hashlib.sha256(sc).digest()
+        return d
+
+    def committee_row(sc: bytes) -> int:
+        d = digest(sc)
+        if d not in row_of:
+            row_of[d] = len(rows)
+            rows.append(sc)
+        return row_of[d]
+
+    zero = hashlib.sha256(bytes(L.SYNC_COMMITTEE_BYTES)).digest()
+    index = np.zeros(batch.n, np.uint32)
+    for i, (fin, cur, nxt) in enumerate(keys):
+        sk = (int(fin), committee_row(cur), STORE_NEXT_UNKNOWN if digest(nxt) == zero else committee_row(nxt))
+        if sk not in store_of:
+            store_of[sk] = len(stores)
+            stores.append(sk)
+        index[i] = store_of[sk]
+    h = hashlib.sha256(b"".join(row_of))  # the committees' digests, in row order
+    fin = np.array([s[0] for s in stores], np.uint64)
+    cur = np.array([s[1] for s in stores], np.uint32)
+    nxt = np.array([s[2] for s in stores], np.uint32)
+    h.update(fin.tobytes() + cur.tobytes() + nxt.tobytes())
+    committees = np.frombuffer(b"".join(rows), np.uint8).reshape(len(rows), L.SYNC_COMMITTEE_BYTES)
+    runtime.ensure_store_table(v, h.digest(), committees, fin, cur, nxt)
+    return v.validate_stores(batch, index, int(current_slot), bytes(genesis_validators_root))
+
+
+def validate_light_client_updates_multi(stores: Sequence, updates: Union[Sequence, PackedUpdates], current_slot: int,
+                                        genesis_validators_root: bytes, verifier: Optional[Verifier] = None
+                                        ) -> Tuple[np.ndarray, np.ndarray]:
+    """validate_light_client_update(stores[i], updates[i], ...) for every i in one device call -> (verdicts,
+    reason codes).  One store object per update; the same object may repeat (it is packed once), and stores or
+    committees that are equal by content share a row of the device's store table."""
+    packed = {}
+    keys = []
+    for s in stores:
+        k = packed.get(id(s))
+        if k is None:
+            k = packed[id(s)] = _store_args(s)
+        keys.append(k)
+    return validate_under_store_keys(keys, updates, current_slot, genesis_validators_root, verifier)
 
 
 def validate_light_client_update(store, update, current_slot: int, genesis_validators_root: bytes,
