@@ -128,10 +128,23 @@ int lcv_validate_updates(lcv_ctx* ctx, const lcv_update_batch* batch, uint64_t c
  * return LCV_EINVAL naming the first offending index; lcv_validate_updates_stores before a table is set returns
  * LCV_ESTATE.
  * lcv_validate_updates_stores is synchronous, host buffers in and out, like lcv_validate_updates: batches above
- * the chunk size are cut the same way, and batches of at most lcv_set_latency_mode's rows run on the fan engine.
- * It always runs the serial shape: lcv_set_pipeline does not apply to it.  Verdicts and reasons are those of
- * lcv_set_store(store row) + lcv_validate_updates(update), row by row.  There is no async, resident or sharded
- * form of it. */
+ * the chunk size are cut the same way, batches of at most lcv_set_latency_mode's rows run on the fan engine, and
+ * lcv_set_pipeline applies.  Verdicts and reasons are those of lcv_set_store(store row) +
+ * lcv_validate_updates(update), row by row.
+ * Every other shape takes table batches too.  lcv_batch_upload_stores makes a resident batch that carries its
+ * store_index column; no table needs to be set at that time, and the batch's largest index is recorded on the
+ * host.  lcv_validate_resident, _resident_dev, _resident_async and lcv_validate_sharded (with lcv_slot_wait and
+ * lcv_slot_allgather behind them) validate such a batch against the store table that is set when they are
+ * called, and a batch from lcv_batch_upload against lcv_set_store, as ever.  Before any launch they check on the
+ * host, in O(1): no table set -> LCV_ESTATE; recorded largest index >= the table's nstore -> LCV_EINVAL, naming
+ * both numbers — a resident batch may outlive the table it was made for.  lcv_validate_stores_async is
+ * lcv_validate_async with the store_index column staged: every index is checked on the host before the DMA
+ * (LCV_EINVAL naming the first offending row, as lcv_validate_updates_stores), and lcv_slot_wait hands the results
+ * out.  A single-store batch and a table batch may be in flight on different slots at once.
+ * Ordering: lcv_set_store_table first waits for every work-space slot (all 8), then rewrites the table.  A
+ * batch enqueued before the call finishes under the table it was enqueued under (its results stay in its slot
+ * for lcv_slot_wait); work enqueued after the call sees the new table.  lcv_set_store does not wait: call it
+ * with no single-store batch in flight. */
 #define LCV_STORE_NEXT_UNKNOWN 0xFFFFFFFFu
 #define LCV_STORE_TABLE_MAX_COMMITTEES 4096
 typedef struct lcv_store_table {
@@ -148,6 +161,8 @@ int lcv_validate_updates_stores(lcv_ctx* ctx, const lcv_update_batch* batch, con
                                 uint8_t* verdict_out, uint8_t* reason_out);
 /* device-resident batches: upload once, validate many times (timed region excludes the upload) */
 int lcv_batch_upload(lcv_ctx* ctx, const lcv_update_batch* batch, lcv_dbatch** out);
+/* the same with the batch's store_index column (n entries): a table batch, see the store table above */
+int lcv_batch_upload_stores(lcv_ctx* ctx, const lcv_update_batch* batch, const uint32_t* store_index, lcv_dbatch** out);
 void lcv_batch_free(lcv_ctx* ctx, lcv_dbatch* b);
 int lcv_validate_resident(lcv_ctx* ctx, lcv_dbatch* b, uint64_t current_slot, const uint8_t* genesis_validators_root,
                           uint8_t* verdict_out, uint8_t* reason_out);
@@ -172,6 +187,9 @@ int lcv_slot_wait(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint
  * buffers may be reused as soon as the call returns. */
 int lcv_validate_async(lcv_ctx* ctx, const lcv_update_batch* batch, uint64_t current_slot,
                        const uint8_t* genesis_validators_root, int slot);
+/* the same against the store table: update i against store row store_index[i] */
+int lcv_validate_stores_async(lcv_ctx* ctx, const lcv_update_batch* batch, const uint32_t* store_index,
+                              uint64_t current_slot, const uint8_t* genesis_validators_root, int slot);
 /* multi-GPU form of lcv_slot_wait: after slot `slot`'s batch (n <= per_rank rows), all-gather every rank's
  * verdict bytes over RCCL (rank-major, each slice zero padded to per_rank) into verdict_all_out
  * (nranks * per_rank bytes) and wait.  Collective: every rank calls it in the same order. */

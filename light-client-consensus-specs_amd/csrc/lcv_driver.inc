@@ -40,6 +40,10 @@ struct lcv_dbatch {
   void* mem = nullptr;
   BatchDev B;
   uint64_t n = 0, npool = 0;
+  // a batch that carries its store_index column (B.store_index) is validated against the store table; the
+  // column's largest entry is recorded on the host when the column is taken, so that every later validation can
+  // check it against the table of that moment in O(1), before any launch
+  uint32_t max_store = 0;
 };
 
 // host-input serving path (lcv_validate_async): per work-space slot, a pinned host staging copy of the
@@ -384,7 +388,7 @@ static int agg_stage(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, con
   return LCV_OK;
 }
 
-// the non-BLS asserts of items [0, n): against the context's store, or (S: lcv_validate_updates_stores) each update
+// the non-BLS asserts of items [0, n): against the context's store, or (S: a batch with a store_index) each update
 // against its own row of the store table — the per-update committee equality (item_nsc_eq_team) then runs ahead
 // of the table form of item_pre on the same stream
 static int pre_stage(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, const Params& P, const StoreDev* S,
@@ -407,7 +411,7 @@ static int pre_stage(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, con
 // updates/s).  P (validate) adds item_pre and the signing root; nsc (first chunk) adds the committee
 // roots; FastAggregateVerify passes neither (its W.msg / W.comm_id are set by the caller).
 // agg_items > n (FastAggregateVerify of > 512 keys, n == 1): the aggregation runs over agg_items
-// slices and item_agg_fold sums them into item 0.  S: the store table of lcv_validate_updates_stores (pre_stage).
+// slices and item_agg_fold sums them into item 0.  S: the store table of a batch with a store_index (pre_stage).
 static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint32_t n, uint32_t agg_items = 0,
                    const Params* P = nullptr, const BatchDev* nsc = nullptr, const StoreDev* S = nullptr) {
   const Work& W = ctx->W;
@@ -508,10 +512,11 @@ static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint3
 // aggregation, Miller loop, final exponentiation, verdict) for one slice, on the current stream.
 // Slices are independent, so validate_impl runs slice k on stream k % pipe_streams: the kernels of
 // different slices overlap, filling the CUs that one stage's tail (or a one-lane-per-update stage)
-// leaves idle.  No stage marks: concurrent kernels would inflate each other's event times.
-static int run_slice(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, const Params& P, const Work& W,
-                     uint32_t n) {
-  LCV_TRY(be_launch(ctx, F_pre{B, C, P, W}, n));
+// leaves idle.  No stage marks: concurrent kernels would inflate each other's event times.  S: the store
+// table of a batch that carries its store_index (pre_stage).
+static int run_slice(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, const Params& P, const StoreDev* S,
+                     const Work& W, uint32_t n) {
+  LCV_TRY(pre_stage(ctx, B, C, P, S, W, n));
   LCV_TRY(be_launch(ctx, F_sigroot{B, P, W}, n));
   LCV_TRY(sig_decode_check(ctx, B, W, n));
   LCV_TRY(hash_to_g2_stage(ctx, W, n));
@@ -645,6 +650,12 @@ static void bind_batch(lcv_dbatch* db, uint8_t* m, const BatchCols& c) {
   B.npool = (uint32_t)c.np;
   db->n = c.n;
   db->npool = c.np;
+  db->max_store = 0;
+  if (c.bytes[13]) {
+    const uint32_t* ix = (const uint32_t*)c.src[13];
+    for (size_t i = 0; i < c.n; ++i)
+      if (ix[i] > db->max_store) db->max_store = ix[i];
+  }
 }
 
 extern "C" {
@@ -674,6 +685,13 @@ int lcv_batch_upload(lcv_ctx* ctx, const lcv_update_batch* hb, lcv_dbatch** out)
   return batch_upload(ctx, hb, nullptr, out);
 }
 
+// a resident batch that carries its store_index column: every resident entry validates it against the store
+// table of the moment of the call (validate_impl checks the recorded largest index against that table)
+int lcv_batch_upload_stores(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index, lcv_dbatch** out) {
+  if (!store_index) return fail(ctx, LCV_EINVAL, "lcv_batch_upload_stores: null argument");
+  return batch_upload(ctx, hb, store_index, out);
+}
+
 void lcv_batch_free(lcv_ctx* ctx, lcv_dbatch* b) {
   if (!ctx || !b) return;
   if (b->mem) be_free(ctx, b->mem);
@@ -694,11 +712,18 @@ static BatchDev chunk_view(const BatchDev& B, size_t base, uint32_t n) {
 // out_host: verdict/reason to host memory; out_dev: verdicts to a device buffer
 static int host_alloc_grow(lcv_ctx* ctx, uint8_t** p, size_t* cap, size_t bytes);
 static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, const uint8_t* gvr, uint8_t* verdict_host,
-                         uint8_t* reason_host, uint8_t* verdict_dev, int slot = -1, bool table = false) {
+                         uint8_t* reason_host, uint8_t* verdict_dev, int slot = -1) {
   if (!ctx || !db || !gvr) return fail(ctx, LCV_EINVAL, "validate: null argument");
-  // table: every update against its own row of the store table (db->B.store_index, checked by the caller)
+  // table: a batch that carries its store_index has every update validated against its own row of the store
+  // table.  A resident batch outlives the table its indices were first checked against, so the largest index
+  // (recorded with the column) is checked against the table of this call, on the host, before any launch
+  const bool table = db->B.store_index != nullptr;
   if (table) {
-    if (!ctx->table_set || !db->B.store_index) return fail(ctx, LCV_ESTATE, "validate: lcv_set_store_table has not been called");
+    if (!ctx->table_set) return fail(ctx, LCV_ESTATE, "validate: lcv_set_store_table has not been called");
+    if (db->max_store >= ctx->table_dev.nstore)
+      return fail(ctx, LCV_EINVAL, "validate: the batch's largest store_index " + std::to_string(db->max_store) +
+                                       " is not a store row of the current table (nstore " +
+                                       std::to_string(ctx->table_dev.nstore) + ")");
   } else if (!ctx->store_set) {
     return fail(ctx, LCV_ESTATE, "validate: lcv_set_store has not been called");
   }
@@ -723,7 +748,7 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
   const StoreDev* S = table ? &ctx->table_dev : nullptr;
   if (!async) be_reset_timings(ctx);
   const int ns = ctx->pipe_streams < 4 ? ctx->pipe_streams : 4;  // lcv_set_pipeline: min(streams, 4)
-  const bool piped = !async && !table && ns > 1 && ctx->pipe_chunks > 1;  // (the table path: serial shape)
+  const bool piped = !async && ns > 1 && ctx->pipe_chunks > 1;
   bool pinned_out = false;
   auto body = [&]() -> int {
     if (piped) {  // sliced chains on `ns` streams (lcv_set_pipeline): the committee roots come first
@@ -773,7 +798,7 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
           const uint32_t len = (m - o) < sl ? (m - o) : sl;
           be_use_stream(ctx, (int)(c % (uint32_t)ns));
           const Work Wc = work_view(ctx->W, o);
-          LCV_TRY(run_slice(ctx, chunk_view(B, o, len), C, P, Wc, len));
+          LCV_TRY(run_slice(ctx, chunk_view(B, o, len), C, P, S, Wc, len));
         }
         // results leave from the main stream once every slice has joined: a copy to pageable host
         // memory on a slice's stream would block the host and serialise the slices
@@ -881,13 +906,14 @@ static void stage_columns(uint8_t* dst, const BatchCols& c) {
   for (auto& x : th) x.join();
 }
 
-int lcv_validate_async(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t current_slot, const uint8_t* gvr, int slot) {
-  if (!ctx || !hb || !gvr || slot < 0 || slot >= LCV_SLOTS)
-    return fail(ctx, LCV_EINVAL, "lcv_validate_async: null argument or slot not in 0..7");
-  if (!ctx->store_set) return fail(ctx, LCV_ESTATE, "lcv_validate_async: lcv_set_store has not been called");
-  if (hb->n > ctx->chunk) return fail(ctx, LCV_EINVAL, "lcv_validate_async: at most 65536 updates per call");
+static int store_index_check(lcv_ctx* ctx, const char* who, const uint32_t* store_index, uint64_t n);
+// store_index null: against the context's store (lcv_validate_async); else row by row against the store table
+// (lcv_validate_stores_async), the 14th column staged with the others
+static int validate_async_host(lcv_ctx* ctx, const char* who, const lcv_update_batch* hb, const uint32_t* store_index,
+                               uint64_t current_slot, const uint8_t* gvr, int slot) {
+  if (store_index) LCV_TRY(store_index_check(ctx, who, store_index, hb->n));  // before the DMA
   BatchCols c;
-  LCV_TRY(batch_cols(ctx, hb, c, "lcv_validate_async"));
+  LCV_TRY(batch_cols(ctx, hb, c, who, store_index));
   HostSlot& h = ctx->hslot[slot];
   be_set_slot(ctx, slot);
   // the staging buffer is reused only after the slot's previous batch has left it
@@ -923,6 +949,23 @@ int lcv_validate_async(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t curren
   h.out_n = c.n;
   h.staged = true;
   return LCV_OK;
+}
+
+int lcv_validate_async(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t current_slot, const uint8_t* gvr, int slot) {
+  if (!ctx || !hb || !gvr || slot < 0 || slot >= LCV_SLOTS)
+    return fail(ctx, LCV_EINVAL, "lcv_validate_async: null argument or slot not in 0..7");
+  if (!ctx->store_set) return fail(ctx, LCV_ESTATE, "lcv_validate_async: lcv_set_store has not been called");
+  if (hb->n > ctx->chunk) return fail(ctx, LCV_EINVAL, "lcv_validate_async: at most 65536 updates per call");
+  return validate_async_host(ctx, "lcv_validate_async", hb, nullptr, current_slot, gvr, slot);
+}
+
+int lcv_validate_stores_async(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index,
+                              uint64_t current_slot, const uint8_t* gvr, int slot) {
+  if (!ctx || !hb || !store_index || !gvr || slot < 0 || slot >= LCV_SLOTS)
+    return fail(ctx, LCV_EINVAL, "lcv_validate_stores_async: null argument or slot not in 0..7");
+  if (!ctx->table_set) return fail(ctx, LCV_ESTATE, "lcv_validate_stores_async: lcv_set_store_table has not been called");
+  if (hb->n > ctx->chunk) return fail(ctx, LCV_EINVAL, "lcv_validate_stores_async: at most 65536 updates per call");
+  return validate_async_host(ctx, "lcv_validate_stores_async", hb, store_index, current_slot, gvr, slot);
 }
 
 int lcv_slot_wait(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint8_t* reason_out) {
@@ -975,12 +1018,12 @@ static int validate_host(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_
     be_set_slot(ctx, 0);
     LCV_TRY(be_h2d(ctx, h.dev, h.pinned, c.total));
     bind_batch(&h.db, (uint8_t*)h.dev, c);
-    return validate_impl(ctx, &h.db, current_slot, gvr, verdict_out, reason_out, nullptr, -1, table);  // returns synced
+    return validate_impl(ctx, &h.db, current_slot, gvr, verdict_out, reason_out, nullptr);  // returns synced
   }
   // larger batches (and invalid arguments, reported by the upload): a device batch per call
   lcv_dbatch* db = nullptr;
   LCV_TRY(batch_upload(ctx, hb, store_index, &db));
-  int rc = validate_impl(ctx, db, current_slot, gvr, verdict_out, reason_out, nullptr, -1, table);
+  int rc = validate_impl(ctx, db, current_slot, gvr, verdict_out, reason_out, nullptr);
   lcv_batch_free(ctx, db);
   return rc;
 }
@@ -1023,8 +1066,12 @@ int lcv_set_store_table(lcv_ctx* ctx, const lcv_store_table* t, uint8_t* key_sta
   std::vector<uint32_t> next(ns);
   for (size_t s = 0; s < ns; ++s)
     next[s] = (t->next[s] == LCV_STORE_NEXT_UNKNOWN || zero_row[t->next[s]]) ? (uint32_t)STORE_NEXT_UNKNOWN : t->next[s];
-  ctx->table_set = false;
+  // drain: batches in flight on any work-space slot read the table's committees and store columns, so every
+  // slot's streams are waited for before that memory is rewritten or freed.  A batch already enqueued thus
+  // finishes under the table it was enqueued under; work enqueued after this call sees the new one
   be_set_slot(ctx, 0);
+  LCV_TRY(be_sync(ctx));
+  ctx->table_set = false;
   auto body = [&]() -> int {
     LCV_TRY(ensure_committees(ctx, ctx->table, nc, K_SC));
     if (ns > ctx->table_store_cap || !ctx->table_mem) {
@@ -1054,16 +1101,22 @@ int lcv_set_store_table(lcv_ctx* ctx, const lcv_store_table* t, uint8_t* key_sta
   return LCV_OK;
 }
 
+// every store_index of a host batch against the table that is set, naming the first offending row
+static int store_index_check(lcv_ctx* ctx, const char* who, const uint32_t* store_index, uint64_t n) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (store_index[i] >= ctx->table_dev.nstore)
+      return fail(ctx, LCV_EINVAL, std::string(who) + ": store_index[" + std::to_string(i) + "] = " +
+                                       std::to_string(store_index[i]) + " is not a store row (nstore " +
+                                       std::to_string(ctx->table_dev.nstore) + ")");
+  return LCV_OK;
+}
+
 int lcv_validate_updates_stores(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index,
                                 uint64_t current_slot, const uint8_t* gvr, uint8_t* verdict_out, uint8_t* reason_out) {
   if (!ctx || !hb || !store_index || !gvr) return fail(ctx, LCV_EINVAL, "lcv_validate_updates_stores: null argument");
   if (!ctx->table_set) return fail(ctx, LCV_ESTATE, "lcv_validate_updates_stores: lcv_set_store_table has not been called");
   if (hb->n == 0 || hb->n > 0xffffffffull) return fail(ctx, LCV_EINVAL, "lcv_validate_updates_stores: need 0 < n < 2^32");
-  for (uint64_t i = 0; i < hb->n; ++i)
-    if (store_index[i] >= ctx->table_dev.nstore)
-      return fail(ctx, LCV_EINVAL, "lcv_validate_updates_stores: store_index[" + std::to_string(i) + "] = " +
-                                       std::to_string(store_index[i]) + " is not a store row (nstore " +
-                                       std::to_string(ctx->table_dev.nstore) + ")");
+  LCV_TRY(store_index_check(ctx, "lcv_validate_updates_stores", store_index, hb->n));
   return validate_host(ctx, hb, store_index, current_slot, gvr, verdict_out, reason_out);
 }
 

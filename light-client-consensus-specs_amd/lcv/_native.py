@@ -74,6 +74,7 @@ SIGNATURES = {
     "lcv_set_store_table": (C.c_int, [C.c_void_p, C.POINTER(StoreTable), u8p]),
     "lcv_validate_updates_stores": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), u32p, C.c_uint64, u8p, u8p, u8p]),
     "lcv_batch_upload": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), C.POINTER(C.c_void_p)]),
+    "lcv_batch_upload_stores": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), u32p, C.POINTER(C.c_void_p)]),
     "lcv_batch_free": (None, [C.c_void_p, C.c_void_p]),
     "lcv_validate_resident": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u8p, u8p, u8p]),
     "lcv_validate_resident_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, u8p, C.c_void_p]),
@@ -81,6 +82,7 @@ SIGNATURES = {
     "lcv_slot_wait": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, u8p, u8p]),
     "lcv_slot_allgather": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, C.c_uint64, u8p]),
     "lcv_validate_async": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), C.c_uint64, u8p, C.c_int]),
+    "lcv_validate_stores_async": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), u32p, C.c_uint64, u8p, C.c_int]),
     "lcv_comm_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "lcv_debug_event_pool": (C.c_int, [C.c_void_p, u64p]),
     "lcv_debug_set_chunk": (C.c_int, [C.c_void_p, C.c_uint64]),

@@ -84,10 +84,14 @@ class PackedUpdates:
 
 
 class ResidentBatch:
-    def __init__(self, verifier: "Verifier", handle: C.c_void_p, n: int):
+    """A device-resident batch (Verifier.upload).  `stores`: it carries its store_index column, so every
+    validate_resident* call validates it against the store table instead of the set_store snapshot."""
+
+    def __init__(self, verifier: "Verifier", handle: C.c_void_p, n: int, stores: bool = False):
         self.v = verifier
         self.handle = handle
         self.n = n
+        self.stores = stores
 
     def free(self):
         if self.handle:
@@ -113,6 +117,8 @@ class Verifier:
         self.device = device
         self.config = _config.MAINNET  # the context's network configuration (lcv_init: mainnet)
         self.latency_mode = 64  # lcv_set_latency_mode's value (lcv_init's default: the fan engine up to 64 rows)
+        self.pipeline = (1, 1)  # lcv_set_pipeline's (streams, chunks)
+        self.chunk_rows = 65536  # rows per validate chunk, and the most one asynchronous call takes (debug_set_chunk)
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc: int, what: str):
@@ -144,6 +150,7 @@ class Verifier:
         """Run validate's per-update stage chain on `chunks` slices over `streams` HIP streams
         (overlapping stages of different slices); (1, 1) = serial stages with per-stage timings."""
         self._check(self.lib.lcv_set_pipeline(self.ctx, int(streams), int(chunks)), "lcv_set_pipeline")
+        self.pipeline = (int(streams), int(chunks))
 
     def set_latency_mode(self, max_rows: int) -> None:
         """Latency mode for small batches (lcv_set_latency_mode): batches of at most max_rows rows run the SOP
@@ -154,6 +161,11 @@ class Verifier:
         0 = the batch engine always."""
         self._check(self.lib.lcv_set_latency_mode(self.ctx, int(max_rows)), "lcv_set_latency_mode")
         self.latency_mode = int(max_rows)
+
+    def debug_set_chunk(self, rows: int) -> None:
+        """Test hook (lcv_debug_set_chunk): rows per validate chunk, a multiple of 64 up to the default 65536."""
+        self._check(self.lib.lcv_debug_set_chunk(self.ctx, int(rows)), "lcv_debug_set_chunk")
+        self.chunk_rows = int(rows)
 
     def engine_log(self, reset: bool = False) -> Dict[str, object]:
         """Which engines ran since the last reset (lcv_debug_engine_log): SOP launches on the fan / batch
@@ -213,9 +225,7 @@ class Verifier:
         """validate_light_client_update of update i against row store_index[i] of the store table
         (lcv_validate_updates_stores) -> (verdicts, reason codes): what set_store(that store) + validate gives."""
         b, keep = batch.to_c()
-        six = np.ascontiguousarray(store_index, np.uint32).reshape(-1)
-        if six.shape[0] != batch.n:
-            raise ValueError("store_index needs one entry per update")
+        six = self._store_index(batch, store_index)
         gvr = as_u8(bytes(genesis_validators_root))
         v = np.zeros(batch.n, np.uint8)
         r = np.zeros(batch.n, np.uint8)
@@ -223,11 +233,26 @@ class Verifier:
                                                          ptr(gvr), ptr(v), ptr(r)), "lcv_validate_updates_stores")
         return v.astype(bool), r
 
-    def upload(self, batch: PackedUpdates) -> ResidentBatch:
+    def _store_index(self, batch: PackedUpdates, store_index) -> np.ndarray:
+        six = np.ascontiguousarray(store_index, np.uint32).reshape(-1)
+        if six.shape[0] != batch.n:
+            raise ValueError("store_index needs one entry per update")
+        return six
+
+    def upload(self, batch: PackedUpdates, store_index=None) -> ResidentBatch:
+        """A device-resident copy of `batch`.  With `store_index` (one store-table row per update:
+        lcv_batch_upload_stores) the batch is a table batch: validate_resident, validate_resident_dev,
+        validate_resident_async and the sharded calls validate update i against row store_index[i] of the store
+        table that is set when they are called (no table is needed yet here)."""
         b, keep = batch.to_c()
         h = C.c_void_p()
-        self._check(self.lib.lcv_batch_upload(self.ctx, C.byref(b), C.byref(h)), "lcv_batch_upload")
-        return ResidentBatch(self, h, batch.n)
+        if store_index is None:
+            self._check(self.lib.lcv_batch_upload(self.ctx, C.byref(b), C.byref(h)), "lcv_batch_upload")
+            return ResidentBatch(self, h, batch.n)
+        six = self._store_index(batch, store_index)
+        self._check(self.lib.lcv_batch_upload_stores(self.ctx, C.byref(b), ptr(six, C.c_uint32), C.byref(h)),
+                    "lcv_batch_upload_stores")
+        return ResidentBatch(self, h, batch.n, stores=True)
 
     def validate_resident(self, rb: ResidentBatch, current_slot: int, genesis_validators_root: bytes,
                           verdict: Optional[np.ndarray] = None, reason: Optional[np.ndarray] = None):
@@ -263,6 +288,18 @@ class Verifier:
         gvr = as_u8(bytes(genesis_validators_root))
         self._check(self.lib.lcv_validate_async(self.ctx, C.byref(b), int(current_slot), ptr(gvr), int(slot)),
                     "lcv_validate_async")
+        del keep
+
+    def validate_stores_async(self, batch: PackedUpdates, store_index, current_slot: int,
+                              genesis_validators_root: bytes, slot: int) -> None:
+        """validate_async against the store table (lcv_validate_stores_async): update i against store row
+        store_index[i].  Every index is checked on the host before anything is enqueued; collect the verdicts
+        with slot_wait(slot).  The arrays may be reused as soon as this returns."""
+        b, keep = batch.to_c()
+        six = self._store_index(batch, store_index)
+        gvr = as_u8(bytes(genesis_validators_root))
+        self._check(self.lib.lcv_validate_stores_async(self.ctx, C.byref(b), ptr(six, C.c_uint32), int(current_slot),
+                                                       ptr(gvr), int(slot)), "lcv_validate_stores_async")
         del keep
 
     def event_pool(self) -> int:

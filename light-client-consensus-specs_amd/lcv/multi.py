@@ -297,23 +297,33 @@ def unshard(gathered: np.ndarray, n_total: int, world: int) -> np.ndarray:
 
 
 def validate_sharded(verifier, batch, current_slot: int, genesis_validators_root: bytes, comm: Comm,
-                     recover: bool = True, grace: float = 10.0) -> np.ndarray:
+                     recover: bool = True, grace: float = 10.0, store_index=None) -> np.ndarray:
     """This rank validates its shard of `batch` (the full PackedUpdates, identical on every rank);
     returns the full verdict array (bool) on every rank.  The store must already be set on `verifier`.
+
+    `store_index` (one store-table row per update, identical on every rank): update i is validated against
+    row store_index[i] of the store table.  The index is sharded with the rows and uploaded with each shard.
+    EVERY rank must have set the SAME table (Verifier.set_store_table) before the call: a rank holds only its
+    own copy, and nothing compares the copies.
 
     Failure containment: when a peer dies or hangs, the collective fails within the
     communicator's timeout on every surviving rank (CommFailed); with `recover` the survivors agree on
     who is left (Comm.recover), shrink the communicator to themselves and the batch is re-sharded over
     them — the failed rank's shard is validated on the survivors — until a pass completes.  The result
     equals the single-rank verdicts."""
+    six = None
+    if store_index is not None:
+        six = np.ascontiguousarray(store_index, np.uint32).reshape(-1)
+        if six.shape[0] != batch.n:
+            raise ValueError("store_index needs one entry per update")
     while True:
         world, rank = comm.world, comm.rank
         lo, hi = shard_bounds(batch.n, world, rank)
         per = -(-batch.n // world)
         if hi > lo:
-            rb = verifier.upload(batch.slice(lo, hi))
+            rb = verifier.upload(batch.slice(lo, hi), None if six is None else six[lo:hi])
         else:  # an empty shard still joins the collective (a one-row dummy batch, verdict overwritten)
-            rb = verifier.upload(batch.slice(0, 1))
+            rb = verifier.upload(batch.slice(0, 1), None if six is None else np.zeros(1, np.uint32))
         try:
             g = comm.validate_sharded(rb, current_slot, genesis_validators_root, max(per, 1))
             return unshard(g, batch.n, world).astype(bool)

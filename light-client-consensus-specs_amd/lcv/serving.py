@@ -1,0 +1,94 @@
+"""`validate_stream`: the serving loop over a stream of host batches, several in flight.
+
+One synchronous call validates one batch and the device idles while the host stages the next; with the
+batches of up to eight work-space slots in flight, a batch's upload and the host's staging overlap the other
+slots' kernels (lcv_validate_async, include/lcv.h).  This is the loop bench.py writes by hand, for any caller:
+single-store batches (Verifier.set_store) and table batches (Verifier.set_store_table, one store row per
+update) may be mixed in one stream.
+"""
+from __future__ import annotations
+
+from collections import deque
+from typing import Iterable, Iterator, Tuple, Union
+
+import numpy as np
+
+from .device import PackedUpdates, Verifier
+
+SLOTS = 8            # work-space slots of a context (LCV_SLOTS)
+MAX_ROWS = 65536     # rows of one asynchronous call
+
+Item = Union[PackedUpdates, Tuple[PackedUpdates, np.ndarray]]
+
+
+def validate_stream(verifier: Verifier, items: Iterable[Item], current_slot: int, genesis_validators_root: bytes,
+                    in_flight: int = SLOTS) -> Iterator[Tuple[np.ndarray, np.ndarray]]:
+    """Validate every item of `items` and yield its (verdicts: bool array, reason codes: uint8 array), in input
+    order.  An item is a PackedUpdates — validated against the store of Verifier.set_store, as
+    Verifier.validate does — or (PackedUpdates, store_index) — update i against row store_index[i] of the table
+    of Verifier.set_store_table, as Verifier.validate_stores does.  The store and the table an item needs must
+    be set before the item is drawn from `items`; a set_store_table between two items waits for the items in
+    flight, which finish under the table they were enqueued under.
+
+    Up to `in_flight` (1..8) calls are in flight, on work-space slots 0 .. in_flight - 1 in turn, through
+    Verifier.validate_async / validate_stores_async; the generator waits for a slot only when it is about to
+    reuse it (and, after the last item, for what is left).  Items above 65,536 rows — the rows of one
+    asynchronous call — are cut into pieces, and an item's result is yielded whole.  No other call may use the
+    verifier's slots while the generator is live; closing it early waits for the slots in flight."""
+    in_flight = int(in_flight)
+    if not 1 <= in_flight <= SLOTS:
+        raise ValueError(f"in_flight must be 1..{SLOTS}")
+    piece_rows = min(MAX_ROWS, int(getattr(verifier, "chunk_rows", MAX_ROWS)))
+    gvr = bytes(genesis_validators_root)
+    pending = deque()  # (slot or None for an empty item, rows, last piece of its item), oldest first
+    parts = []         # the pieces of the oldest item waited for so far
+    next_slot = 0
+
+    def finish_oldest():
+        slot, rows, last = pending.popleft()
+        if slot is not None:
+            parts.append(verifier.slot_wait(slot, rows))
+        if not last:
+            return None
+        v = np.concatenate([p[0] for p in parts]) if parts else np.zeros(0, np.uint8)
+        r = np.concatenate([p[1] for p in parts]) if parts else np.zeros(0, np.uint8)
+        parts.clear()
+        return v.astype(bool), r
+
+    try:
+        for item in items:
+            batch, index = item if isinstance(item, tuple) else (item, None)
+            if index is not None:
+                index = np.ascontiguousarray(index, np.uint32).reshape(-1)
+                if index.shape[0] != batch.n:
+                    raise ValueError("store_index needs one entry per update")
+            if batch.n == 0:
+                pending.append((None, 0, True))
+            for lo in range(0, batch.n, piece_rows):
+                hi = min(lo + piece_rows, batch.n)
+                if sum(1 for p in pending if p[0] is not None) == in_flight:  # the oldest piece holds next_slot
+                    while True:
+                        waited = pending[0][0] is not None
+                        out = finish_oldest()
+                        if out is not None:
+                            yield out
+                        if waited:
+                            break
+                piece = batch if (lo, hi) == (0, batch.n) else batch.slice(lo, hi)
+                if index is None:
+                    verifier.validate_async(piece, current_slot, gvr, next_slot)
+                else:
+                    verifier.validate_stores_async(piece, index[lo:hi], current_slot, gvr, next_slot)
+                pending.append((next_slot, hi - lo, hi == batch.n))
+                next_slot = (next_slot + 1) % in_flight
+        while pending:
+            out = finish_oldest()
+            if out is not None:
+                yield out
+    finally:
+        for slot, _, _ in pending:  # closed early or failed: nothing stays in flight
+            if slot is not None:
+                try:
+                    verifier.slot_wait(slot, 0)
+                except Exception:
+                    pass

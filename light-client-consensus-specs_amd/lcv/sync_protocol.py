@@ -27,6 +27,7 @@ from . import layout as L
 from . import runtime
 from ._native import STORE_NEXT_UNKNOWN
 from .device import PackedUpdates, Verifier
+from .serving import MAX_ROWS, validate_stream
 
 # reason code -> (reference line, description); reason k = the k-th assert of the function
 REASONS = {
@@ -113,7 +114,9 @@ def validate_under_store_keys(keys: Sequence[Tuple[int, bytes, bytes]], updates:
     """Update i against the store snapshot keys[i] = (finalized slot, current_sync_committee bytes,
     next_sync_committee bytes) — what validate_light_client_update reads from a store — in one device call.
     Stores and committees are deduplicated by content into one store table, which is uploaded (its keys decoded
-    and KeyValidated) only when its content differs from the table the verifier already holds."""
+    and KeyValidated) only when its content differs from the table the verifier already holds.  A PackedUpdates
+    batch above one chunk (65,536 rows) goes through lcv.serving.validate_stream, its chunks in flight on the
+    work-space slots, instead of the synchronous call; the results are the same."""
     v = verifier if verifier is not None else runtime.default_verifier()
     batch = updates if isinstance(updates, PackedUpdates) else pack_updates(updates)
     if len(keys) != batch.n:
@@ -153,6 +156,9 @@ def validate_under_store_keys(keys: Sequence[Tuple[int, bytes, bytes]], updates:
     h.update(fin.tobytes() + cur.tobytes() + nxt.tobytes())
     committees = np.frombuffer(b"".join(rows), np.uint8).reshape(len(rows), L.SYNC_COMMITTEE_BYTES)
     runtime.ensure_store_table(v, h.digest(), committees, fin, cur, nxt)
+    if isinstance(updates, PackedUpdates) and batch.n > min(MAX_ROWS, getattr(v, "chunk_rows", MAX_ROWS)):
+        (out,) = validate_stream(v, [(batch, index)], int(current_slot), bytes(genesis_validators_root))
+        return out
     return v.validate_stores(batch, index, int(current_slot), bytes(genesis_validators_root))
 
 
