@@ -159,6 +159,79 @@ int lcv_set_store_table(lcv_ctx* ctx, const lcv_store_table* table, uint8_t* key
 int lcv_validate_updates_stores(lcv_ctx* ctx, const lcv_update_batch* batch, const uint32_t* store_index,
                                 uint64_t current_slot, const uint8_t* genesis_validators_root,
                                 uint8_t* verdict_out, uint8_t* reason_out);
+/* ---- process_light_client_update after validation (sync-protocol.md:514-553), folded over a batch on the device
+ * for ONE store: best update, max participants, optimistic header, and the first row that applies.  No per-row
+ * host work remains; the host applies the one applying row with its own apply_light_client_update.
+ *
+ * The rank record (LCV_RANK_BYTES = 32, little-endian), one per update, written by lcv_rank_updates and, inside
+ * the _fold calls, next to the pre-checks:
+ *   u32 key0 : bit 23     super  = 3 n >= 2 * 512              (n = number of set sync_committee_bits)
+ *              bits 22-13 super ? 0 : n
+ *              bit 12     nsc_branch != 0  &&  period(attested slot) == period(signature_slot)
+ *              bit 11     fin    = finality_branch != 0
+ *              bit 10     fin && period(finalized slot) == period(attested slot)
+ *              bits 9-0   n
+ *   u32 flags: bit 0      is_sync_committee_update (nsc_branch != 0, without the period test)
+ *   u64 attested_slot, u64 signature_slot, u64 finalized_slot
+ * is_better_update(a, b) (sync-protocol.md:260-311, level by level) holds iff
+ *   (key0_a, -attested_a, -signature_a) > (key0_b, -attested_b, -signature_b)   lexicographically;
+ * equal triples mean "not better", so "the first best wins" is the first arg-max of the triple.
+ * lcv_rank_updates reads six columns of the batch only — sync_bits, nsc_branch, finality_branch, attested.beacon
+ * and finalized.beacon (their first 8 bytes: the slot), signature_slot — and uploads only those; every other
+ * pointer of the batch is ignored and may be NULL.  Any n > 0, no store needed; the periods are lcv_set_config's.
+ *
+ * The fold.  Input: the batch's rank records and verdicts, the store values validation already holds
+ * (lcv_set_store's finalized slot and whether its next committee is known) and the 48-byte fold state: the
+ * store's optimistic slot, its two max_active_participants, and the rank of its best_valid_update if it has one.
+ * Let t be the first row with verdict 1, `super`, and (finalized_slot > store finalized slot, or (next committee
+ * not known and flags bit 0 and key0 bits 11 and 10)): the row process_light_client_update applies (:545-553).
+ * Rows after t are not consumed: rows_consumed = t + 1, or n without such a row.  Over the valid rows <= t:
+ *   - current_max_active_participants becomes the running max of n, seeded with the state's (:528-531);
+ *   - the optimistic candidate is the first row attaining the largest attested_slot among the rows with
+ *     n_i > max(previous_max, running_max_i) / 2 (integer division; running_max_i includes row i) and
+ *     attested_slot > the state's optimistic_slot (:534-539): optimistic_row, next.optimistic_slot;
+ *   - the best is the first arg-max of the rank, the state's own best winning ties (:521-525): best_row (-1 when
+ *     the state's best stays, or there is none), next.has_best / best_*.
+ * When a row applies, best_row is -1 and next.has_best is 0 (store.best_valid_update = None, :553), apply_row = t.
+ * next's maxima and optimistic slot are the values BEFORE apply_light_client_update(row t), which the host runs.
+ * accepted_count is the number of rows <= t (or of all rows) with verdict 1.  Results are bit-identical to looping
+ * the reference over rows 0 .. rows_consumed - 1.
+ *
+ * lcv_validate_fold is lcv_validate_updates + the fold of that batch, chained behind the verdicts on the batch's
+ * own stream (batch engine, fan engine and lcv_set_pipeline alike); the result travels back with the verdicts.
+ * n <= LCV_FOLD_MAX_ROWS, else LCV_EINVAL: the caller cuts larger batches and carries `next` forward while
+ * apply_row is -1.  lcv_validate_async_fold is lcv_validate_async with the fold; lcv_slot_wait_fold is
+ * lcv_slot_wait plus the result, and returns LCV_ESTATE for a slot whose batch was not enqueued with a fold.
+ * lcv_debug_fold (test hook) runs the fold alone on caller-supplied records and verdicts, no validation.
+ * Out of scope, refused or absent: a fold of a store-table batch (a batch with a store_index has no _fold entry),
+ * a sharded fold, and lcv.serving.validate_stream does not fold. */
+#define LCV_RANK_BYTES 32
+#define LCV_FOLD_MAX_ROWS 65536
+typedef struct lcv_fold_state {
+  uint64_t optimistic_slot;                  /* store.optimistic_header.beacon.slot */
+  uint64_t previous_max_active_participants;
+  uint64_t current_max_active_participants;
+  uint32_t has_best;                         /* store.best_valid_update is not None; then its rank: */
+  uint32_t best_key0;
+  uint64_t best_attested_slot;
+  uint64_t best_signature_slot;
+} lcv_fold_state;
+typedef struct lcv_fold_result {
+  lcv_fold_state next;
+  uint64_t rows_consumed;
+  int64_t apply_row, best_row, optimistic_row; /* -1: none */
+  uint64_t accepted_count;
+} lcv_fold_result;
+int lcv_rank_updates(lcv_ctx* ctx, const lcv_update_batch* batch, uint8_t* rank_out /* n x 32 */);
+int lcv_validate_fold(lcv_ctx* ctx, const lcv_update_batch* batch, uint64_t current_slot,
+                      const uint8_t* genesis_validators_root, const lcv_fold_state* in, uint8_t* verdict_out,
+                      uint8_t* reason_out, lcv_fold_result* out);
+int lcv_validate_async_fold(lcv_ctx* ctx, const lcv_update_batch* batch, uint64_t current_slot,
+                            const uint8_t* genesis_validators_root, const lcv_fold_state* in, int slot);
+int lcv_slot_wait_fold(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint8_t* reason_out,
+                       lcv_fold_result* out);
+int lcv_debug_fold(lcv_ctx* ctx, const uint8_t* rank /* n x 32 */, const uint8_t* verdict, uint64_t n,
+                   uint64_t store_finalized_slot, int next_known, const lcv_fold_state* in, lcv_fold_result* out);
 /* device-resident batches: upload once, validate many times (timed region excludes the upload) */
 int lcv_batch_upload(lcv_ctx* ctx, const lcv_update_batch* batch, lcv_dbatch** out);
 /* the same with the batch's store_index column (n entries): a table batch, see the store table above */

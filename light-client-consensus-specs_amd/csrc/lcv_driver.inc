@@ -12,6 +12,7 @@
 
 #include "../../include/lcv.h"
 #include "lcv_items.hpp"
+#include "lcv_fold.hpp"
 #include "lcv_sop.hpp"
 #include "lcv_build_id.h"  // LCV_BUILD_ID (Makefile: tools/build_id.py over the sources)
 
@@ -20,10 +21,11 @@ using namespace lcv;
 // One mark per kernel launch (marks never nest, so the host simulation's op counter attributes every
 // operation to exactly one stage, and a HIP event pair brackets exactly one kernel on its stream).
 enum { ST_NSC = 0, ST_PRE, ST_H2C_MAP, ST_H2C, ST_SIG, ST_AGG, ST_MILLER, ST_FEXP, ST_VERDICT, ST_SETUP,
-       ST_LINES, ST_LINES_SIG, ST_SIGROOT, ST_COUNT };
+       ST_LINES, ST_LINES_SIG, ST_SIGROOT, ST_RANK, ST_FOLD, ST_COUNT };
 static const char* kStageNames[ST_COUNT] = {"nsc_htr", "pre_checks", "h2c_sswu", "hash_to_g2", "sig_decode",
                                             "g1_aggregate", "miller_loop", "final_exp", "verdict",
-                                            "setup", "miller_lines", "miller_lines_sig", "signing_root"};
+                                            "setup", "miller_lines", "miller_lines_sig", "signing_root",
+                                            "store_rank", "store_fold"};
 
 struct CommitteeBufs {
   uint8_t* raw = nullptr;
@@ -58,6 +60,7 @@ struct HostSlot {
   size_t out_cap = 0;
   uint64_t out_n = 0;
   bool staged = false;     // out holds the slot's last batch (lcv_slot_wait reads it)
+  bool folded = false;     // ... and, after its 2 out_n bytes, that batch's fold result (lcv_slot_wait_fold)
   lcv_dbatch db;
 };
 
@@ -211,7 +214,8 @@ static int ensure_work(lcv_ctx* ctx, size_t cap, size_t pool_cap, int slot = 0) 
                o_nroot = take(32 * Pc), o_nfl = take(Pc),
                o_qmap = take(384 * C), o_qh = take(192 * C), o_qhinf = take(C), o_qs = take(192 * C), o_sst = take(C), o_pk = take(96 * C),
                o_ast = take(C), o_f = take(576 * C), o_pok = take(C), o_ver = take(C),
-               o_rea = take(C), o_lines = take((size_t)4 * SOP_LINE_WORDS * C);
+               o_rea = take(C), o_lines = take((size_t)4 * SOP_LINE_WORDS * C),
+               o_rank = take(rank_index(C)), o_fold = take(FOLD_RESULT_BYTES);
   void* mem = nullptr;
   LCV_TRY(be_alloc(ctx, &mem, off));
   LCV_TRY(be_memset(ctx, mem, 0, off));
@@ -238,6 +242,8 @@ static int ensure_work(lcv_ctx* ctx, size_t cap, size_t pool_cap, int slot = 0) 
   W.verdict = m + o_ver;
   W.reason = m + o_rea;
   W.lines = (uint32_t*)(m + o_lines);
+  W.rank = m + o_rank;
+  W.fold_out = m + o_fold;
   ctx->work_mem[slot] = mem;
   ctx->work_cap[slot] = C;
   ctx->work_pool_cap[slot] = Pc;
@@ -319,6 +325,7 @@ static Work work_view(const Work& W, size_t base) {
   v.verdict += base; v.reason += base;
   v.f += base * 144;  // item-major (lcv_items.hpp f12_st_coeff)
   v.lines += base * (size_t)SOP_LINE_WORDS;
+  v.rank += rank_index(base);  // item-major (lcv_fold.hpp); fold_out is per work space, not per item
   return v;
 }
 
@@ -412,14 +419,23 @@ static int pre_stage(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, con
 // roots; FastAggregateVerify passes neither (its W.msg / W.comm_id are set by the caller).
 // agg_items > n (FastAggregateVerify of > 512 keys, n == 1): the aggregation runs over agg_items
 // slices and item_agg_fold sums them into item 0.  S: the store table of a batch with a store_index (pre_stage).
+// rank (the _fold calls only): the rank records of the slice (F_rank) follow the pre-checks on the side stream.
+static int rank_stage(lcv_ctx* ctx, const BatchDev& B, const Params& P, const Work& W, uint32_t n) {
+  be_stage_begin(ctx, ST_RANK);
+  LCV_TRY(be_launch(ctx, F_rank{B, P, W}, n));
+  be_stage_end(ctx, ST_RANK);
+  return LCV_OK;
+}
 static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint32_t n, uint32_t agg_items = 0,
-                   const Params* P = nullptr, const BatchDev* nsc = nullptr, const StoreDev* S = nullptr) {
+                   const Params* P = nullptr, const BatchDev* nsc = nullptr, const StoreDev* S = nullptr,
+                   bool rank = false) {
   const Work& W = ctx->W;
 #if defined(LCV_CPU_FAST)
   if (!W.msg_b0) {  // CPU-baseline build: direct per-update code (lcv_cpu_direct.hpp), one core per update
     if (nsc) LCV_TRY(be_launch_team(ctx, F_nsc_team{*nsc, C, W}, nsc->npool));
     if (P) {
       LCV_TRY(pre_stage(ctx, B, C, *P, S, W, n));
+      if (rank) LCV_TRY(rank_stage(ctx, B, *P, W, n));
       LCV_TRY(be_launch(ctx, F_sigroot{B, *P, W}, n));
     }
     be_stage_begin(ctx, ST_SIG);
@@ -453,6 +469,7 @@ static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint3
     be_stage_begin(ctx, ST_PRE);
     LCV_TRY(pre_stage(ctx, B, C, *P, S, W, n));
     be_stage_end(ctx, ST_PRE);
+    if (rank) LCV_TRY(rank_stage(ctx, B, *P, W, n));
   }
   be_stage_begin(ctx, ST_SIG);
   LCV_TRY(launch_items(ctx, F_sig{B, W}, n, n));
@@ -515,8 +532,9 @@ static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint3
 // leaves idle.  No stage marks: concurrent kernels would inflate each other's event times.  S: the store
 // table of a batch that carries its store_index (pre_stage).
 static int run_slice(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, const Params& P, const StoreDev* S,
-                     const Work& W, uint32_t n) {
+                     const Work& W, uint32_t n, bool rank = false) {
   LCV_TRY(pre_stage(ctx, B, C, P, S, W, n));
+  if (rank) LCV_TRY(be_launch(ctx, F_rank{B, P, W}, n));  // the _fold calls: this slice's rank records
   LCV_TRY(be_launch(ctx, F_sigroot{B, P, W}, n));
   LCV_TRY(sig_decode_check(ctx, B, W, n));
   LCV_TRY(hash_to_g2_stage(ctx, W, n));
@@ -711,9 +729,31 @@ static BatchDev chunk_view(const BatchDev& B, size_t base, uint32_t n) {
 
 // out_host: verdict/reason to host memory; out_dev: verdicts to a device buffer
 static int host_alloc_grow(lcv_ctx* ctx, uint8_t** p, size_t* cap, size_t bytes);
+// a fold request of the _fold entries: the state going in and (synchronous form) where the result goes
+struct FoldReq { FoldState in; lcv_fold_result* out; };
+static_assert(sizeof(lcv_fold_state) == sizeof(FoldState) && sizeof(lcv_fold_result) == sizeof(FoldResult) &&
+              sizeof(FoldResult) <= FOLD_RESULT_BYTES, "lcv.h's fold structs are lcv_fold.hpp's");
+static int fold_state_in(lcv_ctx* ctx, const char* who, const lcv_fold_state* in, FoldState& s) {
+  if (!in) return fail(ctx, LCV_EINVAL, std::string(who) + ": null fold state");
+  if (in->previous_max_active_participants > LCV_SYNC_COMMITTEE_SIZE || in->current_max_active_participants > LCV_SYNC_COMMITTEE_SIZE)
+    return fail(ctx, LCV_EINVAL, std::string(who) + ": max_active_participants above SYNC_COMMITTEE_SIZE");
+  memcpy(&s, in, sizeof(s));
+  return LCV_OK;
+}
+// F_fold over the first n rows of the active work space, on the current stream (after F_verdict in stream order)
+static int fold_stage(lcv_ctx* ctx, const FoldState& in, uint64_t store_fin_slot, uint32_t next_known, uint32_t n) {
+  be_stage_begin(ctx, ST_FOLD);
+  LCV_TRY(be_launch_team(ctx, F_fold{ctx->W, in, store_fin_slot, next_known, n}, 1));
+  be_stage_end(ctx, ST_FOLD);
+  return LCV_OK;
+}
+
 static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, const uint8_t* gvr, uint8_t* verdict_host,
-                         uint8_t* reason_host, uint8_t* verdict_dev, int slot = -1) {
+                         uint8_t* reason_host, uint8_t* verdict_dev, int slot = -1, const FoldReq* fold = nullptr) {
   if (!ctx || !db || !gvr) return fail(ctx, LCV_EINVAL, "validate: null argument");
+  if (fold && db->B.store_index) return fail(ctx, LCV_EINVAL, "validate: no fold of a store-table batch");
+  if (fold && (db->n > LCV_FOLD_MAX_ROWS || db->n > ctx->chunk))
+    return fail(ctx, LCV_EINVAL, "validate: a fold takes at most 65536 updates (one chunk) per call");
   // table: a batch that carries its store_index has every update validated against its own row of the store
   // table.  A resident batch outlives the table its indices were first checked against, so the largest index
   // (recorded with the column) is checked against the table of this call, on the host, before any launch
@@ -798,21 +838,26 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
           const uint32_t len = (m - o) < sl ? (m - o) : sl;
           be_use_stream(ctx, (int)(c % (uint32_t)ns));
           const Work Wc = work_view(ctx->W, o);
-          LCV_TRY(run_slice(ctx, chunk_view(B, o, len), C, P, S, Wc, len));
+          LCV_TRY(run_slice(ctx, chunk_view(B, o, len), C, P, S, Wc, len, fold != nullptr));
         }
         // results leave from the main stream once every slice has joined: a copy to pageable host
         // memory on a slice's stream would block the host and serialise the slices
         be_use_stream(ctx, 0);
         for (int k = 1; k < ns; ++k) LCV_TRY(be_join_from(ctx, k));
       } else {
-        LCV_TRY(run_bls(ctx, B, C, m, 0, &P, (!piped && base == 0) ? &db->B : nullptr, S));
+        LCV_TRY(run_bls(ctx, B, C, m, 0, &P, (!piped && base == 0) ? &db->B : nullptr, S, fold != nullptr));
       }
-      if (!async && n <= cap && (verdict_host || reason_host)) {
-        // one chunk: both arrays into pinned memory without a wait each, handed out after the sync below
+      // the fold follows the verdicts of the whole batch (one chunk) on the main stream: after F_verdict in
+      // stream order on both engines, after every slice has joined under a pipeline
+      if (fold) LCV_TRY(fold_stage(ctx, fold->in, P.store_fin_slot, P.next_known, m));
+      if (!async && n <= cap && (verdict_host || reason_host || fold)) {
+        // one chunk: both arrays (and a fold's result) into pinned memory without a wait each, handed out after
+        // the sync below
         HostSlot& h = ctx->hsync;
-        LCV_TRY(host_alloc_grow(ctx, &h.out, &h.out_cap, 2 * (size_t)m));
+        LCV_TRY(host_alloc_grow(ctx, &h.out, &h.out_cap, 2 * (size_t)m + FOLD_RESULT_BYTES));
         LCV_TRY(be_d2h(ctx, h.out, ctx->W.verdict, m));
         LCV_TRY(be_d2h(ctx, h.out + m, ctx->W.reason, m));
+        if (fold) LCV_TRY(be_d2h(ctx, h.out + 2 * (size_t)m, ctx->W.fold_out, sizeof(FoldResult)));
         pinned_out = true;
       } else {
         if (verdict_host) LCV_TRY(be_d2h(ctx, verdict_host + base, ctx->W.verdict, m));
@@ -825,6 +870,7 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
     if (pinned_out) {
       if (verdict_host) memcpy(verdict_host, ctx->hsync.out, n);
       if (reason_host) memcpy(reason_host, ctx->hsync.out + n, n);
+      if (fold && fold->out) memcpy(fold->out, ctx->hsync.out + 2 * n, sizeof(FoldResult));
     }
     be_collect_timings(ctx);
     return LCV_OK;
@@ -833,6 +879,7 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
   if (async) {
     ctx->marks_off = true;  // nothing collects an asynchronous batch's stage marks
     ctx->hslot[slot].staged = false;
+    ctx->hslot[slot].folded = false;
   }
   rc = body();
   ctx->marks_off = marks_were_off;
@@ -910,7 +957,7 @@ static int store_index_check(lcv_ctx* ctx, const char* who, const uint32_t* stor
 // store_index null: against the context's store (lcv_validate_async); else row by row against the store table
 // (lcv_validate_stores_async), the 14th column staged with the others
 static int validate_async_host(lcv_ctx* ctx, const char* who, const lcv_update_batch* hb, const uint32_t* store_index,
-                               uint64_t current_slot, const uint8_t* gvr, int slot) {
+                               uint64_t current_slot, const uint8_t* gvr, int slot, const FoldReq* fold = nullptr) {
   if (store_index) LCV_TRY(store_index_check(ctx, who, store_index, hb->n));  // before the DMA
   BatchCols c;
   LCV_TRY(batch_cols(ctx, hb, c, who, store_index));
@@ -918,9 +965,10 @@ static int validate_async_host(lcv_ctx* ctx, const char* who, const lcv_update_b
   be_set_slot(ctx, slot);
   // the staging buffer is reused only after the slot's previous batch has left it
   int rc = be_wait_event(ctx, EV_H2D);
-  if (rc == LCV_OK && (c.total > h.pinned_cap || 2 * c.n > h.out_cap)) rc = be_sync_slot(ctx);
+  const size_t out_bytes = 2 * c.n + FOLD_RESULT_BYTES;  // verdicts, reasons, a fold's result
+  if (rc == LCV_OK && (c.total > h.pinned_cap || out_bytes > h.out_cap)) rc = be_sync_slot(ctx);
   if (rc == LCV_OK) rc = host_alloc_grow(ctx, &h.pinned, &h.pinned_cap, c.total);
-  if (rc == LCV_OK) rc = host_alloc_grow(ctx, &h.out, &h.out_cap, 2 * c.n);
+  if (rc == LCV_OK) rc = host_alloc_grow(ctx, &h.out, &h.out_cap, out_bytes);
   if (rc == LCV_OK && (c.total > h.dev_cap || !h.dev)) {
     if (h.dev) be_free(ctx, h.dev);
     h.dev = nullptr;
@@ -939,15 +987,17 @@ static int validate_async_host(lcv_ctx* ctx, const char* who, const lcv_update_b
   be_set_slot(ctx, 0);
   if (rc != LCV_OK) return rc;
   bind_batch(&h.db, (uint8_t*)h.dev, c);
-  LCV_TRY(validate_impl(ctx, &h.db, current_slot, gvr, nullptr, nullptr, nullptr, slot));
+  LCV_TRY(validate_impl(ctx, &h.db, current_slot, gvr, nullptr, nullptr, nullptr, slot, fold));
   be_set_slot(ctx, slot);
   const Work& W = ctx->Wslot[slot];
   rc = be_d2h(ctx, h.out, W.verdict, c.n);
   if (rc == LCV_OK) rc = be_d2h(ctx, h.out + c.n, W.reason, c.n);
+  if (rc == LCV_OK && fold) rc = be_d2h(ctx, h.out + 2 * c.n, W.fold_out, sizeof(FoldResult));
   be_set_slot(ctx, 0);
   if (rc != LCV_OK) return rc;
   h.out_n = c.n;
   h.staged = true;
+  h.folded = fold != nullptr;
   return LCV_OK;
 }
 
@@ -995,7 +1045,7 @@ int lcv_slot_wait(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint
 // host batch in, verdicts out, synchronous: against the context's store (store_index null) or, row by row,
 // against the store table
 static int validate_host(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index, uint64_t current_slot,
-                         const uint8_t* gvr, uint8_t* verdict_out, uint8_t* reason_out) {
+                         const uint8_t* gvr, uint8_t* verdict_out, uint8_t* reason_out, const FoldReq* fold = nullptr) {
   const bool table = store_index != nullptr;
   if (ctx && hb && gvr && (table ? ctx->table_set : ctx->store_set) && hb->n > 0 && hb->n <= ctx->chunk) {
     // one chunk (the reference's per-update call shape among them): the columns go through a reused pinned
@@ -1018,8 +1068,9 @@ static int validate_host(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_
     be_set_slot(ctx, 0);
     LCV_TRY(be_h2d(ctx, h.dev, h.pinned, c.total));
     bind_batch(&h.db, (uint8_t*)h.dev, c);
-    return validate_impl(ctx, &h.db, current_slot, gvr, verdict_out, reason_out, nullptr);  // returns synced
+    return validate_impl(ctx, &h.db, current_slot, gvr, verdict_out, reason_out, nullptr, -1, fold);  // returns synced
   }
+  if (fold) return fail(ctx, LCV_EINVAL, "lcv_validate_fold: null argument, no store set, or not 0 < n <= one chunk");
   // larger batches (and invalid arguments, reported by the upload): a device batch per call
   lcv_dbatch* db = nullptr;
   LCV_TRY(batch_upload(ctx, hb, store_index, &db));
@@ -1031,6 +1082,126 @@ static int validate_host(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_
 int lcv_validate_updates(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t current_slot, const uint8_t* gvr,
                          uint8_t* verdict_out, uint8_t* reason_out) {
   return validate_host(ctx, hb, nullptr, current_slot, gvr, verdict_out, reason_out);
+}
+
+// ---- the store fold (include/lcv.h; lcv_fold.hpp): lcv_validate_updates / lcv_validate_async with F_rank beside
+// the pre-checks and F_fold behind the verdicts, the result travelling back with them
+int lcv_validate_fold(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t current_slot, const uint8_t* gvr,
+                      const lcv_fold_state* in, uint8_t* verdict_out, uint8_t* reason_out, lcv_fold_result* out) {
+  if (!ctx || !hb || !gvr || !out) return fail(ctx, LCV_EINVAL, "lcv_validate_fold: null argument");
+  if (!ctx->store_set) return fail(ctx, LCV_ESTATE, "lcv_validate_fold: lcv_set_store has not been called");
+  if (hb->n == 0 || hb->n > LCV_FOLD_MAX_ROWS || hb->n > ctx->chunk)
+    return fail(ctx, LCV_EINVAL, "lcv_validate_fold: need 0 < n <= 65536 (one chunk): cut larger batches and carry `next` forward");
+  FoldReq req;
+  LCV_TRY(fold_state_in(ctx, "lcv_validate_fold", in, req.in));
+  req.out = out;
+  return validate_host(ctx, hb, nullptr, current_slot, gvr, verdict_out, reason_out, &req);
+}
+
+int lcv_validate_async_fold(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t current_slot, const uint8_t* gvr,
+                            const lcv_fold_state* in, int slot) {
+  if (!ctx || !hb || !gvr || slot < 0 || slot >= LCV_SLOTS)
+    return fail(ctx, LCV_EINVAL, "lcv_validate_async_fold: null argument or slot not in 0..7");
+  if (!ctx->store_set) return fail(ctx, LCV_ESTATE, "lcv_validate_async_fold: lcv_set_store has not been called");
+  if (hb->n == 0 || hb->n > LCV_FOLD_MAX_ROWS || hb->n > ctx->chunk)
+    return fail(ctx, LCV_EINVAL, "lcv_validate_async_fold: need 0 < n <= 65536 (one chunk) per call");
+  FoldReq req;
+  LCV_TRY(fold_state_in(ctx, "lcv_validate_async_fold", in, req.in));
+  req.out = nullptr;  // the result waits in the slot's pinned area for lcv_slot_wait_fold
+  return validate_async_host(ctx, "lcv_validate_async_fold", hb, nullptr, current_slot, gvr, slot, &req);
+}
+
+int lcv_slot_wait_fold(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint8_t* reason_out, lcv_fold_result* out) {
+  if (!ctx || !out || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_slot_wait_fold: null argument or slot not in 0..7");
+  HostSlot& h = ctx->hslot[slot];
+  if (!h.staged || !h.folded) return fail(ctx, LCV_ESTATE, "lcv_slot_wait_fold: the slot's batch was not enqueued with a fold");
+  LCV_TRY(lcv_slot_wait(ctx, slot, n, verdict_out, reason_out));  // waits for the slot
+  memcpy(out, h.out + 2 * h.out_n, sizeof(FoldResult));
+  return LCV_OK;
+}
+
+// test hook: F_fold alone on caller-supplied rank records and verdicts (no validation, no store)
+int lcv_debug_fold(lcv_ctx* ctx, const uint8_t* rank, const uint8_t* verdict, uint64_t n, uint64_t store_finalized_slot,
+                   int next_known, const lcv_fold_state* in, lcv_fold_result* out) {
+  if (!ctx || !rank || !verdict || !out) return fail(ctx, LCV_EINVAL, "lcv_debug_fold: null argument");
+  if (n == 0 || n > LCV_FOLD_MAX_ROWS) return fail(ctx, LCV_EINVAL, "lcv_debug_fold: need 0 < n <= 65536");
+  FoldState s;
+  LCV_TRY(fold_state_in(ctx, "lcv_debug_fold", in, s));
+  // the three fields F_fold touches, in an allocation of their own (a whole work space of n rows is not needed)
+  const size_t o_ver = (rank_index((size_t)n) + 255) & ~(size_t)255, o_out = o_ver + (((size_t)n + 255) & ~(size_t)255);
+  void* mem = nullptr;
+  be_set_slot(ctx, 0);
+  LCV_TRY(be_alloc(ctx, &mem, o_out + FOLD_RESULT_BYTES));
+  uint8_t* m = (uint8_t*)mem;
+  Work W = Work{};
+  W.cap = (uint32_t)n;
+  W.rank = m;
+  W.verdict = m + o_ver;
+  W.fold_out = m + o_out;
+  be_reset_timings(ctx);
+  FoldResult res;
+  auto body = [&]() -> int {
+    LCV_TRY(be_h2d(ctx, W.rank, rank, rank_index((size_t)n)));
+    LCV_TRY(be_h2d(ctx, W.verdict, verdict, (size_t)n));
+    be_stage_begin(ctx, ST_FOLD);
+    LCV_TRY(be_launch_team(ctx, F_fold{W, s, store_finalized_slot, next_known ? 1u : 0u, (uint32_t)n}, 1));
+    be_stage_end(ctx, ST_FOLD);
+    LCV_TRY(be_d2h(ctx, &res, W.fold_out, sizeof(res)));
+    return be_sync(ctx);
+  };
+  const int rc = body();
+  be_free(ctx, mem);  // (waits for the streams)
+  if (rc != LCV_OK) return rc;
+  be_collect_timings(ctx);
+  memcpy(out, &res, sizeof(res));
+  return LCV_OK;
+}
+
+// the rank records of a host batch: only the six columns F_rank reads are looked at and uploaded (every other
+// pointer of the batch may be null), in pieces of one chunk; no store, no work space
+int lcv_rank_updates(lcv_ctx* ctx, const lcv_update_batch* hb, uint8_t* rank_out) {
+  if (!ctx || !hb || !rank_out) return fail(ctx, LCV_EINVAL, "lcv_rank_updates: null argument");
+  if (!hb->sync_bits || !hb->nsc_branch || !hb->finality_branch || !hb->attested.beacon || !hb->finalized.beacon ||
+      !hb->signature_slot)
+    return fail(ctx, LCV_EINVAL, "lcv_rank_updates: null column (sync_bits, nsc_branch, finality_branch, attested.beacon, "
+                                 "finalized.beacon, signature_slot are read)");
+  if (hb->n == 0 || hb->n > 0xffffffffull) return fail(ctx, LCV_EINVAL, "lcv_rank_updates: need 0 < n < 2^32");
+  const size_t n = hb->n, piece = n < kChunk ? n : kChunk;
+  const size_t width[6] = {K_BEACON, K_BEACON, K_NSC_BRANCH, K_FIN_BRANCH, 64, 8};
+  const uint8_t* src[6] = {hb->attested.beacon, hb->finalized.beacon, hb->nsc_branch, hb->finality_branch, hb->sync_bits,
+                           (const uint8_t*)hb->signature_slot};
+  size_t off[7], total = 0;
+  for (int k = 0; k < 7; ++k) {
+    off[k] = total;
+    total += ((k < 6 ? width[k] : (size_t)RANK_BYTES) * piece + 255) & ~(size_t)255;
+  }
+  void* mem = nullptr;
+  be_set_slot(ctx, 0);
+  LCV_TRY(be_alloc(ctx, &mem, total));
+  uint8_t* m = (uint8_t*)mem;
+  BatchDev B = {};
+  B.att_beacon = m + off[0]; B.fin_beacon = m + off[1]; B.nsc_branch = m + off[2]; B.finality_branch = m + off[3];
+  B.bits = m + off[4]; B.sig_slot = (const uint64_t*)(m + off[5]);
+  Work W = Work{};
+  W.rank = m + off[6];
+  Params P = {};
+  P.cfg = ctx->cfg;
+  be_reset_timings(ctx);
+  auto body = [&]() -> int {
+    for (size_t base = 0; base < n; base += piece) {
+      const size_t len = n - base < piece ? n - base : piece;
+      for (int k = 0; k < 6; ++k) LCV_TRY(be_h2d(ctx, m + off[k], src[k] + width[k] * base, width[k] * len));
+      B.n = (uint32_t)len;
+      LCV_TRY(rank_stage(ctx, B, P, W, (uint32_t)len));
+      LCV_TRY(be_d2h(ctx, rank_out + rank_index(base), W.rank, rank_index(len)));
+      LCV_TRY(be_sync(ctx));  // the caller's pageable memory: each piece has left before the buffers are reused
+    }
+    be_collect_timings(ctx);
+    return LCV_OK;
+  };
+  const int rc = body();
+  be_free(ctx, mem);  // (waits for the streams)
+  return rc;
 }
 
 // ---- store table: a store snapshot per update (a catch-up over several sync-committee periods, whose updates
@@ -1298,7 +1469,8 @@ int lcv_debug_set_chunk(lcv_ctx* ctx, uint64_t rows) {
 // lcv_functors_sop.hpp lines_index): item i of field k covers `rows` elements of `esize` bytes, element r at
 // base + index(i, r).
 // kind 0 SoA (stride cap), 1 f, 2 lines, 3 committee-pool SoA (stride pool_cap, one item per distinct committee;
-// work_view does not advance these: they are not per update)
+// work_view does not advance these: they are not per update), 4 the rank records (item-major, lcv_fold.hpp
+// rank_index), 5 one per work space (the fold's result: a single item, not advanced by work_view either)
 struct FieldRef { const char* name; const uint8_t* base; size_t esize, rows; int kind; size_t pool_cap = 0; };
 static int work_fields(const Work& W, FieldRef* f) {
   int n = 0;
@@ -1320,6 +1492,8 @@ static int work_fields(const Work& W, FieldRef* f) {
   f[n++] = {"lines", (const uint8_t*)W.lines, 4, SOP_LINE_WORDS, 2};
   f[n++] = {"nsc_root", (const uint8_t*)W.nsc_root, 4, 8, 3, W.pool_cap};
   f[n++] = {"nsc_flags", W.nsc_flags, 1, 1, 3, W.pool_cap};
+  f[n++] = {"rank", W.rank, 1, RANK_BYTES, 4};
+  f[n++] = {"fold_out", W.fold_out, 1, FOLD_RESULT_BYTES, 5, 1};
   return n;
 }
 // byte address of element r of item i (cap: the stride of the SoA fields)
@@ -1328,6 +1502,8 @@ static const uint8_t* field_addr(const FieldRef& f, size_t cap, size_t i, size_t
   if (f.kind == 0) idx = soa_index(cap, i, r);
   else if (f.kind == 1) idx = f12_index(i, (uint32_t)(r / 12)) + r % 12;
   else if (f.kind == 3) idx = soa_index(f.pool_cap, i, r);
+  else if (f.kind == 4) idx = rank_index(i) + r;
+  else if (f.kind == 5) idx = r;
   else idx = lines_index(i) + r;
   return f.base + idx * f.esize;
 }
@@ -1347,7 +1523,7 @@ extern "C" int lcv_debug_work_check(lcv_ctx* ctx, uint64_t cap, uint64_t slice, 
       work_fields(work_view(W, b), part);
       const size_t len = C - b < slice ? C - b : slice;
       for (int k = 0; k < nf; ++k)
-        if (full[k].kind != 3)
+        if (full[k].kind != 3 && full[k].kind != 5)
         for (size_t j = 0; j < len; ++j)
           for (size_t r = 0; r < full[k].rows; ++r)
             if (field_addr(part[k], C, j, r) != field_addr(full[k], C, b + j, r))
@@ -1369,7 +1545,7 @@ extern "C" int lcv_debug_work_check(lcv_ctx* ctx, uint64_t cap, uint64_t slice, 
     for (int k = 0; k < nf; ++k) {
       const uint8_t* lo = field_addr(fr[k], C, 0, 0);
       const uint8_t* hi = lo;
-      const size_t items = fr[k].kind == 3 ? fr[k].pool_cap : C;
+      const size_t items = (fr[k].kind == 3 || fr[k].kind == 5) ? fr[k].pool_cap : C;
       for (size_t i = 0; i < items; ++i)
         for (size_t r = 0; r < fr[k].rows; ++r) {
           const uint8_t* a = field_addr(fr[k], C, i, r);

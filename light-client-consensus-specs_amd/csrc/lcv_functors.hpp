@@ -3,6 +3,7 @@
 // The including file defines LCV_HD (the call-operator qualifier: __device__ or empty).
 #pragma once
 #include "lcv_items.hpp"
+#include "lcv_fold.hpp"
 
 using namespace lcv;
 
@@ -22,6 +23,17 @@ struct F_nsc_eq_team {
   LCV_HD uint32_t rounds() const { return NSCEQ_ROUNDS; }
   LCV_HD void operator()(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, uint32_t*) const {
     item_nsc_eq_team(i, lane, r, lds, B, C, S, P, W);
+  }
+};
+// store fold (lcv_validate_fold, lcv_rank_updates; lcv_fold.hpp): the rank record of every update, and the fold of
+// records and verdicts into the next store state — one 64-lane team for the whole batch, phases as rounds
+struct F_rank { BatchDev B; Params P; Work W; LCV_HD void operator()(uint32_t i) const { item_rank(i, B, P, W); } };
+struct F_fold {
+  Work W; FoldState in; uint64_t store_fin_slot; uint32_t next_known; uint32_t n;
+  static constexpr uint32_t TEAM = FOLD_TEAM, LDS_WORDS = FOLD_LDS, SHARED_WORDS = 0;
+  LCV_HD uint32_t rounds() const { return FOLD_ROUNDS; }
+  LCV_HD void operator()(uint32_t, uint32_t lane, uint32_t r, uint32_t* lds, uint32_t*) const {
+    item_fold_team(lane, r, lds, W, in, store_fin_slot, next_known, n);
   }
 };
 struct F_sigroot { BatchDev B; Params P; Work W; LCV_HD void operator()(uint32_t i) const { item_sigroot(i, B, P, W); } };

@@ -94,6 +94,8 @@ struct Work {
   uint8_t* reason;       // [cap]
   uint32_t* lines;       // [item][2 pairings][6 * 68 line values][12]  (SOP Miller loop: lines -> accumulation)
   uint32_t msg_b0;       // 1: W.msg already holds expand_message_xmd's b0 (arbitrary-length messages)
+  uint8_t* rank;         // [cap][32] rank record of update i (item-major, lcv_fold.hpp rank_index); the _fold calls only
+  uint8_t* fold_out;     // [128] the fold's result (one per work space, lcv_fold.hpp FoldResult)
 };
 
 // fp2 coefficient g_i (of w^i) -> its fp2 slot in the SoA Fp12 layout of soa_st_fp12 (c0.c0, c0.c1,

@@ -60,6 +60,33 @@ class StoreTable(C.Structure):
     ]
 
 
+class FoldStateC(C.Structure):
+    """lcv_fold_state (48 bytes)."""
+    _fields_ = [
+        ("optimistic_slot", C.c_uint64),
+        ("previous_max_active_participants", C.c_uint64),
+        ("current_max_active_participants", C.c_uint64),
+        ("has_best", C.c_uint32),
+        ("best_key0", C.c_uint32),
+        ("best_attested_slot", C.c_uint64),
+        ("best_signature_slot", C.c_uint64),
+    ]
+
+
+class FoldResultC(C.Structure):
+    """lcv_fold_result."""
+    _fields_ = [
+        ("next", FoldStateC),
+        ("rows_consumed", C.c_uint64),
+        ("apply_row", C.c_int64),
+        ("best_row", C.c_int64),
+        ("optimistic_row", C.c_int64),
+        ("accepted_count", C.c_uint64),
+    ]
+
+
+RANK_BYTES = 32
+FOLD_MAX_ROWS = 65536
 STORE_NEXT_UNKNOWN = 0xFFFFFFFF
 STORE_TABLE_MAX_COMMITTEES = 4096
 
@@ -73,6 +100,14 @@ SIGNATURES = {
     "lcv_validate_updates": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), C.c_uint64, u8p, u8p, u8p]),
     "lcv_set_store_table": (C.c_int, [C.c_void_p, C.POINTER(StoreTable), u8p]),
     "lcv_validate_updates_stores": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), u32p, C.c_uint64, u8p, u8p, u8p]),
+    "lcv_rank_updates": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), u8p]),
+    "lcv_validate_fold": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), C.c_uint64, u8p, C.POINTER(FoldStateC), u8p, u8p,
+                                    C.POINTER(FoldResultC)]),
+    "lcv_validate_async_fold": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), C.c_uint64, u8p, C.POINTER(FoldStateC),
+                                          C.c_int]),
+    "lcv_slot_wait_fold": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, u8p, u8p, C.POINTER(FoldResultC)]),
+    "lcv_debug_fold": (C.c_int, [C.c_void_p, u8p, u8p, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(FoldStateC),
+                                 C.POINTER(FoldResultC)]),
     "lcv_batch_upload": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), C.POINTER(C.c_void_p)]),
     "lcv_batch_upload_stores": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), u32p, C.POINTER(C.c_void_p)]),
     "lcv_batch_free": (None, [C.c_void_p, C.c_void_p]),

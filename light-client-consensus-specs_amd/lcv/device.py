@@ -8,10 +8,57 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from . import config as _config
-from ._native import (Lib, LcvError, UpdateBatch, HeaderCols, StoreTable, STORE_NEXT_UNKNOWN, as_u8, load, ptr)
+from ._native import (Lib, LcvError, UpdateBatch, HeaderCols, StoreTable, FoldStateC, FoldResultC,
+                      STORE_NEXT_UNKNOWN, as_u8, load, ptr)
 
 SYNC_COMMITTEE_BYTES = 24624
 EXEC_RECORD_BYTES = 832
+
+# the 32-byte rank record of an update (include/lcv.h): is_better_update(a, b) (sync-protocol.md:260-311) iff
+# (key0_a, -attested_a, -signature_a) > (key0_b, -attested_b, -signature_b)
+RANK_DTYPE = np.dtype([("key0", "<u4"), ("flags", "<u4"), ("attested_slot", "<u8"), ("signature_slot", "<u8"),
+                       ("finalized_slot", "<u8")])
+RANK_SUPER, RANK_REL_SC, RANK_FIN, RANK_FIN_SC, RANK_N_MASK = 1 << 23, 1 << 12, 1 << 11, 1 << 10, 0x3FF
+
+
+@dataclass
+class FoldState:
+    """lcv_fold_state: what the post-validation store logic reads besides validation's own store values."""
+    optimistic_slot: int = 0
+    previous_max_active_participants: int = 0
+    current_max_active_participants: int = 0
+    has_best: bool = False
+    best_key0: int = 0
+    best_attested_slot: int = 0
+    best_signature_slot: int = 0
+
+    def to_c(self) -> FoldStateC:
+        return FoldStateC(int(self.optimistic_slot), int(self.previous_max_active_participants),
+                          int(self.current_max_active_participants), 1 if self.has_best else 0, int(self.best_key0),
+                          int(self.best_attested_slot), int(self.best_signature_slot))
+
+    @staticmethod
+    def from_c(c: FoldStateC) -> "FoldState":
+        return FoldState(int(c.optimistic_slot), int(c.previous_max_active_participants),
+                         int(c.current_max_active_participants), bool(c.has_best), int(c.best_key0),
+                         int(c.best_attested_slot), int(c.best_signature_slot))
+
+
+@dataclass
+class FoldResult:
+    """lcv_fold_result: the state after the consumed rows (maxima and optimistic slot before
+    apply_light_client_update of apply_row), and the rows the host needs; -1 = none."""
+    next: FoldState
+    rows_consumed: int
+    apply_row: int
+    best_row: int
+    optimistic_row: int
+    accepted_count: int
+
+    @staticmethod
+    def from_c(c: FoldResultC) -> "FoldResult":
+        return FoldResult(FoldState.from_c(c.next), int(c.rows_consumed), int(c.apply_row), int(c.best_row),
+                          int(c.optimistic_row), int(c.accepted_count))
 
 
 @dataclass
@@ -301,6 +348,67 @@ class Verifier:
         self._check(self.lib.lcv_validate_stores_async(self.ctx, C.byref(b), ptr(six, C.c_uint32), int(current_slot),
                                                        ptr(gvr), int(slot)), "lcv_validate_stores_async")
         del keep
+
+    # ------------------------------------------------------------------ store fold (include/lcv.h)
+    def rank(self, batch: PackedUpdates) -> np.ndarray:
+        """The rank record of every update (lcv_rank_updates) as a RANK_DTYPE array; no store needed."""
+        b, keep = batch.to_c()
+        out = np.zeros(batch.n, RANK_DTYPE)
+        if batch.n:
+            self._check(self.lib.lcv_rank_updates(self.ctx, C.byref(b), ptr(out.view(np.uint8))), "lcv_rank_updates")
+        return out
+
+    def _no_table_fold(self, store_index, what: str) -> None:
+        if store_index is not None:  # the C entries take no store_index: a table batch has no fold
+            raise LcvError(f"{what}: status -1: no fold of a store-table batch (a batch with a store_index)")
+
+    def validate_fold(self, batch: PackedUpdates, current_slot: int, genesis_validators_root: bytes,
+                      state: FoldState, store_index=None):
+        """validate + the device fold of process_light_client_update's post-validation logic over the batch
+        (lcv_validate_fold; at most 65,536 rows) -> (verdicts, reason codes, FoldResult)."""
+        self._no_table_fold(store_index, "lcv_validate_fold")
+        b, keep = batch.to_c()
+        gvr = as_u8(bytes(genesis_validators_root))
+        v = np.zeros(batch.n, np.uint8)
+        r = np.zeros(batch.n, np.uint8)
+        st, res = state.to_c(), FoldResultC()
+        self._check(self.lib.lcv_validate_fold(self.ctx, C.byref(b), int(current_slot), ptr(gvr), C.byref(st), ptr(v),
+                                               ptr(r), C.byref(res)), "lcv_validate_fold")
+        return v.astype(bool), r, FoldResult.from_c(res)
+
+    def validate_async_fold(self, batch: PackedUpdates, current_slot: int, genesis_validators_root: bytes,
+                            state: FoldState, slot: int, store_index=None) -> None:
+        """validate_async with the fold (lcv_validate_async_fold); collect with slot_wait_fold(slot)."""
+        self._no_table_fold(store_index, "lcv_validate_async_fold")
+        b, keep = batch.to_c()
+        gvr = as_u8(bytes(genesis_validators_root))
+        st = state.to_c()
+        self._check(self.lib.lcv_validate_async_fold(self.ctx, C.byref(b), int(current_slot), ptr(gvr), C.byref(st),
+                                                     int(slot)), "lcv_validate_async_fold")
+        del keep
+
+    def slot_wait_fold(self, slot: int, n: int):
+        """Wait for the folded batch of `slot` -> (verdicts, reason codes, FoldResult); LcvError (status -4) if
+        the slot's batch was not enqueued with a fold."""
+        v = np.zeros(n, np.uint8)
+        r = np.zeros(n, np.uint8)
+        res = FoldResultC()
+        self._check(self.lib.lcv_slot_wait_fold(self.ctx, int(slot), int(n), ptr(v), ptr(r), C.byref(res)),
+                    "lcv_slot_wait_fold")
+        return v.astype(bool), r, FoldResult.from_c(res)
+
+    def debug_fold(self, rank: np.ndarray, verdict: np.ndarray, store_finalized_slot: int, next_known: bool,
+                   state: FoldState) -> FoldResult:
+        """Test hook (lcv_debug_fold): the fold kernel alone on caller-supplied rank records and verdicts."""
+        rk = np.ascontiguousarray(rank, RANK_DTYPE)
+        vd = np.ascontiguousarray(verdict, np.uint8)
+        if rk.shape != vd.shape or rk.ndim != 1:
+            raise ValueError("need one verdict per rank record")
+        st, res = state.to_c(), FoldResultC()
+        self._check(self.lib.lcv_debug_fold(self.ctx, ptr(rk.view(np.uint8)), ptr(vd), rk.shape[0],
+                                            int(store_finalized_slot), 1 if next_known else 0, C.byref(st),
+                                            C.byref(res)), "lcv_debug_fold")
+        return FoldResult.from_c(res)
 
     def event_pool(self) -> int:
         """HIP events held for stage timings (test hook: must stay bounded under asynchronous calls)."""

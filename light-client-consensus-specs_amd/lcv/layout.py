@@ -20,6 +20,7 @@ No BLS or SHA arithmetic happens here: packing is pure byte plumbing (the device
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Iterable, List, Sequence, Tuple
 
 import numpy as np
@@ -119,3 +120,58 @@ def pack_bits(bits: Sequence) -> bytes:
 
 def unpack_bits(b64: bytes) -> List[bool]:
     return [bool(x) for x in np.unpackbits(np.frombuffer(bytes(b64), np.uint8), bitorder="little")]
+
+
+# ------------------------------------------------------------------ the inverse: packed rows -> duck-typed objects
+def unpack_beacon(b: bytes):
+    b = bytes(b)
+    return SimpleNamespace(slot=int.from_bytes(b[0:8], "little"), proposer_index=int.from_bytes(b[8:16], "little"),
+                           parent_root=b[16:48], state_root=b[48:80], body_root=b[80:112])
+
+
+def unpack_execution(rec: bytes):
+    rec = bytes(rec)
+    out = {}
+    for k, name in enumerate(EXEC_FIELDS):
+        chunk = rec[32 * k:32 * k + 32]
+        if name == "logs_bloom":
+            out[name] = rec[EXEC_BLOOM_OFF:EXEC_BLOOM_OFF + 256]
+        elif name == "extra_data":
+            out[name] = chunk[:int.from_bytes(rec[EXEC_EXTRALEN_OFF:EXEC_EXTRALEN_OFF + 4], "little")]
+        elif name in _U64_FIELDS:
+            out[name] = int.from_bytes(chunk[:8], "little")
+        elif name == "base_fee_per_gas":
+            out[name] = int.from_bytes(chunk, "little")
+        elif name == "fee_recipient":
+            out[name] = chunk[:20]
+        else:
+            out[name] = chunk
+    return SimpleNamespace(**out)
+
+
+def unpack_header(beacon: bytes, execution: bytes, branch: bytes):
+    branch = bytes(branch)
+    return SimpleNamespace(beacon=unpack_beacon(beacon), execution=unpack_execution(execution),
+                           execution_branch=[branch[32 * k:32 * k + 32] for k in range(4)])
+
+
+def unpack_sync_committee(sc: bytes):
+    sc = bytes(sc)
+    return SimpleNamespace(pubkeys=[sc[PUBKEY_BYTES * j:PUBKEY_BYTES * (j + 1)] for j in range(SYNC_COMMITTEE_SIZE)],
+                           aggregate_pubkey=sc[SYNC_COMMITTEE_SIZE * PUBKEY_BYTES:])
+
+
+def unpack_update(packed, i: int):
+    """Row i of a PackedUpdates batch as a duck-typed LightClientUpdate (the reference's field names,
+    sync-protocol.md:120-133): the inverse of packing — pack_updates([unpack_update(p, i)]) is row i again."""
+    t = lambda a: np.asarray(a[i]).tobytes()  # noqa: E731
+    nbr, fbr = t(packed.nsc_branch), t(packed.finality_branch)
+    return SimpleNamespace(
+        attested_header=unpack_header(t(packed.att_beacon), t(packed.att_exec), t(packed.att_branch)),
+        next_sync_committee=unpack_sync_committee(packed.nsc_pool[int(packed.nsc_index[i])].tobytes()),
+        next_sync_committee_branch=[nbr[32 * k:32 * k + 32] for k in range(5)],
+        finalized_header=unpack_header(t(packed.fin_beacon), t(packed.fin_exec), t(packed.fin_branch)),
+        finality_branch=[fbr[32 * k:32 * k + 32] for k in range(6)],
+        sync_aggregate=SimpleNamespace(sync_committee_bits=unpack_bits(t(packed.sync_bits)),
+                                       sync_committee_signature=t(packed.sync_signature)),
+        signature_slot=int(packed.signature_slot[i]))

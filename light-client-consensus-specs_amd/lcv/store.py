@@ -41,8 +41,9 @@ import numpy as np
 from . import config
 from . import layout as L
 from . import runtime
-from .device import Verifier
-from .sync_protocol import REASONS, validate_light_client_updates, validate_under_store_keys
+from ._native import FOLD_MAX_ROWS
+from .device import (FoldState, PackedUpdates, RANK_DTYPE, RANK_FIN, RANK_FIN_SC, RANK_REL_SC, RANK_SUPER, Verifier)
+from .sync_protocol import REASONS, pack_updates, validate_light_client_updates, validate_under_store_keys
 
 # SLOTS_PER_EPOCH * EPOCHS_PER_SYNC_COMMITTEE_PERIOD and UPDATE_TIMEOUT (sync-protocol.md:89) come from the
 # active network configuration (lcv.config.active(); mainnet unless set)
@@ -258,6 +259,124 @@ def sync_light_client_updates(store, updates: Sequence, current_slot: int, genes
         stats_out["validate_calls"] = calls
         stats_out["rows_validated"] = rows
     return accepted
+
+
+# ------------------------------------------------------------------ the device fold (include/lcv.h)
+def _rank_key(update) -> np.void:
+    """The device's rank record (lcv.device.RANK_DTYPE) of one update object, computed on the host: the store's
+    own best_valid_update enters the fold through it."""
+    n = _participants(update)
+    att, sig, fin = _slot(update.attested_header), int(update.signature_slot), _slot(update.finalized_header)
+    is_sc, is_fin = is_sync_committee_update(update), is_finality_update(update)
+    period = compute_sync_committee_period_at_slot
+    key0 = (RANK_SUPER if n * 3 >= L.SYNC_COMMITTEE_SIZE * 2 else n << 13) | n
+    if is_sc and period(att) == period(sig):
+        key0 |= RANK_REL_SC
+    if is_fin:
+        key0 |= RANK_FIN
+        if period(fin) == period(att):
+            key0 |= RANK_FIN_SC
+    return np.array([(key0, 1 if is_sc else 0, att, sig, fin)], RANK_DTYPE)[0]
+
+
+def _fold_check_config(v: Verifier, who: str) -> None:
+    if v.config != config.active():
+        raise ValueError(f"{who}: the verifier validates under network configuration "
+                         f"{v.config.name!r} but lcv.config.active() is {config.active().name!r}; call "
+                         f"lcv.config.set_active() (or Verifier.set_config) so both sides agree")
+
+
+def fold_light_client_updates(store, updates, current_slot: int, genesis_validators_root: bytes,
+                              verifier: Optional[Verifier] = None, reasons_out: Optional[list] = None,
+                              stats_out: Optional[dict] = None) -> np.ndarray:
+    """`process_light_client_updates` — the same accept flags, reason codes and final store — with the store
+    logic after validation folded on the device (Verifier.validate_fold): best update, max participants,
+    optimistic header and the first row that applies come back with the verdicts, so no per-row Python remains.
+
+    `updates`: a sequence of update objects or a PackedUpdates batch (rows the store ends up holding are rebuilt
+    with lcv.layout.unpack_update).  Per segment: the store is set, the fold state built from it (the old best's
+    rank by _rank_key), validate_fold run over chunks of at most 65,536 rows until one reports an apply_row, the
+    store's current_max_active_participants / optimistic_header / best_valid_update written from the result's
+    rows, the applying row applied with apply_light_client_update, and the next segment starts after it.
+
+    stats_out (optional dict) receives validate_calls and segments."""
+    v = verifier if verifier is not None else runtime.default_verifier()
+    _fold_check_config(v, "fold_light_client_updates")
+    packed = isinstance(updates, PackedUpdates)
+    batch = updates if packed else pack_updates(updates)
+    row = (lambda i: L.unpack_update(batch, i)) if packed else (lambda i: updates[i])
+    n = batch.n
+    accepted = np.zeros(n, bool)
+    reasons = np.zeros(n, np.uint8)
+    chunk = min(FOLD_MAX_ROWS, int(getattr(v, "chunk_rows", FOLD_MAX_ROWS)))
+    calls = segments = 0
+    start = 0
+    while start < n:
+        segments += 1
+        runtime.ensure_store(v, *_validation_key(store))
+        state = FoldState(optimistic_slot=_slot(store.optimistic_header),
+                          previous_max_active_participants=int(store.previous_max_active_participants),
+                          current_max_active_participants=int(store.current_max_active_participants))
+        if store.best_valid_update is not None:
+            k = _rank_key(store.best_valid_update)
+            state.has_best, state.best_key0 = True, int(k["key0"])
+            state.best_attested_slot, state.best_signature_slot = int(k["attested_slot"]), int(k["signature_slot"])
+        pos, apply_row, best_row, optimistic_row = start, -1, -1, -1
+        while pos < n and apply_row < 0:
+            ok, rs, res = v.validate_fold(batch.slice(pos, min(n, pos + chunk)), int(current_slot),
+                                          bytes(genesis_validators_root), state)
+            calls += 1
+            k = res.rows_consumed
+            accepted[pos:pos + k] = ok[:k]
+            reasons[pos:pos + k] = rs[:k]
+            if res.best_row >= 0:
+                best_row = pos + res.best_row
+            if res.optimistic_row >= 0:
+                optimistic_row = pos + res.optimistic_row
+            if res.apply_row >= 0:
+                apply_row = pos + res.apply_row
+            state = res.next
+            pos += k
+        store.current_max_active_participants = state.current_max_active_participants
+        if optimistic_row >= 0:
+            store.optimistic_header = row(optimistic_row).attested_header
+        if apply_row >= 0:
+            apply_light_client_update(store, row(apply_row))
+            store.best_valid_update = None
+        elif best_row >= 0:
+            store.best_valid_update = row(best_row)
+        start = pos
+    if reasons_out is not None:
+        reasons_out.extend(int(r) for r in reasons)
+    if stats_out is not None:
+        stats_out["validate_calls"] = calls
+        stats_out["segments"] = segments
+    return accepted
+
+
+def rank_updates(updates, verifier: Optional[Verifier] = None) -> np.ndarray:
+    """The device's rank records (lcv.device.RANK_DTYPE, one per update) of update objects or a PackedUpdates
+    batch: is_better_update(a, b) iff (key0_a, -attested_a, -signature_a) > (key0_b, -attested_b, -signature_b)."""
+    v = verifier if verifier is not None else runtime.default_verifier()
+    return v.rank(updates if isinstance(updates, PackedUpdates) else pack_updates(updates))
+
+
+def best_update_per_period(updates, verifier: Optional[Verifier] = None) -> dict:
+    """full-node.md:184-187: the best LightClientUpdate (according to is_better_update) for each sync committee
+    period -> {period: row}.  A row belongs to the period of its attested header; rows whose signature_slot lies
+    in another period are left out.  Per period the first arg-max of the device's rank records (one lexsort)."""
+    v = verifier if verifier is not None else runtime.default_verifier()
+    rec = rank_updates(updates, v)
+    spp = v.config.SLOTS_PER_PERIOD
+    period = rec["attested_slot"] // np.uint64(spp)
+    rows = np.nonzero(period == rec["signature_slot"] // np.uint64(spp))[0]
+    if rows.size == 0:
+        return {}
+    r = rec[rows]
+    order = np.lexsort((rows, r["signature_slot"], r["attested_slot"], -r["key0"].astype(np.int64), period[rows]))
+    p = period[rows][order]
+    first = np.concatenate(([True], p[1:] != p[:-1]))
+    return {int(pp): int(rr) for pp, rr in zip(p[first], rows[order][first])}
 
 
 def process_light_client_update(store, update, current_slot: int, genesis_validators_root: bytes,
