@@ -203,8 +203,32 @@ int lcv_validate_updates_stores(lcv_ctx* ctx, const lcv_update_batch* batch, con
  * apply_row is -1.  lcv_validate_async_fold is lcv_validate_async with the fold; lcv_slot_wait_fold is
  * lcv_slot_wait plus the result, and returns LCV_ESTATE for a slot whose batch was not enqueued with a fold.
  * lcv_debug_fold (test hook) runs the fold alone on caller-supplied records and verdicts, no validation.
- * Out of scope, refused or absent: a fold of a store-table batch (a batch with a store_index has no _fold entry),
- * a sharded fold, and lcv.serving.validate_stream does not fold. */
+ * A batch with a store_index is refused by these entries (LCV_EINVAL): its fold is the segmented fold below.
+ *
+ * The segmented fold: one call validates a store-table batch and folds it per store.  A segment is the subsequence
+ * of the batch's rows that share one store_index value s, in batch order; the rows of different stores may
+ * interleave in any way, and segments are independent (a row that applies in one store consumes nothing in
+ * another).  For every store s with at least one row, out[s] is exactly the fold above of that subsequence, run
+ * against store row s of the table (its finalized slot; next committee known iff next[s] is a committee row that
+ * is not all zero) from the state in[s], except that apply_row, best_row and optimistic_row are BATCH row numbers
+ * (-1: none); rows_consumed and accepted_count count rows of the segment.  Row i of store s is consumed iff
+ * out[s].apply_row < 0 || i <= out[s].apply_row.  `in` and `out` have one entry per store row of the table; only
+ * the entries of stores that have a row in the batch are read, and only those are written: out[s] of a store with
+ * no row is left untouched.  The host groups the rows by store in the pass that checks the indices (O(n log n),
+ * independent of nstore); the grouping and the present stores' states travel with the batch's columns in its one
+ * host-to-device copy, one 64-lane team per store present folds behind the verdicts (lcv_last_timings: the
+ * store_fold stage), and 128 bytes per store present travel back with the verdicts.  A slot's result buffer is
+ * allocated by its first segmented fold.
+ * lcv_validate_stores_fold is lcv_validate_updates_stores + that fold (n <= LCV_FOLD_MAX_ROWS and one chunk, else
+ * LCV_EINVAL; LCV_ESTATE without a table; LCV_EINVAL naming the row of a store_index >= nstore, or the store of a
+ * present in[s] whose maxima exceed 512 — all before any launch).  lcv_validate_stores_async_fold is
+ * lcv_validate_stores_async with it; lcv_slot_wait_stores_fold collects it and returns LCV_ESTATE for a slot not
+ * enqueued by lcv_validate_stores_async_fold, as lcv_slot_wait_fold does for a slot that was; lcv_slot_wait hands
+ * out such a slot's verdicts and reasons as for any staged batch.  lcv_debug_fold_stores (test hook) runs the
+ * kernel alone on caller-supplied records, verdicts, store rows and per-store values: no validation, no table.
+ * Out of scope, refused or absent: a fold of a resident table batch (lcv_batch_upload_stores), a sharded fold,
+ * lcv.serving.validate_stream does not fold, and lcv.store.sync_light_client_updates does not (its rows are one
+ * logical store at successive times, so their fold states chain). */
 #define LCV_RANK_BYTES 32
 #define LCV_FOLD_MAX_ROWS 65536
 typedef struct lcv_fold_state {
@@ -232,6 +256,19 @@ int lcv_slot_wait_fold(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out,
                        lcv_fold_result* out);
 int lcv_debug_fold(lcv_ctx* ctx, const uint8_t* rank /* n x 32 */, const uint8_t* verdict, uint64_t n,
                    uint64_t store_finalized_slot, int next_known, const lcv_fold_state* in, lcv_fold_result* out);
+int lcv_validate_stores_fold(lcv_ctx* ctx, const lcv_update_batch* batch, const uint32_t* store_index,
+                             uint64_t current_slot, const uint8_t* genesis_validators_root,
+                             const lcv_fold_state* in /* nstore, indexed by store row */, uint8_t* verdict_out,
+                             uint8_t* reason_out, lcv_fold_result* out /* nstore, entries of present stores written */);
+int lcv_validate_stores_async_fold(lcv_ctx* ctx, const lcv_update_batch* batch, const uint32_t* store_index,
+                                   uint64_t current_slot, const uint8_t* genesis_validators_root,
+                                   const lcv_fold_state* in, int slot);
+int lcv_slot_wait_stores_fold(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint8_t* reason_out,
+                              lcv_fold_result* out /* nstore */);
+int lcv_debug_fold_stores(lcv_ctx* ctx, const uint8_t* rank /* n x 32 */, const uint8_t* verdict,
+                          const uint32_t* store_index, uint64_t n, const uint64_t* store_finalized_slot /* nstore */,
+                          const uint8_t* next_known /* nstore */, uint64_t nstore, const lcv_fold_state* in,
+                          lcv_fold_result* out);
 /* device-resident batches: upload once, validate many times (timed region excludes the upload) */
 int lcv_batch_upload(lcv_ctx* ctx, const lcv_update_batch* batch, lcv_dbatch** out);
 /* the same with the batch's store_index column (n entries): a table batch, see the store table above */

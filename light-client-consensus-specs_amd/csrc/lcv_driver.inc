@@ -6,6 +6,7 @@
 // and the LCV_HD qualifier for functor call operators.
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <thread>
 #include <vector>
@@ -61,7 +62,19 @@ struct HostSlot {
   uint64_t out_n = 0;
   bool staged = false;     // out holds the slot's last batch (lcv_slot_wait reads it)
   bool folded = false;     // ... and, after its 2 out_n bytes, that batch's fold result (lcv_slot_wait_fold)
+  // ... or (lcv_validate_stores_async_fold) one 128-byte result per store present, for the store rows seg_store
+  bool seg_folded = false;
+  std::vector<uint32_t> seg_store;
   lcv_dbatch db;
+};
+
+// the rows of a store-table batch grouped by store (fold_segments): the distinct stores present, ascending; each
+// one's rows in ascending order; the present stores' fold states, gathered.  `key` is the grouping's scratch
+struct FoldSegs {
+  std::vector<uint64_t> key;
+  std::vector<uint32_t> store, off, row;
+  std::vector<FoldState> in;
+  uint32_t nseg = 0;
 };
 
 struct lcv_ctx {
@@ -89,6 +102,11 @@ struct lcv_ctx {
   size_t work_cap[LCV_SLOTS] = {}, work_pool_cap[LCV_SLOTS] = {};
   Work Wslot[LCV_SLOTS];
   Work W;  // the active slot's work space
+  // the per-store results of a segmented fold (lcv_validate_stores_fold), 128 bytes per store present: an
+  // allocation of its own per work-space slot, made by the slot's first segmented fold and grown on demand
+  void* seg_mem[LCV_SLOTS] = {};
+  size_t seg_cap[LCV_SLOTS] = {};
+  FoldSegs segs;  // the grouping of the call in progress (staged before the call returns)
   float stage_ms[ST_COUNT];
   void* sop_mem = nullptr;   // device copies of the SOP pairing programs (tools/gen_sop.py)
   SopView sop_lines, sop_acc, sop_fexp, sop_h2c, sop_miller;
@@ -584,8 +602,10 @@ void lcv_destroy(lcv_ctx* ctx) {
   for (CommitteeBufs* cb : {&ctx->store, &ctx->adhoc, &ctx->table}) {
     if (cb->raw) { be_free(ctx, cb->raw); be_free(ctx, cb->pts); be_free(ctx, cb->sum_all); be_free(ctx, cb->badmask); be_free(ctx, cb->key_status); }
   }
-  for (int k = 0; k < LCV_SLOTS; ++k)
+  for (int k = 0; k < LCV_SLOTS; ++k) {
     if (ctx->work_mem[k]) be_free(ctx, ctx->work_mem[k]);
+    if (ctx->seg_mem[k]) be_free(ctx, ctx->seg_mem[k]);
+  }
   if (ctx->sop_mem) be_free(ctx, ctx->sop_mem);
   if (ctx->comm_buf) be_free(ctx, ctx->comm_buf);
   for (void* p : ctx->comm_retired) be_free(ctx, p);
@@ -621,8 +641,10 @@ int lcv_set_store(lcv_ctx* ctx, uint64_t finalized_slot, const uint8_t* cur, con
 }  // extern "C"
 
 // the 13 columns of a packed batch, and the per-update store-table rows of lcv_validate_updates_stores (column
-// 13: empty otherwise), each at a 256-byte aligned offset of one device allocation
-enum { BATCH_COLS = 14 };
+// 13: empty otherwise), each at a 256-byte aligned offset of one device allocation.  Columns 14-17 (a segmented
+// fold, lcv_validate_stores_fold: empty otherwise) are the grouping of the rows by store and the present stores'
+// fold states (FoldSegs: store, off, row, in), which so travel with the batch in its one copy
+enum { BATCH_COLS = 18 };
 struct BatchCols {
   const void* src[BATCH_COLS];
   size_t bytes[BATCH_COLS], off[BATCH_COLS];
@@ -630,16 +652,19 @@ struct BatchCols {
 };
 
 static int batch_cols(lcv_ctx* ctx, const lcv_update_batch* hb, BatchCols& c, const char* who,
-                      const uint32_t* store_index = nullptr) {
-  const size_t n = hb->n, np = hb->npool;
+                      const uint32_t* store_index = nullptr, const FoldSegs* segs = nullptr) {
+  const size_t n = hb->n, np = hb->npool, ng = segs ? segs->nseg : 0;
   if (n == 0 || np == 0 || n > 0xffffffffull || np > 0xffffffffull)
     return fail(ctx, LCV_EINVAL, std::string(who) + ": need 0 < n, 0 < npool < 2^32");
   const void* src[BATCH_COLS] = {hb->attested.beacon, hb->attested.execution, hb->attested.exec_branch,
                          hb->finalized.beacon, hb->finalized.execution, hb->finalized.exec_branch,
                          hb->nsc_pool, hb->nsc_index, hb->nsc_branch, hb->finality_branch,
-                         hb->sync_bits, hb->sync_signature, hb->signature_slot, store_index};
+                         hb->sync_bits, hb->sync_signature, hb->signature_slot, store_index,
+                         ng ? segs->store.data() : nullptr, ng ? segs->off.data() : nullptr,
+                         ng ? segs->row.data() : nullptr, ng ? segs->in.data() : nullptr};
   const size_t bytes[BATCH_COLS] = {112 * n, 832 * n, 128 * n, 112 * n, 832 * n, 128 * n, (size_t)K_SC * np, 4 * n,
-                                    160 * n, 192 * n, 64 * n, 96 * n, 8 * n, store_index ? 4 * n : 0};
+                                    160 * n, 192 * n, 64 * n, 96 * n, 8 * n, store_index ? 4 * n : 0,
+                                    4 * ng, ng ? 4 * (ng + 1) : 0, ng ? 4 * n : 0, sizeof(FoldState) * ng};
   c.total = 0;
   for (int k = 0; k < BATCH_COLS; ++k) {
     if (!src[k] && k < 13) return fail(ctx, LCV_EINVAL, std::string(who) + ": null column");
@@ -730,7 +755,9 @@ static BatchDev chunk_view(const BatchDev& B, size_t base, uint32_t n) {
 // out_host: verdict/reason to host memory; out_dev: verdicts to a device buffer
 static int host_alloc_grow(lcv_ctx* ctx, uint8_t** p, size_t* cap, size_t bytes);
 // a fold request of the _fold entries: the state going in and (synchronous form) where the result goes
-struct FoldReq { FoldState in; lcv_fold_result* out; };
+// segs (lcv_validate_stores_fold): a segmented fold of a store-table batch — `in` is unused, `out` is indexed by
+// store row, and seg_dev points at the grouping's columns in the batch's device copy (seg_bind)
+struct FoldReq { FoldState in; lcv_fold_result* out; const FoldSegs* segs = nullptr; FoldSegDev seg_dev = {}; };
 static_assert(sizeof(lcv_fold_state) == sizeof(FoldState) && sizeof(lcv_fold_result) == sizeof(FoldResult) &&
               sizeof(FoldResult) <= FOLD_RESULT_BYTES, "lcv.h's fold structs are lcv_fold.hpp's");
 static int fold_state_in(lcv_ctx* ctx, const char* who, const lcv_fold_state* in, FoldState& s) {
@@ -747,11 +774,44 @@ static int fold_stage(lcv_ctx* ctx, const FoldState& in, uint64_t store_fin_slot
   be_stage_end(ctx, ST_FOLD);
   return LCV_OK;
 }
+// the segmented fold's device side.  seg_bind: the grouping's columns of a staged batch (batch_cols 14-17) in its
+// device copy m.  ensure_fold_seg: the slot's result buffer (be_free waits for the streams).  fold_seg_stage:
+// F_fold_seg, one team per store present, where fold_stage would run F_fold
+static void seg_bind(FoldReq& f, uint8_t* m, const BatchCols& c) {
+  f.seg_dev.seg_store = (const uint32_t*)(m + c.off[14]);
+  f.seg_dev.seg_off = (const uint32_t*)(m + c.off[15]);
+  f.seg_dev.seg_row = (const uint32_t*)(m + c.off[16]);
+  f.seg_dev.in = m + c.off[17];
+}
+static int ensure_fold_seg(lcv_ctx* ctx, int slot, size_t nseg) {
+  if (nseg <= ctx->seg_cap[slot] && ctx->seg_mem[slot]) return LCV_OK;
+  size_t cap = 2 * ctx->seg_cap[slot] > nseg ? 2 * ctx->seg_cap[slot] : nseg;
+  if (cap < 64) cap = 64;
+  if (ctx->seg_mem[slot]) be_free(ctx, ctx->seg_mem[slot]);
+  ctx->seg_mem[slot] = nullptr;
+  ctx->seg_cap[slot] = 0;
+  LCV_TRY(be_alloc(ctx, &ctx->seg_mem[slot], cap * FOLD_RESULT_BYTES));
+  ctx->seg_cap[slot] = cap;
+  return LCV_OK;
+}
+static int fold_seg_stage(lcv_ctx* ctx, const Work& W, const StoreDev& S, const FoldSegDev& G, uint32_t nseg) {
+  be_stage_begin(ctx, ST_FOLD);
+  LCV_TRY(be_launch_team(ctx, F_fold_seg{W, S, G}, nseg));
+  be_stage_end(ctx, ST_FOLD);
+  return LCV_OK;
+}
+// the results of a segmented fold, as they arrived (128 bytes per store present), to the caller's array indexed
+// by store row: only the present stores' entries are written
+static void fold_seg_scatter(lcv_fold_result* out, const uint8_t* res, const uint32_t* seg_store, size_t nseg) {
+  for (size_t g = 0; g < nseg; ++g) memcpy(&out[seg_store[g]], res + FOLD_RESULT_BYTES * g, sizeof(FoldResult));
+}
 
 static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, const uint8_t* gvr, uint8_t* verdict_host,
                          uint8_t* reason_host, uint8_t* verdict_dev, int slot = -1, const FoldReq* fold = nullptr) {
   if (!ctx || !db || !gvr) return fail(ctx, LCV_EINVAL, "validate: null argument");
-  if (fold && db->B.store_index) return fail(ctx, LCV_EINVAL, "validate: no fold of a store-table batch");
+  const FoldSegs* segs = fold ? fold->segs : nullptr;  // a segmented fold: a table batch, its rows grouped by store
+  if (fold && !segs && db->B.store_index) return fail(ctx, LCV_EINVAL, "validate: no fold of a store-table batch");
+  if (segs && !db->B.store_index) return fail(ctx, LCV_EINVAL, "validate: a segmented fold needs a store-table batch");
   if (fold && (db->n > LCV_FOLD_MAX_ROWS || db->n > ctx->chunk))
     return fail(ctx, LCV_EINVAL, "validate: a fold takes at most 65536 updates (one chunk) per call");
   // table: a batch that carries its store_index has every update validated against its own row of the store
@@ -773,10 +833,17 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
   const size_t cap = n < ctx->chunk ? n : ctx->chunk;
   be_set_slot(ctx, async ? slot : 0);
   int rc = ensure_work(ctx, cap, db->npool, async ? slot : 0);
+  if (rc == LCV_OK && segs) rc = ensure_fold_seg(ctx, async ? slot : 0, segs->nseg);
   if (rc != LCV_OK) {
     be_set_slot(ctx, 0);
     return rc;
   }
+  FoldSegDev seg_dev = {};
+  if (segs) {
+    seg_dev = fold->seg_dev;
+    seg_dev.out = (uint8_t*)ctx->seg_mem[async ? slot : 0];
+  }
+  const size_t fold_bytes = segs ? (size_t)FOLD_RESULT_BYTES * segs->nseg : (size_t)FOLD_RESULT_BYTES;
   Params P;
   P.cfg = ctx->cfg;
   P.current_slot = current_slot;
@@ -849,15 +916,18 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
       }
       // the fold follows the verdicts of the whole batch (one chunk) on the main stream: after F_verdict in
       // stream order on both engines, after every slice has joined under a pipeline
-      if (fold) LCV_TRY(fold_stage(ctx, fold->in, P.store_fin_slot, P.next_known, m));
+      // (a segmented fold: one team per store present, each against its own row of the table)
+      if (segs) LCV_TRY(fold_seg_stage(ctx, ctx->W, ctx->table_dev, seg_dev, segs->nseg));
+      else if (fold) LCV_TRY(fold_stage(ctx, fold->in, P.store_fin_slot, P.next_known, m));
       if (!async && n <= cap && (verdict_host || reason_host || fold)) {
         // one chunk: both arrays (and a fold's result) into pinned memory without a wait each, handed out after
         // the sync below
         HostSlot& h = ctx->hsync;
-        LCV_TRY(host_alloc_grow(ctx, &h.out, &h.out_cap, 2 * (size_t)m + FOLD_RESULT_BYTES));
+        LCV_TRY(host_alloc_grow(ctx, &h.out, &h.out_cap, 2 * (size_t)m + fold_bytes));
         LCV_TRY(be_d2h(ctx, h.out, ctx->W.verdict, m));
         LCV_TRY(be_d2h(ctx, h.out + m, ctx->W.reason, m));
-        if (fold) LCV_TRY(be_d2h(ctx, h.out + 2 * (size_t)m, ctx->W.fold_out, sizeof(FoldResult)));
+        if (segs) LCV_TRY(be_d2h(ctx, h.out + 2 * (size_t)m, seg_dev.out, fold_bytes));
+        else if (fold) LCV_TRY(be_d2h(ctx, h.out + 2 * (size_t)m, ctx->W.fold_out, sizeof(FoldResult)));
         pinned_out = true;
       } else {
         if (verdict_host) LCV_TRY(be_d2h(ctx, verdict_host + base, ctx->W.verdict, m));
@@ -870,7 +940,8 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
     if (pinned_out) {
       if (verdict_host) memcpy(verdict_host, ctx->hsync.out, n);
       if (reason_host) memcpy(reason_host, ctx->hsync.out + n, n);
-      if (fold && fold->out) memcpy(fold->out, ctx->hsync.out + 2 * n, sizeof(FoldResult));
+      if (segs && fold->out) fold_seg_scatter(fold->out, ctx->hsync.out + 2 * n, segs->store.data(), segs->nseg);
+      else if (fold && fold->out) memcpy(fold->out, ctx->hsync.out + 2 * n, sizeof(FoldResult));
     }
     be_collect_timings(ctx);
     return LCV_OK;
@@ -880,6 +951,7 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
     ctx->marks_off = true;  // nothing collects an asynchronous batch's stage marks
     ctx->hslot[slot].staged = false;
     ctx->hslot[slot].folded = false;
+    ctx->hslot[slot].seg_folded = false;
   }
   rc = body();
   ctx->marks_off = marks_were_off;
@@ -957,15 +1029,17 @@ static int store_index_check(lcv_ctx* ctx, const char* who, const uint32_t* stor
 // store_index null: against the context's store (lcv_validate_async); else row by row against the store table
 // (lcv_validate_stores_async), the 14th column staged with the others
 static int validate_async_host(lcv_ctx* ctx, const char* who, const lcv_update_batch* hb, const uint32_t* store_index,
-                               uint64_t current_slot, const uint8_t* gvr, int slot, const FoldReq* fold = nullptr) {
-  if (store_index) LCV_TRY(store_index_check(ctx, who, store_index, hb->n));  // before the DMA
+                               uint64_t current_slot, const uint8_t* gvr, int slot, FoldReq* fold = nullptr) {
+  const FoldSegs* segs = fold ? fold->segs : nullptr;  // (a segmented fold's grouping has checked every index)
+  if (store_index && !segs) LCV_TRY(store_index_check(ctx, who, store_index, hb->n));  // before the DMA
   BatchCols c;
-  LCV_TRY(batch_cols(ctx, hb, c, who, store_index));
+  LCV_TRY(batch_cols(ctx, hb, c, who, store_index, segs));
   HostSlot& h = ctx->hslot[slot];
   be_set_slot(ctx, slot);
   // the staging buffer is reused only after the slot's previous batch has left it
   int rc = be_wait_event(ctx, EV_H2D);
-  const size_t out_bytes = 2 * c.n + FOLD_RESULT_BYTES;  // verdicts, reasons, a fold's result
+  // verdicts, reasons, a fold's result (a segmented fold's: one per store present)
+  const size_t out_bytes = 2 * c.n + (size_t)FOLD_RESULT_BYTES * (segs ? segs->nseg : 1);
   if (rc == LCV_OK && (c.total > h.pinned_cap || out_bytes > h.out_cap)) rc = be_sync_slot(ctx);
   if (rc == LCV_OK) rc = host_alloc_grow(ctx, &h.pinned, &h.pinned_cap, c.total);
   if (rc == LCV_OK) rc = host_alloc_grow(ctx, &h.out, &h.out_cap, out_bytes);
@@ -987,17 +1061,28 @@ static int validate_async_host(lcv_ctx* ctx, const char* who, const lcv_update_b
   be_set_slot(ctx, 0);
   if (rc != LCV_OK) return rc;
   bind_batch(&h.db, (uint8_t*)h.dev, c);
+  if (segs) seg_bind(*fold, (uint8_t*)h.dev, c);
   LCV_TRY(validate_impl(ctx, &h.db, current_slot, gvr, nullptr, nullptr, nullptr, slot, fold));
   be_set_slot(ctx, slot);
   const Work& W = ctx->Wslot[slot];
   rc = be_d2h(ctx, h.out, W.verdict, c.n);
   if (rc == LCV_OK) rc = be_d2h(ctx, h.out + c.n, W.reason, c.n);
-  if (rc == LCV_OK && fold) rc = be_d2h(ctx, h.out + 2 * c.n, W.fold_out, sizeof(FoldResult));
+  if (rc == LCV_OK && segs) rc = be_d2h(ctx, h.out + 2 * c.n, ctx->seg_mem[slot], (size_t)FOLD_RESULT_BYTES * segs->nseg);
+  else if (rc == LCV_OK && fold) rc = be_d2h(ctx, h.out + 2 * c.n, W.fold_out, sizeof(FoldResult));
   be_set_slot(ctx, 0);
   if (rc != LCV_OK) return rc;
   h.out_n = c.n;
   h.staged = true;
-  h.folded = fold != nullptr;
+  h.folded = fold != nullptr && !segs;
+  h.seg_folded = segs != nullptr;
+  if (segs) {
+    try {
+      h.seg_store = segs->store;
+    } catch (...) {  // an extern "C" entry point must not let an exception out
+      h.staged = h.seg_folded = false;
+      return fail(ctx, LCV_ENOMEM, std::string(who) + ": out of host memory");
+    }
+  }
   return LCV_OK;
 }
 
@@ -1045,14 +1130,14 @@ int lcv_slot_wait(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint
 // host batch in, verdicts out, synchronous: against the context's store (store_index null) or, row by row,
 // against the store table
 static int validate_host(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index, uint64_t current_slot,
-                         const uint8_t* gvr, uint8_t* verdict_out, uint8_t* reason_out, const FoldReq* fold = nullptr) {
+                         const uint8_t* gvr, uint8_t* verdict_out, uint8_t* reason_out, FoldReq* fold = nullptr) {
   const bool table = store_index != nullptr;
   if (ctx && hb && gvr && (table ? ctx->table_set : ctx->store_set) && hb->n > 0 && hb->n <= ctx->chunk) {
     // one chunk (the reference's per-update call shape among them): the columns go through a reused pinned
     // staging buffer and ONE DMA into a reused device copy (lcv_validate_async's path, waited for here)
     // instead of a device allocation, one copy per column and a free per call
     BatchCols c;
-    LCV_TRY(batch_cols(ctx, hb, c, "lcv_validate_updates", store_index));
+    LCV_TRY(batch_cols(ctx, hb, c, "lcv_validate_updates", store_index, fold ? fold->segs : nullptr));
     HostSlot& h = ctx->hsync;
     be_set_slot(ctx, 0);
     int rc = host_alloc_grow(ctx, &h.pinned, &h.pinned_cap, c.total);
@@ -1068,6 +1153,7 @@ static int validate_host(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_
     be_set_slot(ctx, 0);
     LCV_TRY(be_h2d(ctx, h.dev, h.pinned, c.total));
     bind_batch(&h.db, (uint8_t*)h.dev, c);
+    if (fold && fold->segs) seg_bind(*fold, (uint8_t*)h.dev, c);
     return validate_impl(ctx, &h.db, current_slot, gvr, verdict_out, reason_out, nullptr, -1, fold);  // returns synced
   }
   if (fold) return fail(ctx, LCV_EINVAL, "lcv_validate_fold: null argument, no store set, or not 0 < n <= one chunk");
@@ -1289,6 +1375,145 @@ int lcv_validate_updates_stores(lcv_ctx* ctx, const lcv_update_batch* hb, const 
   if (hb->n == 0 || hb->n > 0xffffffffull) return fail(ctx, LCV_EINVAL, "lcv_validate_updates_stores: need 0 < n < 2^32");
   LCV_TRY(store_index_check(ctx, "lcv_validate_updates_stores", store_index, hb->n));
   return validate_host(ctx, hb, store_index, current_slot, gvr, verdict_out, reason_out);
+}
+
+// ---- the fold of a store-table batch, store by store (include/lcv.h, "The segmented fold"; lcv_fold.hpp)
+// store_index_check's pass, grouping as it goes: every index against nstore (naming the first offending row), and
+// the rows keyed by (store, row).  Sorting the keys is the stable grouping — skipped when the rows already come
+// store by store — so the cost is O(n log n) whatever the table's size, and nothing here is sized by nstore.
+// Then the present stores' fold states are checked and gathered (in: indexed by store row).
+static int fold_segments(lcv_ctx* ctx, const char* who, const uint32_t* store_index, uint64_t n, uint64_t nstore,
+                         const lcv_fold_state* in, FoldSegs& g) {
+  try {
+    g.key.resize(n);
+    bool sorted = true;
+    for (uint64_t i = 0; i < n; ++i) {
+      if (store_index[i] >= nstore)
+        return fail(ctx, LCV_EINVAL, std::string(who) + ": store_index[" + std::to_string(i) + "] = " +
+                                         std::to_string(store_index[i]) + " is not a store row (nstore " +
+                                         std::to_string(nstore) + ")");
+      g.key[i] = ((uint64_t)store_index[i] << 32) | i;
+      if (i && g.key[i] < g.key[i - 1]) sorted = false;
+    }
+    if (!sorted) std::sort(g.key.begin(), g.key.end());
+    g.store.clear();
+    g.off.clear();
+    g.in.clear();
+    g.row.resize(n);
+    for (uint64_t j = 0; j < n; ++j) {
+      const uint32_t s = (uint32_t)(g.key[j] >> 32);
+      if (j == 0 || s != g.store.back()) {
+        g.store.push_back(s);
+        g.off.push_back((uint32_t)j);
+      }
+      g.row[j] = (uint32_t)g.key[j];
+    }
+    g.off.push_back((uint32_t)n);
+    g.nseg = (uint32_t)g.store.size();
+    g.in.resize(g.nseg);
+  } catch (...) {  // an extern "C" entry point must not let an exception out
+    return fail(ctx, LCV_ENOMEM, std::string(who) + ": out of host memory");
+  }
+  for (uint32_t k = 0; k < g.nseg; ++k)
+    LCV_TRY(fold_state_in(ctx, (std::string(who) + ": in[" + std::to_string(g.store[k]) + "]").c_str(), &in[g.store[k]], g.in[k]));
+  return LCV_OK;
+}
+
+int lcv_validate_stores_fold(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index, uint64_t current_slot,
+                             const uint8_t* gvr, const lcv_fold_state* in, uint8_t* verdict_out, uint8_t* reason_out,
+                             lcv_fold_result* out) {
+  if (!ctx || !hb || !store_index || !gvr || !in || !out) return fail(ctx, LCV_EINVAL, "lcv_validate_stores_fold: null argument");
+  if (hb->n == 0 || hb->n > LCV_FOLD_MAX_ROWS || hb->n > ctx->chunk)
+    return fail(ctx, LCV_EINVAL, "lcv_validate_stores_fold: need 0 < n <= 65536 (one chunk): cut larger batches and carry each store's `next` forward");
+  if (!ctx->table_set) return fail(ctx, LCV_ESTATE, "lcv_validate_stores_fold: lcv_set_store_table has not been called");
+  LCV_TRY(fold_segments(ctx, "lcv_validate_stores_fold", store_index, hb->n, ctx->table_dev.nstore, in, ctx->segs));
+  FoldReq req;
+  req.in = FoldState{};
+  req.out = out;
+  req.segs = &ctx->segs;
+  return validate_host(ctx, hb, store_index, current_slot, gvr, verdict_out, reason_out, &req);
+}
+
+int lcv_validate_stores_async_fold(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index,
+                                   uint64_t current_slot, const uint8_t* gvr, const lcv_fold_state* in, int slot) {
+  if (!ctx || !hb || !store_index || !gvr || !in || slot < 0 || slot >= LCV_SLOTS)
+    return fail(ctx, LCV_EINVAL, "lcv_validate_stores_async_fold: null argument or slot not in 0..7");
+  if (hb->n == 0 || hb->n > LCV_FOLD_MAX_ROWS || hb->n > ctx->chunk)
+    return fail(ctx, LCV_EINVAL, "lcv_validate_stores_async_fold: need 0 < n <= 65536 (one chunk) per call");
+  if (!ctx->table_set) return fail(ctx, LCV_ESTATE, "lcv_validate_stores_async_fold: lcv_set_store_table has not been called");
+  LCV_TRY(fold_segments(ctx, "lcv_validate_stores_async_fold", store_index, hb->n, ctx->table_dev.nstore, in, ctx->segs));
+  FoldReq req;
+  req.in = FoldState{};
+  req.out = nullptr;  // the results wait in the slot's pinned area for lcv_slot_wait_stores_fold
+  req.segs = &ctx->segs;
+  return validate_async_host(ctx, "lcv_validate_stores_async_fold", hb, store_index, current_slot, gvr, slot, &req);
+}
+
+int lcv_slot_wait_stores_fold(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint8_t* reason_out,
+                              lcv_fold_result* out) {
+  if (!ctx || !out || slot < 0 || slot >= LCV_SLOTS)
+    return fail(ctx, LCV_EINVAL, "lcv_slot_wait_stores_fold: null argument or slot not in 0..7");
+  HostSlot& h = ctx->hslot[slot];
+  if (!h.staged || !h.seg_folded)
+    return fail(ctx, LCV_ESTATE, "lcv_slot_wait_stores_fold: the slot's batch was not enqueued by lcv_validate_stores_async_fold");
+  LCV_TRY(lcv_slot_wait(ctx, slot, n, verdict_out, reason_out));  // waits for the slot
+  fold_seg_scatter(out, h.out + 2 * h.out_n, h.seg_store.data(), h.seg_store.size());
+  return LCV_OK;
+}
+
+// test hook: F_fold_seg alone on caller-supplied rank records, verdicts, store rows and per-store values (no
+// validation, no table: the two store columns the kernel reads are built here, next_known[s] != 0 as a known row)
+int lcv_debug_fold_stores(lcv_ctx* ctx, const uint8_t* rank, const uint8_t* verdict, const uint32_t* store_index, uint64_t n,
+                          const uint64_t* store_finalized_slot, const uint8_t* next_known, uint64_t nstore,
+                          const lcv_fold_state* in, lcv_fold_result* out) {
+  if (!ctx || !rank || !verdict || !store_index || !store_finalized_slot || !next_known || !in || !out)
+    return fail(ctx, LCV_EINVAL, "lcv_debug_fold_stores: null argument");
+  if (n == 0 || n > LCV_FOLD_MAX_ROWS) return fail(ctx, LCV_EINVAL, "lcv_debug_fold_stores: need 0 < n <= 65536");
+  if (nstore == 0 || nstore > 0xffffffffull) return fail(ctx, LCV_EINVAL, "lcv_debug_fold_stores: need 0 < nstore < 2^32");
+  FoldSegs& g = ctx->segs;
+  LCV_TRY(fold_segments(ctx, "lcv_debug_fold_stores", store_index, n, nstore, in, g));
+  std::vector<uint32_t> next;
+  std::vector<uint8_t> res;
+  try {
+    next.resize(nstore);
+    res.resize((size_t)FOLD_RESULT_BYTES * g.nseg);
+  } catch (...) {
+    return fail(ctx, LCV_ENOMEM, "lcv_debug_fold_stores: out of host memory");
+  }
+  for (uint64_t s = 0; s < nstore; ++s) next[s] = next_known[s] ? 0u : (uint32_t)STORE_NEXT_UNKNOWN;
+  const size_t ng = g.nseg;
+  const void* src[8] = {rank, verdict, store_finalized_slot, next.data(), g.store.data(), g.off.data(), g.row.data(), g.in.data()};
+  const size_t bytes[8] = {rank_index((size_t)n), (size_t)n, 8 * (size_t)nstore, 4 * (size_t)nstore, 4 * ng, 4 * (ng + 1),
+                           4 * (size_t)n, sizeof(FoldState) * ng};
+  size_t off[9], total = 0;
+  for (int k = 0; k < 9; ++k) {
+    off[k] = total;
+    total += ((k < 8 ? bytes[k] : (size_t)FOLD_RESULT_BYTES * ng) + 255) & ~(size_t)255;
+  }
+  void* mem = nullptr;
+  be_set_slot(ctx, 0);
+  LCV_TRY(be_alloc(ctx, &mem, total));
+  uint8_t* m = (uint8_t*)mem;
+  Work W = Work{};
+  W.cap = (uint32_t)n;
+  W.rank = m + off[0];
+  W.verdict = m + off[1];
+  const StoreDev S = {(const uint64_t*)(m + off[2]), nullptr, (const uint32_t*)(m + off[3]), (uint32_t)nstore};
+  const FoldSegDev G = {(const uint32_t*)(m + off[4]), (const uint32_t*)(m + off[5]), (const uint32_t*)(m + off[6]),
+                        m + off[7], m + off[8]};
+  be_reset_timings(ctx);
+  auto body = [&]() -> int {
+    for (int k = 0; k < 8; ++k) LCV_TRY(be_h2d(ctx, m + off[k], src[k], bytes[k]));
+    LCV_TRY(fold_seg_stage(ctx, W, S, G, g.nseg));
+    LCV_TRY(be_d2h(ctx, res.data(), G.out, res.size()));
+    return be_sync(ctx);
+  };
+  const int rc = body();
+  be_free(ctx, mem);  // (waits for the streams)
+  if (rc != LCV_OK) return rc;
+  be_collect_timings(ctx);
+  fold_seg_scatter(out, res.data(), g.store.data(), g.nseg);
+  return LCV_OK;
 }
 
 // The communication buffer never blocks a collective call: lcv_comm_init sizes it for every slot's largest

@@ -1,6 +1,7 @@
-// lcv_fold.hpp — process_light_client_update after validation (sync-protocol.md:514-553) over a batch, for one
-// store: a rank record per update (item_rank, one lane per update) and the fold of records and verdicts into the
-// next store state (item_fold_team, one 64-lane team for the whole batch).  Semantics: include/lcv.h.
+// lcv_fold.hpp — process_light_client_update after validation (sync-protocol.md:514-553) over a batch: a rank
+// record per update (item_rank, one lane per update) and the fold of records and verdicts into the next store
+// state — for one store (item_fold_team, one 64-lane team for the whole batch) or store by store over a
+// store-table batch (item_fold_seg_team, one team per store present).  Semantics: include/lcv.h.
 //   is_better_update (:260-311) is a lexicographic order on (key0, -attested_slot, -signature_slot), so "the first
 //   best update" is the first arg-max of the rank, and the per-row loop becomes a scan up to the first row that
 //   applies (:545-553).
@@ -99,8 +100,9 @@ LCV_FN void item_rank(uint32_t i, const BatchDev& B, const Params& P, const Work
   rank_st(W.rank, i, r);
 }
 
-// The fold: one team of 64 lanes for the whole batch, lane l owning the contiguous stripe of ceil(n / 64) rows
-// [l L, (l + 1) L).  A lane never reads, in a round, an LDS word another lane writes in that round.
+// The fold: one team of 64 lanes for the rows of one store (the whole batch, or a segment of a store-table batch),
+// lane l owning the contiguous stripe of ceil(n / 64) positions [l L, (l + 1) L).  A lane never reads, in a round,
+// an LDS word another lane writes in that round.
 //   round 0  every lane: the first row of its stripe that applies, and the max participation over the stripe's
 //            valid rows up to that row
 //   round 1  lane 0: the 64 summaries in lane order -> t, the running max each lane starts from, lanes past t dead
@@ -113,21 +115,31 @@ enum : uint32_t {
   FOLD_O_FIRST = 0, FOLD_O_MAX = 64, FOLD_O_PREFIX = 128, FOLD_O_T = 192, FOLD_O_RUN = 193,
   FOLD_O_BEST = 256, FOLD_O_OPT = 320, FOLD_O_CNT = 384, FOLD_LDS = 448,
 };
+// The rows a fold walks, as a compile-time map from position j of the walk to a row of W.rank / W.verdict: every
+// row of the batch in order (F_fold), or one store's rows of a store-table batch (F_fold_seg: a segment, the batch
+// rows seg_row[0 .. len) in ascending order).  Positions are what the rounds compare and keep in LDS; round 3
+// turns the positions it reports into batch rows.
+struct FoldRowsAll { LCV_HD uint32_t operator()(uint32_t j) const { return j; } };
+struct FoldRowsSeg { const uint32_t* row; LCV_HD uint32_t operator()(uint32_t j) const { return row[j]; } };
 // rows [i0, i0 + FOLD_BLK) of a stripe ending at `end` (i0 < end): records and verdicts loaded together, before any
 // is looked at, so a lane has FOLD_BLK rows' loads in flight (a lane's rows are 32 bytes apart, the lanes' a stripe
 // apart: the loads do not coalesce, their latency is what the walk costs).  Rows past `end` read row end - 1 and
 // count as invalid.
 enum : uint32_t { FOLD_BLK = 8 };
-LCV_FN void fold_ld_block(RankRec x[FOLD_BLK], uint8_t ok[FOLD_BLK], const Work& W, uint32_t i0, uint32_t end) {
+template <class Rows>
+LCV_FN void fold_ld_block(RankRec x[FOLD_BLK], uint8_t ok[FOLD_BLK], const Work& W, const Rows& rows, uint32_t i0,
+                          uint32_t end) {
   LCV_UNROLL for (uint32_t k = 0; k < FOLD_BLK; ++k) {
     const bool in = i0 + k < end;
-    const uint32_t i = in ? i0 + k : end - 1;
+    const uint32_t i = rows(in ? i0 + k : end - 1);
     ok[k] = in ? W.verdict[i] : (uint8_t)0;
     rank_ld(x[k], W.rank, i);
   }
 }
-LCV_FN void item_fold_team(uint32_t lane, uint32_t r, uint32_t* lds, const Work& W, const FoldState& in,
-                           uint64_t store_fin_slot, uint32_t next_known, uint32_t n) {
+// n rows (positions 0 .. n - 1 of `rows`), the result to `out` (FOLD_RESULT_BYTES, 16-byte aligned)
+template <class Rows>
+LCV_FN void item_fold_rows(uint32_t lane, uint32_t r, uint32_t* lds, const Work& W, const Rows& rows, const FoldState& in,
+                           uint64_t store_fin_slot, uint32_t next_known, uint32_t n, uint8_t* out) {
   const uint32_t L = (n + FOLD_TEAM - 1) / FOLD_TEAM;
   const uint32_t lo = lane * L < n ? lane * L : n;
   const uint32_t hi = n - lo < L ? n : lo + L;
@@ -136,7 +148,7 @@ LCV_FN void item_fold_team(uint32_t lane, uint32_t r, uint32_t* lds, const Work&
     LCV_NOUNROLL for (uint32_t i0 = lo; i0 < hi && first == FOLD_NONE; i0 += FOLD_BLK) {
       RankRec x[FOLD_BLK];
       uint8_t ok[FOLD_BLK];
-      fold_ld_block(x, ok, W, i0, hi);
+      fold_ld_block(x, ok, W, rows, i0, hi);
       LCV_UNROLL for (uint32_t k = 0; k < FOLD_BLK; ++k) {
         if (first != FOLD_NONE || !ok[k]) continue;
         const uint32_t ni = x[k].key0 & RANK_N_MASK;
@@ -174,7 +186,7 @@ LCV_FN void item_fold_team(uint32_t lane, uint32_t r, uint32_t* lds, const Work&
       LCV_NOUNROLL for (uint32_t i0 = lo; i0 < end; i0 += FOLD_BLK) {
         RankRec x[FOLD_BLK];
         uint8_t ok[FOLD_BLK];
-        fold_ld_block(x, ok, W, i0, end);
+        fold_ld_block(x, ok, W, rows, i0, end);
         LCV_UNROLL for (uint32_t k = 0; k < FOLD_BLK; ++k) {
           if (!ok[k]) continue;
           const uint32_t ni = x[k].key0 & RANK_N_MASK;
@@ -211,18 +223,20 @@ LCV_FN void item_fold_team(uint32_t lane, uint32_t r, uint32_t* lds, const Work&
       const uint32_t o = lds[FOLD_O_OPT + l], b = lds[FOLD_O_BEST + l];
       RankRec x;
       if (o != FOLD_NONE) {
-        rank_ld(x, W.rank, o);
+        const uint32_t row = rows(o);
+        rank_ld(x, W.rank, row);
         if (x.att > opt_att) {
           opt_att = x.att;
-          res.optimistic_row = (int64_t)o;
+          res.optimistic_row = (int64_t)row;
         }
       }
       if (b != FOLD_NONE) {
-        rank_ld(x, W.rank, b);
+        const uint32_t row = rows(b);
+        rank_ld(x, W.rank, row);
         if (!has || rank_better(x.key0, x.att, x.sig, b_key, b_att, b_sig)) {
           has = true;
           b_key = x.key0; b_att = x.att; b_sig = x.sig;
-          res.best_row = (int64_t)b;
+          res.best_row = (int64_t)row;
         }
       }
     }
@@ -237,9 +251,49 @@ LCV_FN void item_fold_team(uint32_t lane, uint32_t r, uint32_t* lds, const Work&
     res.next.best_att = has ? b_att : 0;
     res.next.best_sig = has ? b_sig : 0;
     res.rows_consumed = t != FOLD_NONE ? (uint64_t)t + 1 : (uint64_t)n;
-    res.apply_row = t != FOLD_NONE ? (int64_t)t : -1;
-    *(FoldResult*)W.fold_out = res;
+    res.apply_row = t != FOLD_NONE ? (int64_t)rows(t) : -1;
+    *(FoldResult*)out = res;
   }
+}
+// the whole batch as one store's rows (F_fold)
+LCV_FN void item_fold_team(uint32_t lane, uint32_t r, uint32_t* lds, const Work& W, const FoldState& in,
+                           uint64_t store_fin_slot, uint32_t next_known, uint32_t n) {
+  item_fold_rows(lane, r, lds, W, FoldRowsAll{}, in, store_fin_slot, next_known, n, W.fold_out);
+}
+
+// The fold of a store-table batch, store by store (lcv_validate_stores_fold): the host groups the batch's rows by
+// store_index into segments — seg_store[g] the store row, seg_row[seg_off[g] .. seg_off[g + 1]) its batch rows in
+// ascending order — and gathers the present stores' fold states; team g folds segment g against store row
+// seg_store[g] of the table and writes batch row numbers to out + g * FOLD_RESULT_BYTES.
+struct FoldSegDev {
+  const uint32_t* seg_store;  // [nseg] distinct store rows present, ascending
+  const uint32_t* seg_off;    // [nseg + 1]
+  const uint32_t* seg_row;    // [n]
+  const uint8_t* in;          // [nseg][48] FoldState of store seg_store[g] (16-byte aligned)
+  uint8_t* out;               // [nseg][FOLD_RESULT_BYTES]
+};
+LCV_FN void fold_state_ld(FoldState& s, const uint8_t* base, size_t g) {
+  const uint8_t* p = base + sizeof(FoldState) * g;
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint4* q = (const uint4*)p;  // three 16-byte loads
+  const uint4 a = q[0], b = q[1], c = q[2];
+  s.optimistic_slot = (uint64_t)a.x | ((uint64_t)a.y << 32);
+  s.previous_max = (uint64_t)a.z | ((uint64_t)a.w << 32);
+  s.current_max = (uint64_t)b.x | ((uint64_t)b.y << 32);
+  s.has_best = b.z; s.best_key0 = b.w;
+  s.best_att = (uint64_t)c.x | ((uint64_t)c.y << 32);
+  s.best_sig = (uint64_t)c.z | ((uint64_t)c.w << 32);
+#else
+  memcpy(&s, p, sizeof(FoldState));
+#endif
+}
+LCV_FN void item_fold_seg_team(uint32_t g, uint32_t lane, uint32_t r, uint32_t* lds, const Work& W, const StoreDev& S,
+                               const FoldSegDev& G) {
+  const uint32_t s = G.seg_store[g], off = G.seg_off[g], len = G.seg_off[g + 1] - off;
+  FoldState in;
+  fold_state_ld(in, G.in, g);
+  item_fold_rows(lane, r, lds, W, FoldRowsSeg{G.seg_row + off}, in, S.fin_slot[s],
+                 S.next[s] != STORE_NEXT_UNKNOWN ? 1u : 0u, len, G.out + (size_t)FOLD_RESULT_BYTES * g);
 }
 
 }  // namespace lcv

@@ -36,6 +36,15 @@ struct F_fold {
     item_fold_team(lane, r, lds, W, in, store_fin_slot, next_known, n);
   }
 };
+// the fold of a store-table batch (lcv_validate_stores_fold): one team per store present, on that store's rows
+struct F_fold_seg {
+  Work W; StoreDev S; FoldSegDev G;
+  static constexpr uint32_t TEAM = FOLD_TEAM, LDS_WORDS = FOLD_LDS, SHARED_WORDS = 0;
+  LCV_HD uint32_t rounds() const { return FOLD_ROUNDS; }
+  LCV_HD void operator()(uint32_t g, uint32_t lane, uint32_t r, uint32_t* lds, uint32_t*) const {
+    item_fold_seg_team(g, lane, r, lds, W, S, G);
+  }
+};
 struct F_sigroot { BatchDev B; Params P; Work W; LCV_HD void operator()(uint32_t i) const { item_sigroot(i, B, P, W); } };
 struct F_h2c_map { Work W; LCV_HD void operator()(uint32_t t) const { item_h2c_map(t, W); } };
 struct F_sig { BatchDev B; Work W; LCV_HD void operator()(uint32_t i) const { item_sig(i, B, W); } };

@@ -108,6 +108,13 @@ SIGNATURES = {
     "lcv_slot_wait_fold": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, u8p, u8p, C.POINTER(FoldResultC)]),
     "lcv_debug_fold": (C.c_int, [C.c_void_p, u8p, u8p, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(FoldStateC),
                                  C.POINTER(FoldResultC)]),
+    "lcv_validate_stores_fold": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), u32p, C.c_uint64, u8p,
+                                           C.POINTER(FoldStateC), u8p, u8p, C.POINTER(FoldResultC)]),
+    "lcv_validate_stores_async_fold": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), u32p, C.c_uint64, u8p,
+                                                 C.POINTER(FoldStateC), C.c_int]),
+    "lcv_slot_wait_stores_fold": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64, u8p, u8p, C.POINTER(FoldResultC)]),
+    "lcv_debug_fold_stores": (C.c_int, [C.c_void_p, u8p, u8p, u32p, C.c_uint64, u64p, u8p, C.c_uint64,
+                                        C.POINTER(FoldStateC), C.POINTER(FoldResultC)]),
     "lcv_batch_upload": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), C.POINTER(C.c_void_p)]),
     "lcv_batch_upload_stores": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), u32p, C.POINTER(C.c_void_p)]),
     "lcv_batch_free": (None, [C.c_void_p, C.c_void_p]),

@@ -410,6 +410,99 @@ class Verifier:
                                             C.byref(res)), "lcv_debug_fold")
         return FoldResult.from_c(res)
 
+    # ------------------------------------------------------------------ the fold of a store-table batch, per store
+    @staticmethod
+    def _fold_states(states, rows: int = 0):
+        arr = (FoldStateC * max(len(states), rows))()
+        for k, s in enumerate(states):
+            arr[k] = s.to_c()
+        return arr
+
+    @staticmethod
+    def _fold_states_cover(states, present) -> None:
+        if present and present[-1] >= len(states):
+            raise ValueError(f"store_index names store row {present[-1]} but only {len(states)} fold states were given")
+
+    @staticmethod
+    def _fold_results(res, present) -> list:
+        """One FoldResult per store row; None for the stores `present` does not name (their entries are not
+        written by the C entries)."""
+        out = [None] * len(res)
+        for s in present:
+            out[s] = FoldResult.from_c(res[s])
+        return out
+
+    def validate_stores_fold(self, batch: PackedUpdates, store_index, current_slot: int,
+                             genesis_validators_root: bytes, states: Sequence[FoldState]):
+        """validate_stores + the device fold per store (lcv_validate_stores_fold; at most 65,536 rows): update i is
+        validated against store row store_index[i] and folded with that store's other rows, in batch order, from
+        states[store_index[i]] -> (verdicts, reason codes, results).  `states`: one FoldState per store row of the
+        table; `results`: one FoldResult per store row, None for stores without a row in the batch.  The results'
+        apply_row / best_row / optimistic_row are batch rows; row i of store s was consumed iff
+        results[s].apply_row < 0 or i <= results[s].apply_row."""
+        b, keep = batch.to_c()
+        six = self._store_index(batch, store_index)
+        gvr = as_u8(bytes(genesis_validators_root))
+        v = np.zeros(batch.n, np.uint8)
+        r = np.zeros(batch.n, np.uint8)
+        present = np.unique(six).tolist()
+        rows = max(len(states), present[-1] + 1 if present else 0, 1)  # (the C entry names a store_index out of range)
+        st, res = self._fold_states(states, rows), (FoldResultC * rows)()
+        self._check(self.lib.lcv_validate_stores_fold(self.ctx, C.byref(b), ptr(six, C.c_uint32), int(current_slot),
+                                                      ptr(gvr), st, ptr(v), ptr(r), res), "lcv_validate_stores_fold")
+        self._fold_states_cover(states, present)
+        return v.astype(bool), r, self._fold_results(res, present)[:len(states)]
+
+    def validate_stores_async_fold(self, batch: PackedUpdates, store_index, current_slot: int,
+                                   genesis_validators_root: bytes, states: Sequence[FoldState], slot: int) -> None:
+        """validate_stores_async with the fold per store (lcv_validate_stores_async_fold); collect with
+        slot_wait_stores_fold(slot, n, nstore)."""
+        b, keep = batch.to_c()
+        six = self._store_index(batch, store_index)
+        gvr = as_u8(bytes(genesis_validators_root))
+        present = np.unique(six).tolist()
+        self._fold_states_cover(states, present)
+        st = self._fold_states(states)
+        self._check(self.lib.lcv_validate_stores_async_fold(self.ctx, C.byref(b), ptr(six, C.c_uint32), int(current_slot),
+                                                            ptr(gvr), st, int(slot)), "lcv_validate_stores_async_fold")
+        self._seg_present = getattr(self, "_seg_present", {})
+        self._seg_present[int(slot)] = present
+        del keep
+
+    def slot_wait_stores_fold(self, slot: int, n: int, nstore: int):
+        """Wait for the table batch folded on `slot` -> (verdicts, reason codes, results: one FoldResult per store
+        row, None for stores without a row); LcvError (status -4) if the slot's batch was not enqueued by
+        validate_stores_async_fold."""
+        v = np.zeros(n, np.uint8)
+        r = np.zeros(n, np.uint8)
+        res = (FoldResultC * max(1, int(nstore)))()
+        self._check(self.lib.lcv_slot_wait_stores_fold(self.ctx, int(slot), int(n), ptr(v), ptr(r), res),
+                    "lcv_slot_wait_stores_fold")
+        present = getattr(self, "_seg_present", {}).get(int(slot), [])
+        return v.astype(bool), r, self._fold_results(res, present)[:int(nstore)]
+
+    def debug_fold_stores(self, rank: np.ndarray, verdict: np.ndarray, store_index, store_finalized_slot, next_known,
+                          states: Sequence[FoldState], out=None) -> list:
+        """Test hook (lcv_debug_fold_stores): the segmented fold kernel alone on caller-supplied rank records,
+        verdicts and store rows; store s has finalized slot store_finalized_slot[s] and next_known[s].  `out`
+        (optional FoldResultC array, one per store) receives the raw results, so a caller can see which entries
+        were written."""
+        rk = np.ascontiguousarray(rank, RANK_DTYPE)
+        vd = np.ascontiguousarray(verdict, np.uint8)
+        six = np.ascontiguousarray(store_index, np.uint32).reshape(-1)
+        fin = np.ascontiguousarray(store_finalized_slot, np.uint64).reshape(-1)
+        nk = np.ascontiguousarray(next_known, np.uint8).reshape(-1)
+        if rk.ndim != 1 or rk.shape != vd.shape or rk.shape != six.shape:
+            raise ValueError("need one verdict and one store_index per rank record")
+        if not (fin.shape[0] == nk.shape[0] == len(states)) or not len(states):
+            raise ValueError("need one finalized slot, one next_known and one fold state per store")
+        st = self._fold_states(states)
+        res = out if out is not None else (FoldResultC * len(states))()
+        self._check(self.lib.lcv_debug_fold_stores(self.ctx, ptr(rk.view(np.uint8)), ptr(vd), ptr(six, C.c_uint32),
+                                                   rk.shape[0], ptr(fin, C.c_uint64), ptr(nk), fin.shape[0], st, res),
+                    "lcv_debug_fold_stores")
+        return self._fold_results(res, [s for s in np.unique(six).tolist() if s < len(states)])
+
     def event_pool(self) -> int:
         """HIP events held for stage timings (test hook: must stay bounded under asynchronous calls)."""
         n = C.c_uint64()

@@ -32,6 +32,7 @@ containers, or the lightweight defaults below for the finality / optimistic conv
 from __future__ import annotations
 
 import copy
+import hashlib
 from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Any, Optional, Sequence
@@ -41,7 +42,7 @@ import numpy as np
 from . import config
 from . import layout as L
 from . import runtime
-from ._native import FOLD_MAX_ROWS
+from ._native import FOLD_MAX_ROWS, STORE_NEXT_UNKNOWN
 from .device import (FoldState, PackedUpdates, RANK_DTYPE, RANK_FIN, RANK_FIN_SC, RANK_REL_SC, RANK_SUPER, Verifier)
 from .sync_protocol import REASONS, pack_updates, validate_light_client_updates, validate_under_store_keys
 
@@ -286,6 +287,18 @@ def _fold_check_config(v: Verifier, who: str) -> None:
                          f"lcv.config.set_active() (or Verifier.set_config) so both sides agree")
 
 
+def _fold_state_of(store) -> FoldState:
+    """The fold state of a store: its optimistic slot, its maxima, and its best_valid_update's rank (_rank_key)."""
+    state = FoldState(optimistic_slot=_slot(store.optimistic_header),
+                      previous_max_active_participants=int(store.previous_max_active_participants),
+                      current_max_active_participants=int(store.current_max_active_participants))
+    if store.best_valid_update is not None:
+        k = _rank_key(store.best_valid_update)
+        state.has_best, state.best_key0 = True, int(k["key0"])
+        state.best_attested_slot, state.best_signature_slot = int(k["attested_slot"]), int(k["signature_slot"])
+    return state
+
+
 def fold_light_client_updates(store, updates, current_slot: int, genesis_validators_root: bytes,
                               verifier: Optional[Verifier] = None, reasons_out: Optional[list] = None,
                               stats_out: Optional[dict] = None) -> np.ndarray:
@@ -314,13 +327,7 @@ def fold_light_client_updates(store, updates, current_slot: int, genesis_validat
     while start < n:
         segments += 1
         runtime.ensure_store(v, *_validation_key(store))
-        state = FoldState(optimistic_slot=_slot(store.optimistic_header),
-                          previous_max_active_participants=int(store.previous_max_active_participants),
-                          current_max_active_participants=int(store.current_max_active_participants))
-        if store.best_valid_update is not None:
-            k = _rank_key(store.best_valid_update)
-            state.has_best, state.best_key0 = True, int(k["key0"])
-            state.best_attested_slot, state.best_signature_slot = int(k["attested_slot"]), int(k["signature_slot"])
+        state = _fold_state_of(store)
         pos, apply_row, best_row, optimistic_row = start, -1, -1, -1
         while pos < n and apply_row < 0:
             ok, rs, res = v.validate_fold(batch.slice(pos, min(n, pos + chunk)), int(current_slot),
@@ -351,6 +358,130 @@ def fold_light_client_updates(store, updates, current_slot: int, genesis_validat
     if stats_out is not None:
         stats_out["validate_calls"] = calls
         stats_out["segments"] = segments
+    return accepted
+
+
+def _take_rows(batch: PackedUpdates, idx: np.ndarray) -> PackedUpdates:
+    """Rows idx of a PackedUpdates batch (the committee pool is shared)."""
+    if idx.size == batch.n:  # (idx is ascending and without repeats: the whole batch)
+        return batch
+    kw = {f: (getattr(batch, f) if f == "nsc_pool" else np.ascontiguousarray(getattr(batch, f)[idx]))
+          for f in batch.__dataclass_fields__}
+    return PackedUpdates(**kw)
+
+
+def fold_light_client_updates_multi(stores: Sequence, updates, current_slot: int, genesis_validators_root: bytes,
+                                    verifier: Optional[Verifier] = None, reasons_out: Optional[list] = None,
+                                    stats_out: Optional[dict] = None) -> np.ndarray:
+    """`process_light_client_updates` for many stores at once: stores[i] is the store OBJECT update i is for (the
+    same object may repeat; the rows of different stores may interleave in any way).  For every distinct store
+    object S the accept flags, reason codes and final state of S are those of
+    process_light_client_updates(S, [updates[i] for i if stores[i] is S], ...) — validated and folded in one
+    device call per round for all stores together (Verifier.validate_stores_fold), with no per-row Python.
+
+    `updates`: update objects or a PackedUpdates batch (rows a store ends up holding are rebuilt with
+    lcv.layout.unpack_update).  A round takes the rows still pending, in order; builds a store table with one
+    store row per store object that has pending rows (committees shared by content, store rows not: stores with
+    equal validation keys still fold from different states) and each store's fold state; validates and folds, in
+    chunks of at most 65,536 rows, a store's `next` carried from chunk to chunk until the store applies a row;
+    writes every present store from its result (maxima, optimistic header, best update — or
+    apply_light_client_update and no best); and keeps the rows after a store's applying row for the next round,
+    which validates them against the store as it then is.  Host work is O(stores) per round and O(1) per row.
+
+    stats_out (optional dict) receives rounds, validate_calls and table_uploads."""
+    v = verifier if verifier is not None else runtime.default_verifier()
+    _fold_check_config(v, "fold_light_client_updates_multi")
+    packed = isinstance(updates, PackedUpdates)
+    batch = updates if packed else pack_updates(updates)
+    row = (lambda i: L.unpack_update(batch, int(i))) if packed else (lambda i: updates[int(i)])
+    n = batch.n
+    if len(stores) != n:
+        raise ValueError("need one store per update")
+    accepted = np.zeros(n, bool)
+    reasons = np.zeros(n, np.uint8)
+    objs, ordinal = [], {}
+    owner = np.zeros(n, np.int64)
+    for i, s in enumerate(stores):
+        k = ordinal.get(id(s))
+        if k is None:
+            k = ordinal[id(s)] = len(objs)
+            objs.append(s)
+        owner[i] = k
+    chunk = min(FOLD_MAX_ROWS, int(getattr(v, "chunk_rows", FOLD_MAX_ROWS)))
+    cs, gvr = int(current_slot), bytes(genesis_validators_root)
+    zero = hashlib.sha256(bytes(L.SYNC_COMMITTEE_BYTES)).digest()
+    rounds = calls = uploads = 0
+    pending = np.arange(n)
+    while pending.size:
+        rounds += 1
+        present, local = np.unique(owner[pending], return_inverse=True)  # store row s <-> object objs[present[s]]
+        ns = present.size
+        # the table: one store row per present store object, committees shared by content
+        com, com_row = [], {}
+
+        def committee_row(sc: bytes) -> int:
+            d = hashlib.sha256(sc).digest()
+            if d == zero:
+                return STORE_NEXT_UNKNOWN
+            if d not in com_row:
+                com_row[d] = len(com)
+                com.append(sc)
+            return com_row[d]
+
+        fin, cur, nxt = np.zeros(ns, np.uint64), np.zeros(ns, np.uint32), np.zeros(ns, np.uint32)
+        states = []
+        for s, k in enumerate(present.tolist()):
+            f, c, x = _validation_key(objs[k])
+            fin[s], cur[s], nxt[s] = f, committee_row(c), committee_row(x)
+            states.append(_fold_state_of(objs[k]))
+        h = hashlib.sha256(b"".join(com_row))
+        h.update(fin.tobytes() + cur.tobytes() + nxt.tobytes())
+        committees = np.frombuffer(b"".join(com), np.uint8).reshape(len(com), L.SYNC_COMMITTEE_BYTES)
+        uploads += bool(runtime.ensure_store_table(v, h.digest(), committees, fin, cur, nxt))
+        apply_row, best_row, optimistic_row = (np.full(ns, -1, np.int64) for _ in range(3))  # batch rows
+        left = []
+        for pos in range(0, pending.size, chunk):
+            rows_ix, loc = pending[pos:pos + chunk], local[pos:pos + chunk]
+            live = apply_row[loc] < 0  # a store that applied in an earlier chunk consumes nothing more this round
+            if not live.all():
+                left.append(rows_ix[~live])
+                rows_ix, loc = rows_ix[live], loc[live]
+            if not rows_ix.size:
+                continue
+            ok, rs, res = v.validate_stores_fold(_take_rows(batch, rows_ix), loc, cs, gvr, states)
+            calls += 1
+            last = np.full(ns, rows_ix.size, np.int64)  # per store: the last row of this chunk it consumed
+            for s, r in enumerate(res):
+                if r is None:
+                    continue
+                states[s] = r.next
+                if r.best_row >= 0:
+                    best_row[s] = rows_ix[r.best_row]
+                if r.optimistic_row >= 0:
+                    optimistic_row[s] = rows_ix[r.optimistic_row]
+                if r.apply_row >= 0:
+                    apply_row[s], last[s] = rows_ix[r.apply_row], r.apply_row
+            consumed = np.arange(rows_ix.size) <= last[loc]
+            accepted[rows_ix[consumed]] = ok[consumed]
+            reasons[rows_ix[consumed]] = rs[consumed]
+            left.append(rows_ix[~consumed])
+        for s, k in enumerate(present.tolist()):
+            store = objs[k]
+            store.current_max_active_participants = states[s].current_max_active_participants
+            if optimistic_row[s] >= 0:
+                store.optimistic_header = row(optimistic_row[s]).attested_header
+            if apply_row[s] >= 0:
+                apply_light_client_update(store, row(apply_row[s]))
+                store.best_valid_update = None
+            elif best_row[s] >= 0:
+                store.best_valid_update = row(best_row[s])
+        pending = np.sort(np.concatenate(left)) if left else np.zeros(0, np.int64)
+    if reasons_out is not None:
+        reasons_out.extend(int(r) for r in reasons)
+    if stats_out is not None:
+        stats_out["rounds"] = rounds
+        stats_out["validate_calls"] = calls
+        stats_out["table_uploads"] = uploads
     return accepted
 
 
