@@ -378,6 +378,90 @@ int lcv_bootstrap_check_batch(lcv_ctx* ctx, const uint8_t* beacon112, const uint
                               const uint8_t* exec_branch128, const uint8_t* committees, const uint8_t* committee_branch160,
                               const uint8_t* trusted_root32, uint64_t n, uint8_t* reason_out);
 
+/* ---- the producer side, batched (full-node.md: create_light_client_update :138-188, _finality_update :197-205,
+ * _optimistic_update :213-219, create_light_client_bootstrap :105-121; block_to_light_client_header :43-91).
+ * Input: tables of sparse views and, per update, rows of those tables — a view shared by many updates (a block is
+ * `block` of one update and `attested_block` of the next) is hashed once.  A state view keeps the five fields the
+ * light-client data reads and every BeaconState field by its hash_tree_root (field_roots, 28 x 32 B in field
+ * order; entries 2, 4, 20, 22, 23 are recomputed); its two committees are rows of `committees` (ncomm x 24624 B,
+ * the distinct SSZ SyncCommittee values).  A block view keeps the header fields, the sync aggregate, the payload
+ * as the 832-byte execution record above and every body field by root (body_roots, 12 x 32 B; entry 8 is
+ * recomputed, entry 9 when exec_kind != 0).  exec_kind: 0 no payload, 1 Capella (15 fields), 2 Deneb (17).
+ * Every index — the cases', cur_index / nxt_index — and exec_kind are checked on the host before anything is
+ * launched: LCV_EINVAL names the first offender, no kernel runs and reason_out is not written.
+ * Kernels (lcv_last_timings: produce_views, produce_rows): HTR(SyncCommittee) per committee row; per block view the
+ * body tree -> header, block root, execution branch; per state view the state tree -> state root, the three
+ * branches, the root of latest_block_header with that state root; then per update the asserts and the row.
+ * reason_out[i] (lcv_producer_reason): the k-th check of create_light_client_update in evaluation order, the first
+ * failing one.  A row with a non-zero reason is LightClientUpdate(): every column zero, nsc_index = ncomm.
+ * Output pool: the ncomm input rows, then one all-zero row (npool = ncomm + 1); nsc_index[i] is the attested
+ * state's nxt_index where the update carries a next_sync_committee, else ncomm.  kind: 0 update, 1 finality update
+ * (next-committee fields zero), 2 optimistic update (finalized fields zero too), as lcv_ssz_decode_updates' rows.
+ * The fork epochs and periods are lcv_set_config's.  n == 0: LCV_OK, nothing done (*out = NULL). */
+enum lcv_producer_reason {
+  LCV_P_OK = 0,
+  LCV_P_ATTESTED_PRE_ALTAIR = 1,    /* :143 */
+  LCV_P_NO_PARTICIPANTS = 2,        /* :144 */
+  LCV_P_STATE_SLOT = 3,             /* :146 state.slot != state.latest_block_header.slot */
+  LCV_P_STATE_BLOCK = 4,            /* :149 header root (state_root filled in) != hash_tree_root(block.message) */
+  LCV_P_ATTESTED_STATE_SLOT = 5,    /* :152 */
+  LCV_P_ATTESTED_BLOCK = 6,         /* :155 attested header root, attested block root, block.parent_root */
+  LCV_P_ATTESTED_NO_PAYLOAD = 7,    /* :160 attested block at a Capella-or-later epoch with exec_kind 0 */
+  LCV_P_FINALIZED_NO_PAYLOAD = 8,   /* :171 the same for the finalized block */
+  LCV_P_FINALIZED_ROOT = 9,         /* :172 finalized header root != attested_state.finalized_checkpoint.root */
+  LCV_P_FINALIZED_GENESIS = 10      /* :174 genesis finalized block, checkpoint root not zero */
+};
+typedef struct lcv_state_views {
+  const uint64_t* slot;                /* ns */
+  const uint8_t* latest_block_header;  /* ns x 112 */
+  const uint64_t* fin_epoch;           /* ns: finalized_checkpoint.epoch */
+  const uint8_t* fin_root;             /* ns x 32: finalized_checkpoint.root */
+  const uint8_t* field_roots;          /* ns x 28 x 32 */
+  const uint32_t* cur_index;           /* ns: committee row of current_sync_committee */
+  const uint32_t* nxt_index;           /* ns: committee row of next_sync_committee */
+} lcv_state_views;
+typedef struct lcv_block_views {
+  const uint64_t* slot;            /* nb */
+  const uint64_t* proposer_index;  /* nb */
+  const uint8_t* parent_root;      /* nb x 32 */
+  const uint8_t* state_root;       /* nb x 32 */
+  const uint8_t* bits;             /* nb x 64: sync_aggregate.sync_committee_bits */
+  const uint8_t* signature;        /* nb x 96 */
+  const uint8_t* execution;        /* nb x 832 */
+  const uint8_t* exec_kind;        /* nb */
+  const uint8_t* body_roots;       /* nb x 12 x 32 */
+} lcv_block_views;
+typedef struct lcv_update_cases {
+  const uint32_t* state;           /* n: rows of the state views */
+  const uint32_t* block;           /* n: rows of the block views */
+  const uint32_t* attested_state;
+  const uint32_t* attested_block;
+  const int32_t* finalized_block;  /* n: row of the block views, or -1: none */
+} lcv_update_cases;
+/* the batch is made on the device, in lcv_batch_upload's layout: every resident entry takes it; lcv_batch_free */
+int lcv_create_updates_resident(lcv_ctx* ctx, const lcv_state_views* states, uint64_t ns, const lcv_block_views* blocks,
+                                uint64_t nb, const uint8_t* committees, uint64_t ncomm, const lcv_update_cases* cases,
+                                uint64_t n, int kind, uint8_t* reason_out, lcv_dbatch** out);
+/* the same, copied out: `out` names caller-allocated columns of n rows (written through) and a pool of ncomm + 1
+ * rows; out->n and out->npool are not read */
+int lcv_create_updates(lcv_ctx* ctx, const lcv_state_views* states, uint64_t ns, const lcv_block_views* blocks,
+                       uint64_t nb, const uint8_t* committees, uint64_t ncomm, const lcv_update_cases* cases,
+                       uint64_t n, int kind, const lcv_update_batch* out, uint8_t* reason_out);
+/* a resident batch back to the host: all its rows (rows == NULL, nrows ignored), or rows[0 .. nrows) in that order
+ * (each < the batch's n; gathered on the device); the pool is copied whole (out->nsc_pool: the batch's npool rows) */
+int lcv_batch_download(lcv_ctx* ctx, lcv_dbatch* b, const uint32_t* rows, uint64_t nrows, const lcv_update_batch* out);
+/* lcv_rank_updates over a resident batch: the same kernel, the same records */
+int lcv_rank_resident(lcv_ctx* ctx, lcv_dbatch* b, uint8_t* rank_out /* n x 32 */);
+/* create_light_client_bootstrap per (state_idx[i], block_idx[i]), from the same view kernels, as the columns
+ * lcv_bootstrap_check_batch takes; the committee as committee_index[i] = the state's cur_index.  reason: 1 :107
+ * state before Altair, 2 :109 state.slot != its header's slot, 3 :112 header root != block root, 4 a Capella-or-
+ * later block with exec_kind 0; such a row is all zero and its committee_index is ncomm */
+int lcv_create_bootstraps(lcv_ctx* ctx, const lcv_state_views* states, uint64_t ns, const lcv_block_views* blocks,
+                          uint64_t nb, const uint8_t* committees, uint64_t ncomm, const uint32_t* state_idx,
+                          const uint32_t* block_idx, uint64_t n, uint8_t* beacon112, uint8_t* exec832,
+                          uint8_t* exec_branch128, uint32_t* committee_index, uint8_t* committee_branch160,
+                          uint8_t* reason_out);
+
 /* ---- SSZ wire decode (host only, no device work; csrc/lcv_wire.cpp).  Replaces the upstream SSZ
  * deserialisation of the reference's containers (sync-protocol.md:109-115 LightClientBootstrap,
  * :120-133 LightClientUpdate, :138-148 LightClientFinalityUpdate, :153-160 LightClientOptimisticUpdate)

@@ -14,6 +14,7 @@
 #include "../../include/lcv.h"
 #include "lcv_items.hpp"
 #include "lcv_fold.hpp"
+#include "lcv_producer.hpp"
 #include "lcv_sop.hpp"
 #include "lcv_build_id.h"  // LCV_BUILD_ID (Makefile: tools/build_id.py over the sources)
 
@@ -22,11 +23,11 @@ using namespace lcv;
 // One mark per kernel launch (marks never nest, so the host simulation's op counter attributes every
 // operation to exactly one stage, and a HIP event pair brackets exactly one kernel on its stream).
 enum { ST_NSC = 0, ST_PRE, ST_H2C_MAP, ST_H2C, ST_SIG, ST_AGG, ST_MILLER, ST_FEXP, ST_VERDICT, ST_SETUP,
-       ST_LINES, ST_LINES_SIG, ST_SIGROOT, ST_RANK, ST_FOLD, ST_COUNT };
+       ST_LINES, ST_LINES_SIG, ST_SIGROOT, ST_RANK, ST_FOLD, ST_PRODUCE_VIEWS, ST_PRODUCE_ROWS, ST_COUNT };
 static const char* kStageNames[ST_COUNT] = {"nsc_htr", "pre_checks", "h2c_sswu", "hash_to_g2", "sig_decode",
                                             "g1_aggregate", "miller_loop", "final_exp", "verdict",
                                             "setup", "miller_lines", "miller_lines_sig", "signing_root",
-                                            "store_rank", "store_fold"};
+                                            "store_rank", "store_fold", "produce_views", "produce_rows"};
 
 struct CommitteeBufs {
   uint8_t* raw = nullptr;
@@ -651,6 +652,22 @@ struct BatchCols {
   size_t total = 0, n = 0, np = 0;
 };
 
+// the layout alone (no host sources): n rows, np pool rows, with a store_index column or not, ng fold segments
+static void batch_layout(BatchCols& c, size_t n, size_t np, bool stores, size_t ng) {
+  const size_t bytes[BATCH_COLS] = {112 * n, 832 * n, 128 * n, 112 * n, 832 * n, 128 * n, (size_t)K_SC * np, 4 * n,
+                                    160 * n, 192 * n, 64 * n, 96 * n, 8 * n, stores ? 4 * n : 0,
+                                    4 * ng, ng ? 4 * (ng + 1) : 0, ng ? 4 * n : 0, sizeof(FoldState) * ng};
+  c.total = 0;
+  for (int k = 0; k < BATCH_COLS; ++k) {
+    c.src[k] = nullptr;
+    c.bytes[k] = bytes[k];
+    c.off[k] = c.total;
+    c.total += (bytes[k] + 255) & ~(size_t)255;
+  }
+  c.n = n;
+  c.np = np;
+}
+
 static int batch_cols(lcv_ctx* ctx, const lcv_update_batch* hb, BatchCols& c, const char* who,
                       const uint32_t* store_index = nullptr, const FoldSegs* segs = nullptr) {
   const size_t n = hb->n, np = hb->npool, ng = segs ? segs->nseg : 0;
@@ -662,21 +679,12 @@ static int batch_cols(lcv_ctx* ctx, const lcv_update_batch* hb, BatchCols& c, co
                          hb->sync_bits, hb->sync_signature, hb->signature_slot, store_index,
                          ng ? segs->store.data() : nullptr, ng ? segs->off.data() : nullptr,
                          ng ? segs->row.data() : nullptr, ng ? segs->in.data() : nullptr};
-  const size_t bytes[BATCH_COLS] = {112 * n, 832 * n, 128 * n, 112 * n, 832 * n, 128 * n, (size_t)K_SC * np, 4 * n,
-                                    160 * n, 192 * n, 64 * n, 96 * n, 8 * n, store_index ? 4 * n : 0,
-                                    4 * ng, ng ? 4 * (ng + 1) : 0, ng ? 4 * n : 0, sizeof(FoldState) * ng};
-  c.total = 0;
-  for (int k = 0; k < BATCH_COLS; ++k) {
-    if (!src[k] && k < 13) return fail(ctx, LCV_EINVAL, std::string(who) + ": null column");
-    c.src[k] = src[k];
-    c.bytes[k] = bytes[k];
-    c.off[k] = c.total;
-    c.total += (bytes[k] + 255) & ~(size_t)255;
-  }
+  for (int k = 0; k < 13; ++k)
+    if (!src[k]) return fail(ctx, LCV_EINVAL, std::string(who) + ": null column");
+  batch_layout(c, n, np, store_index != nullptr, ng);
+  for (int k = 0; k < BATCH_COLS; ++k) c.src[k] = src[k];
   for (size_t i = 0; i < n; ++i)
     if (hb->nsc_index[i] >= np) return fail(ctx, LCV_EINVAL, std::string(who) + ": nsc_index out of range");
-  c.n = n;
-  c.np = np;
   return LCV_OK;
 }
 
@@ -2085,6 +2093,299 @@ int lcv_debug_pairing(lcv_ctx* ctx, const uint8_t* p96, const uint8_t* q192, uin
     return be_launch(ctx, F_export_fp12{W.f, W.cap, d[2]}, (uint32_t)n);
   });
   be_collect_timings(ctx);  // miller / final_exp kernel times (lcv_last_timings)
+  return rc;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ the producer side (lcv_producer.hpp)
+// One device allocation per call: the view tables, the cases, the stage-0 / stage-1 scratch rows, the reasons (and
+// what a caller adds: `extra`).  Every index a kernel follows is checked on the host before anything is launched.
+struct ProdRun {
+  void* mem = nullptr;
+  uint8_t* extra = nullptr;  // the caller's part of the allocation
+  uint8_t* reason = nullptr; // [n]
+  ProdStates S; ProdBlocks K; ProdCases C; ProdScratch X;
+  const uint32_t* idx0 = nullptr;  // the bootstrap entry's two index columns
+  const uint32_t* idx1 = nullptr;
+};
+
+static int prod_check_views(lcv_ctx* ctx, const char* who, const lcv_state_views* s, uint64_t ns, const lcv_block_views* b,
+                            uint64_t nb, const uint8_t* committees, uint64_t ncomm) {
+  const std::string w(who);
+  if (!s->slot || !s->latest_block_header || !s->fin_epoch || !s->fin_root || !s->field_roots || !s->cur_index ||
+      !s->nxt_index || !b->slot || !b->proposer_index || !b->parent_root || !b->state_root || !b->bits || !b->signature ||
+      !b->execution || !b->exec_kind || !b->body_roots || !committees)
+    return fail(ctx, LCV_EINVAL, w + ": null column");
+  if (ns == 0 || nb == 0 || ncomm == 0 || ns >= 0xffffffffull || nb >= 0xffffffffull || ncomm >= 0xffffffffull)
+    return fail(ctx, LCV_EINVAL, w + ": need 0 < ns, nb, ncomm < 2^32 - 1");
+  for (uint64_t t = 0; t < ns; ++t)
+    if (s->cur_index[t] >= ncomm || s->nxt_index[t] >= ncomm)
+      return fail(ctx, LCV_EINVAL, w + ": committee index of state view " + std::to_string(t) + " out of range");
+  for (uint64_t k = 0; k < nb; ++k)
+    if (b->exec_kind[k] > 2)
+      return fail(ctx, LCV_EINVAL, w + ": exec_kind of block view " + std::to_string(k) + " is not 0, 1 or 2");
+  return LCV_OK;
+}
+static int prod_check_index(lcv_ctx* ctx, const char* who, const char* col, const uint32_t* ix, uint64_t n, uint64_t lim) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (ix[i] >= lim)
+      return fail(ctx, LCV_EINVAL, std::string(who) + ": " + col + "[" + std::to_string(i) + "] = " +
+                                       std::to_string(ix[i]) + " out of range (" + std::to_string(lim) + " rows)");
+  return LCV_OK;
+}
+
+// uploads the views (and the n-row index columns ix[0 .. nix), 4 bytes per entry), hashes the committee rows of
+// `pool` (device, ncomm rows of K_SC bytes; null: `committees` is uploaded into the allocation) and runs stage 1
+static int prod_views(lcv_ctx* ctx, const lcv_state_views* s, uint64_t ns, const lcv_block_views* b, uint64_t nb,
+                      const uint8_t* committees, const uint8_t* pool, uint64_t ncomm, const void* const* ix, int nix,
+                      uint64_t n, size_t extra_bytes, ProdRun& R) {
+  enum { NV = 16 };
+  const void* src[NV] = {s->slot, s->latest_block_header, s->fin_epoch, s->fin_root, s->field_roots, s->cur_index,
+                         s->nxt_index, b->slot, b->proposer_index, b->parent_root, b->state_root, b->bits,
+                         b->signature, b->execution, b->exec_kind, b->body_roots};
+  const size_t bytes[NV] = {8 * ns, 112 * ns, 8 * ns, 32 * ns, 32 * PROD_STATE_FIELDS * ns, 4 * ns, 4 * ns, 8 * nb, 8 * nb,
+                            32 * nb, 32 * nb, 64 * nb, 96 * nb, (size_t)K_EXEC * nb, nb, 32 * PROD_BODY_FIELDS * nb};
+  auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  size_t off[NV], total = 0;
+  for (int k = 0; k < NV; ++k) { off[k] = total; total += pad(bytes[k]); }
+  size_t ixoff[8];
+  for (int k = 0; k < nix; ++k) { ixoff[k] = total; total += pad(4 * n); }
+  const size_t o_pool = total; total += pool ? 0 : pad((size_t)K_SC * ncomm);
+  const size_t o_root = total; total += pad(32 * ncomm);
+  const size_t o_flag = total; total += pad(ncomm);
+  const size_t o_blk = total; total += pad((size_t)PROD_BLK_ROW * nb);
+  const size_t o_st = total; total += pad((size_t)PROD_ST_ROW * ns);
+  const size_t o_reason = total; total += pad(n);
+  const size_t o_extra = total; total += pad(extra_bytes);
+  LCV_TRY(be_alloc(ctx, &R.mem, total));
+  uint8_t* m = (uint8_t*)R.mem;
+  for (int k = 0; k < NV; ++k) LCV_TRY(be_h2d(ctx, m + off[k], src[k], bytes[k]));
+  for (int k = 0; k < nix; ++k) LCV_TRY(be_h2d(ctx, m + ixoff[k], ix[k], 4 * n));
+  if (!pool) {
+    LCV_TRY(be_h2d(ctx, m + o_pool, committees, (size_t)K_SC * ncomm));
+    pool = m + o_pool;
+  }
+  R.S = ProdStates{(const uint64_t*)(m + off[0]), m + off[1], (const uint64_t*)(m + off[2]), m + off[3], m + off[4],
+                   (const uint32_t*)(m + off[5]), (const uint32_t*)(m + off[6])};
+  R.K = ProdBlocks{(const uint64_t*)(m + off[7]), (const uint64_t*)(m + off[8]), m + off[9], m + off[10], m + off[11],
+                   m + off[12], m + off[13], m + off[14], m + off[15]};
+  if (nix == 5)
+    R.C = ProdCases{(const uint32_t*)(m + ixoff[0]), (const uint32_t*)(m + ixoff[1]), (const uint32_t*)(m + ixoff[2]),
+                    (const uint32_t*)(m + ixoff[3]), (const int32_t*)(m + ixoff[4])};
+  if (nix == 2) { R.idx0 = (const uint32_t*)(m + ixoff[0]); R.idx1 = (const uint32_t*)(m + ixoff[1]); }
+  R.X = ProdScratch{(const uint32_t*)(m + o_root), (uint32_t)ncomm, m + o_blk, m + o_st};
+  R.reason = m + o_reason;
+  R.extra = m + o_extra;
+  // stage 0: HTR(SyncCommittee) per committee row on validation's own 64-lane tree (its store-equality flag
+  // compares every row with row 0 and is not read)
+  BatchDev PB = {};
+  PB.nsc_pool = pool;
+  PB.npool = (uint32_t)ncomm;
+  CommitteeDev PC = {};
+  PC.next_raw = pool;
+  Work PW = Work{};
+  PW.pool_cap = (uint32_t)ncomm;
+  PW.nsc_root = (uint32_t*)(m + o_root);
+  PW.nsc_flags = m + o_flag;
+  be_stage_begin(ctx, ST_PRODUCE_VIEWS);
+  LCV_TRY(be_launch_team(ctx, F_nsc_team{PB, PC, PW}, (uint32_t)ncomm));
+  be_stage_end(ctx, ST_PRODUCE_VIEWS);
+  be_stage_begin(ctx, ST_PRODUCE_VIEWS);
+  LCV_TRY(be_launch(ctx, F_prod_block{R.K, R.X}, (uint32_t)nb));
+  be_stage_end(ctx, ST_PRODUCE_VIEWS);
+  be_stage_begin(ctx, ST_PRODUCE_VIEWS);
+  LCV_TRY(be_launch(ctx, F_prod_state{R.S, R.X}, (uint32_t)ns));
+  be_stage_end(ctx, ST_PRODUCE_VIEWS);
+  return LCV_OK;
+}
+
+static ProdOut prod_out(const BatchDev& B) {
+  return ProdOut{(uint8_t*)B.att_beacon, (uint8_t*)B.att_exec, (uint8_t*)B.att_branch, (uint8_t*)B.fin_beacon,
+                 (uint8_t*)B.fin_exec, (uint8_t*)B.fin_branch, (uint32_t*)B.nsc_index, (uint8_t*)B.nsc_branch,
+                 (uint8_t*)B.finality_branch, (uint8_t*)B.bits, (uint8_t*)B.sig, (uint64_t*)B.sig_slot};
+}
+
+// a resident batch's 12 row columns (and its pool, when asked) to the caller's arrays
+static int prod_copy_out(lcv_ctx* ctx, const BatchDev& B, size_t n, const lcv_update_batch* out, bool with_pool,
+                         size_t npool) {
+  void* dst[12] = {(void*)out->attested.beacon, (void*)out->attested.execution, (void*)out->attested.exec_branch,
+                   (void*)out->finalized.beacon, (void*)out->finalized.execution, (void*)out->finalized.exec_branch,
+                   (void*)out->nsc_index, (void*)out->nsc_branch, (void*)out->finality_branch, (void*)out->sync_bits,
+                   (void*)out->sync_signature, (void*)out->signature_slot};
+  const void* src[12] = {B.att_beacon, B.att_exec, B.att_branch, B.fin_beacon, B.fin_exec, B.fin_branch, B.nsc_index,
+                         B.nsc_branch, B.finality_branch, B.bits, B.sig, B.sig_slot};
+  const size_t width[12] = {112, 832, 128, 112, 832, 128, 4, 160, 192, 64, 96, 8};
+  for (int k = 0; k < 12; ++k) LCV_TRY(be_d2h(ctx, dst[k], src[k], width[k] * n));
+  if (with_pool) LCV_TRY(be_d2h(ctx, (void*)out->nsc_pool, B.nsc_pool, (size_t)K_SC * npool));
+  return LCV_OK;
+}
+static bool batch_out_null(const lcv_update_batch* o) {
+  return !o || !o->attested.beacon || !o->attested.execution || !o->attested.exec_branch || !o->finalized.beacon ||
+         !o->finalized.execution || !o->finalized.exec_branch || !o->nsc_pool || !o->nsc_index || !o->nsc_branch ||
+         !o->finality_branch || !o->sync_bits || !o->sync_signature || !o->signature_slot;
+}
+
+extern "C" {
+
+int lcv_create_updates_resident(lcv_ctx* ctx, const lcv_state_views* states, uint64_t ns, const lcv_block_views* blocks,
+                                uint64_t nb, const uint8_t* committees, uint64_t ncomm, const lcv_update_cases* cases,
+                                uint64_t n, int kind, uint8_t* reason_out, lcv_dbatch** out) {
+  const char* who = "lcv_create_updates";
+  if (out) *out = nullptr;
+  if (!ctx || !states || !blocks || !committees || !cases || !reason_out || !out)
+    return fail(ctx, LCV_EINVAL, std::string(who) + ": null argument");
+  if (kind < 0 || kind > 2) return fail(ctx, LCV_EINVAL, std::string(who) + ": kind is 0 (update), 1 (finality) or 2 (optimistic)");
+  if (n == 0) return LCV_OK;
+  if (n >= 0xffffffffull) return fail(ctx, LCV_EINVAL, std::string(who) + ": need n < 2^32 - 1");
+  if (!cases->state || !cases->block || !cases->attested_state || !cases->attested_block || !cases->finalized_block)
+    return fail(ctx, LCV_EINVAL, std::string(who) + ": null column");
+  LCV_TRY(prod_check_views(ctx, who, states, ns, blocks, nb, committees, ncomm));
+  LCV_TRY(prod_check_index(ctx, who, "state", cases->state, n, ns));
+  LCV_TRY(prod_check_index(ctx, who, "block", cases->block, n, nb));
+  LCV_TRY(prod_check_index(ctx, who, "attested_state", cases->attested_state, n, ns));
+  LCV_TRY(prod_check_index(ctx, who, "attested_block", cases->attested_block, n, nb));
+  for (uint64_t i = 0; i < n; ++i)
+    if (cases->finalized_block[i] < -1 || (cases->finalized_block[i] >= 0 && (uint64_t)cases->finalized_block[i] >= nb))
+      return fail(ctx, LCV_EINVAL, std::string(who) + ": finalized_block[" + std::to_string(i) + "] = " +
+                                       std::to_string(cases->finalized_block[i]) + " out of range (-1, or a row of " +
+                                       std::to_string(nb) + ")");
+  // the batch: lcv_batch_upload's layout, the pool = the committee rows and one all-zero row
+  BatchCols c;
+  batch_layout(c, n, ncomm + 1, false, 0);
+  lcv_dbatch* db = new (std::nothrow) lcv_dbatch();
+  if (!db) return LCV_ENOMEM;
+  be_set_slot(ctx, 0);
+  int rc = be_alloc(ctx, &db->mem, c.total);
+  if (rc != LCV_OK) { delete db; return rc; }
+  uint8_t* m = (uint8_t*)db->mem;
+  bind_batch(db, m, c);
+  ProdRun R;
+  be_reset_timings(ctx);
+  auto body = [&]() -> int {
+    LCV_TRY(be_h2d(ctx, m + c.off[6], committees, (size_t)K_SC * ncomm));
+    LCV_TRY(be_memset(ctx, m + c.off[6] + (size_t)K_SC * ncomm, 0, K_SC));
+    const void* ix[5] = {cases->state, cases->block, cases->attested_state, cases->attested_block, cases->finalized_block};
+    LCV_TRY(prod_views(ctx, states, ns, blocks, nb, committees, db->B.nsc_pool, ncomm, ix, 5, n, 0, R));
+    be_stage_begin(ctx, ST_PRODUCE_ROWS);
+    LCV_TRY(be_launch_team(ctx, F_prod_rows{R.S, R.K, R.C, R.X, prod_out(db->B), ctx->cfg, (uint32_t)kind,
+                                            (uint32_t)ncomm, R.reason}, (uint32_t)n));
+    be_stage_end(ctx, ST_PRODUCE_ROWS);
+    LCV_TRY(be_d2h(ctx, reason_out, R.reason, n));
+    LCV_TRY(be_sync(ctx));
+    be_collect_timings(ctx);
+    return LCV_OK;
+  };
+  rc = body();
+  if (R.mem) be_free(ctx, R.mem);  // (waits for the streams)
+  if (rc != LCV_OK) { be_free(ctx, db->mem); delete db; return rc; }
+  *out = db;
+  return LCV_OK;
+}
+
+int lcv_batch_download(lcv_ctx* ctx, lcv_dbatch* b, const uint32_t* rows, uint64_t nrows, const lcv_update_batch* out) {
+  if (!ctx || !b || batch_out_null(out)) return fail(ctx, LCV_EINVAL, "lcv_batch_download: null argument");
+  be_set_slot(ctx, 0);
+  if (!rows) {
+    LCV_TRY(prod_copy_out(ctx, b->B, b->n, out, true, b->npool));
+    return be_sync(ctx);
+  }
+  if (nrows >= 0xffffffffull) return fail(ctx, LCV_EINVAL, "lcv_batch_download: need nrows < 2^32 - 1");
+  LCV_TRY(prod_check_index(ctx, "lcv_batch_download", "rows", rows, nrows, b->n));
+  LCV_TRY(be_d2h(ctx, (void*)out->nsc_pool, b->B.nsc_pool, (size_t)K_SC * b->npool));
+  if (nrows == 0) return be_sync(ctx);
+  // the listed rows are gathered on the device into a batch of nrows rows (no pool), which is copied out
+  BatchCols c;
+  batch_layout(c, nrows, 0, false, 0);
+  const size_t o_rows = c.total;
+  void* mem = nullptr;
+  LCV_TRY(be_alloc(ctx, &mem, c.total + 4 * nrows));
+  lcv_dbatch t;
+  bind_batch(&t, (uint8_t*)mem, c);
+  auto body = [&]() -> int {
+    LCV_TRY(be_h2d(ctx, (uint8_t*)mem + o_rows, rows, 4 * nrows));
+    LCV_TRY(be_launch_team(ctx, F_prod_pick{b->B, (const uint32_t*)((uint8_t*)mem + o_rows), prod_out(t.B)}, (uint32_t)nrows));
+    LCV_TRY(prod_copy_out(ctx, t.B, nrows, out, false, 0));
+    return be_sync(ctx);
+  };
+  const int rc = body();
+  be_free(ctx, mem);
+  return rc;
+}
+
+int lcv_create_updates(lcv_ctx* ctx, const lcv_state_views* states, uint64_t ns, const lcv_block_views* blocks,
+                       uint64_t nb, const uint8_t* committees, uint64_t ncomm, const lcv_update_cases* cases,
+                       uint64_t n, int kind, const lcv_update_batch* out, uint8_t* reason_out) {
+  if (!ctx || batch_out_null(out)) return fail(ctx, LCV_EINVAL, "lcv_create_updates: null argument");
+  lcv_dbatch* db = nullptr;
+  LCV_TRY(lcv_create_updates_resident(ctx, states, ns, blocks, nb, committees, ncomm, cases, n, kind, reason_out, &db));
+  if (!db) return LCV_OK;  // n == 0
+  const int rc = lcv_batch_download(ctx, db, nullptr, 0, out);
+  lcv_batch_free(ctx, db);
+  return rc;
+}
+
+// lcv_rank_updates over a resident batch: F_rank on the batch where it lies, the records copied out
+int lcv_rank_resident(lcv_ctx* ctx, lcv_dbatch* b, uint8_t* rank_out) {
+  if (!ctx || !b || !rank_out) return fail(ctx, LCV_EINVAL, "lcv_rank_resident: null argument");
+  if (b->n == 0) return LCV_OK;
+  void* mem = nullptr;
+  be_set_slot(ctx, 0);
+  LCV_TRY(be_alloc(ctx, &mem, rank_index(b->n)));
+  Work W = Work{};
+  W.rank = (uint8_t*)mem;
+  Params P = {};
+  P.cfg = ctx->cfg;
+  be_reset_timings(ctx);
+  auto body = [&]() -> int {
+    LCV_TRY(rank_stage(ctx, b->B, P, W, (uint32_t)b->n));
+    LCV_TRY(be_d2h(ctx, rank_out, W.rank, rank_index(b->n)));
+    LCV_TRY(be_sync(ctx));
+    be_collect_timings(ctx);
+    return LCV_OK;
+  };
+  const int rc = body();
+  be_free(ctx, mem);
+  return rc;
+}
+
+int lcv_create_bootstraps(lcv_ctx* ctx, const lcv_state_views* states, uint64_t ns, const lcv_block_views* blocks,
+                          uint64_t nb, const uint8_t* committees, uint64_t ncomm, const uint32_t* state_idx,
+                          const uint32_t* block_idx, uint64_t n, uint8_t* beacon112, uint8_t* exec832,
+                          uint8_t* exec_branch128, uint32_t* committee_index, uint8_t* committee_branch160,
+                          uint8_t* reason_out) {
+  const char* who = "lcv_create_bootstraps";
+  if (!ctx || !states || !blocks || !committees || !state_idx || !block_idx || !beacon112 || !exec832 || !exec_branch128 ||
+      !committee_index || !committee_branch160 || !reason_out)
+    return fail(ctx, LCV_EINVAL, std::string(who) + ": null argument");
+  if (n == 0) return LCV_OK;
+  if (n >= 0xffffffffull) return fail(ctx, LCV_EINVAL, std::string(who) + ": need n < 2^32 - 1");
+  LCV_TRY(prod_check_views(ctx, who, states, ns, blocks, nb, committees, ncomm));
+  LCV_TRY(prod_check_index(ctx, who, "state_idx", state_idx, n, ns));
+  LCV_TRY(prod_check_index(ctx, who, "block_idx", block_idx, n, nb));
+  const size_t width[5] = {K_BEACON, K_EXEC, K_EXEC_BRANCH, 4, K_NSC_BRANCH};
+  size_t off[5], extra = 0;
+  for (int k = 0; k < 5; ++k) { off[k] = extra; extra += (width[k] * n + 255) & ~(size_t)255; }
+  ProdRun R;
+  be_set_slot(ctx, 0);
+  be_reset_timings(ctx);
+  auto body = [&]() -> int {
+    const void* ix[2] = {state_idx, block_idx};
+    LCV_TRY(prod_views(ctx, states, ns, blocks, nb, committees, nullptr, ncomm, ix, 2, n, extra, R));
+    uint8_t* e = R.extra;
+    const ProdBootOut O = {e + off[0], e + off[1], e + off[2], (uint32_t*)(e + off[3]), e + off[4], R.reason};
+    be_stage_begin(ctx, ST_PRODUCE_ROWS);
+    LCV_TRY(be_launch_team(ctx, F_prod_boot{R.S, R.K, R.idx0, R.idx1, R.X, O, ctx->cfg, (uint32_t)ncomm}, (uint32_t)n));
+    be_stage_end(ctx, ST_PRODUCE_ROWS);
+    void* dst[5] = {beacon112, exec832, exec_branch128, committee_index, committee_branch160};
+    for (int k = 0; k < 5; ++k) LCV_TRY(be_d2h(ctx, dst[k], e + off[k], width[k] * n));
+    LCV_TRY(be_d2h(ctx, reason_out, R.reason, n));
+    LCV_TRY(be_sync(ctx));
+    be_collect_timings(ctx);
+    return LCV_OK;
+  };
+  const int rc = body();
+  if (R.mem) be_free(ctx, R.mem);
   return rc;
 }
 

@@ -30,7 +30,7 @@ struct Backend {
   int open_stage[4] = {-1, -1, -1, -1};
   std::chrono::steady_clock::time_point t0[4];
   unsigned long long ops0[4][4] = {};
-  unsigned long long ops[16][4] = {};
+  unsigned long long ops[32][4] = {};  // per stage (ST_COUNT <= 32)
   // test-only stand-in for the RCCL communicator: collectives through files in a directory shared by
   // the ranks (the "unique id" is its path), so the multi-process path runs on the CPU (tests/test_multi.py)
   std::string comm_dir;
@@ -161,7 +161,7 @@ static void be_stage_end(lcv_ctx* ctx, int stage) {
 static void be_reset_timings(lcv_ctx* ctx) {
   for (int k = 0; k < 4; ++k) ctx->be.open_stage[k] = -1;
   for (int s = 0; s < ST_COUNT; ++s) ctx->stage_ms[s] = 0.f;
-  for (int s = 0; s < 16; ++s) for (int k = 0; k < 4; ++k) ctx->be.ops[s][k] = 0;
+  for (int s = 0; s < 32; ++s) for (int k = 0; k < 4; ++k) ctx->be.ops[s][k] = 0;
 }
 static void be_collect_timings(lcv_ctx*) {}
 
@@ -265,7 +265,7 @@ extern "C" int lcv_device_count(int* out) {
 // 3 SOP half-multiplications (a 12x12-limb product or a Montgomery reduction)
 extern "C" int lcv_debug_opcounts(lcv_ctx* ctx, unsigned long long* out, int max_stages) {
   if (!ctx || !out) return LCV_EINVAL;
-  for (int s = 0; s < max_stages && s < 16; ++s)
+  for (int s = 0; s < max_stages && s < 32; ++s)
     for (int k = 0; k < 4; ++k) out[4 * s + k] = ctx->be.ops[s][k];
   return LCV_OK;
 }

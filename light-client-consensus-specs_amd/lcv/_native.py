@@ -85,6 +85,24 @@ class FoldResultC(C.Structure):
     ]
 
 
+class StateViews(C.Structure):
+    """lcv_state_views."""
+    _fields_ = [("slot", u64p), ("latest_block_header", u8p), ("fin_epoch", u64p), ("fin_root", u8p),
+                ("field_roots", u8p), ("cur_index", u32p), ("nxt_index", u32p)]
+
+
+class BlockViews(C.Structure):
+    """lcv_block_views."""
+    _fields_ = [("slot", u64p), ("proposer_index", u64p), ("parent_root", u8p), ("state_root", u8p), ("bits", u8p),
+                ("signature", u8p), ("execution", u8p), ("exec_kind", u8p), ("body_roots", u8p)]
+
+
+class UpdateCases(C.Structure):
+    """lcv_update_cases."""
+    _fields_ = [("state", u32p), ("block", u32p), ("attested_state", u32p), ("attested_block", u32p),
+                ("finalized_block", C.POINTER(C.c_int32))]
+
+
 RANK_BYTES = 32
 FOLD_MAX_ROWS = 65536
 STORE_NEXT_UNKNOWN = 0xFFFFFFFF
@@ -151,6 +169,16 @@ SIGNATURES = {
     "lcv_merkle_branch_batch": (C.c_int, [C.c_void_p, u8p, u8p, C.c_uint32, C.c_uint64, u8p, C.c_uint64, u8p]),
     "lcv_htr_sync_committee_batch": (C.c_int, [C.c_void_p, u8p, C.c_uint64, u8p]),
     "lcv_bootstrap_check_batch": (C.c_int, [C.c_void_p, u8p, u8p, u8p, u8p, u8p, u8p, C.c_uint64, u8p]),
+    "lcv_create_updates_resident": (C.c_int, [C.c_void_p, C.POINTER(StateViews), C.c_uint64, C.POINTER(BlockViews),
+                                              C.c_uint64, u8p, C.c_uint64, C.POINTER(UpdateCases), C.c_uint64, C.c_int,
+                                              u8p, C.POINTER(C.c_void_p)]),
+    "lcv_create_updates": (C.c_int, [C.c_void_p, C.POINTER(StateViews), C.c_uint64, C.POINTER(BlockViews), C.c_uint64,
+                                     u8p, C.c_uint64, C.POINTER(UpdateCases), C.c_uint64, C.c_int,
+                                     C.POINTER(UpdateBatch), u8p]),
+    "lcv_batch_download": (C.c_int, [C.c_void_p, C.c_void_p, u32p, C.c_uint64, C.POINTER(UpdateBatch)]),
+    "lcv_rank_resident": (C.c_int, [C.c_void_p, C.c_void_p, u8p]),
+    "lcv_create_bootstraps": (C.c_int, [C.c_void_p, C.POINTER(StateViews), C.c_uint64, C.POINTER(BlockViews), C.c_uint64,
+                                        u8p, C.c_uint64, u32p, u32p, C.c_uint64, u8p, u8p, u8p, u32p, u8p, u8p]),
     "lcv_ssz_decode_updates": (C.c_int, [u8p, u64p, u64p, C.c_uint64, C.c_int, C.c_int, C.POINTER(UpdateBatch),
                                          u64p, u64p, u8p]),
     "lcv_ssz_decode_updates_mixed": (C.c_int, [u8p, u64p, u64p, C.c_uint64, C.c_int, u8p, C.POINTER(UpdateBatch),

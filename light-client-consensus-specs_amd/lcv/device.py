@@ -8,8 +8,8 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from . import config as _config
-from ._native import (Lib, LcvError, UpdateBatch, HeaderCols, StoreTable, FoldStateC, FoldResultC,
-                      STORE_NEXT_UNKNOWN, as_u8, load, ptr)
+from ._native import (Lib, LcvError, UpdateBatch, HeaderCols, StoreTable, FoldStateC, FoldResultC, StateViews,
+                      BlockViews, UpdateCases, STORE_NEXT_UNKNOWN, as_u8, load, ptr)
 
 SYNC_COMMITTEE_BYTES = 24624
 EXEC_RECORD_BYTES = 832
@@ -130,15 +130,103 @@ class PackedUpdates:
         return b, keep
 
 
+    @staticmethod
+    def empty(n: int, npool: int) -> "PackedUpdates":
+        """An all-zero batch of n rows and npool pool rows (the arrays the download entries write into)."""
+        z = lambda *shape: np.zeros(shape, np.uint8)  # noqa: E731
+        return PackedUpdates(att_beacon=z(n, 112), att_exec=z(n, 832), att_branch=z(n, 128), fin_beacon=z(n, 112),
+                             fin_exec=z(n, 832), fin_branch=z(n, 128), nsc_pool=z(npool, SYNC_COMMITTEE_BYTES),
+                             nsc_index=np.zeros(n, np.uint32), nsc_branch=z(n, 160), finality_branch=z(n, 192),
+                             sync_bits=z(n, 64), sync_signature=z(n, 96), signature_slot=np.zeros(n, np.uint64))
+
+
+UPDATE_KINDS = {"update": 0, "finality": 1, "optimistic": 2}
+
+
+@dataclass
+class PackedViews:
+    """Tables of sparse state / block views (include/lcv.h lcv_state_views, lcv_block_views) and the pool of their
+    distinct SyncCommittee values: the input of the batched producer entries (lcv.producer.pack_views)."""
+    state_slot: np.ndarray        # (ns,) u64
+    state_header: np.ndarray      # (ns, 112) u8  latest_block_header
+    state_fin_epoch: np.ndarray   # (ns,) u64
+    state_fin_root: np.ndarray    # (ns, 32) u8
+    state_roots: np.ndarray       # (ns, 28, 32) u8
+    state_cur: np.ndarray         # (ns,) u32  committee row of current_sync_committee
+    state_nxt: np.ndarray         # (ns,) u32  committee row of next_sync_committee
+    block_slot: np.ndarray        # (nb,) u64
+    block_proposer: np.ndarray    # (nb,) u64
+    block_parent: np.ndarray      # (nb, 32) u8
+    block_state_root: np.ndarray  # (nb, 32) u8
+    block_bits: np.ndarray        # (nb, 64) u8
+    block_sig: np.ndarray         # (nb, 96) u8
+    block_exec: np.ndarray        # (nb, 832) u8
+    block_kind: np.ndarray        # (nb,) u8   0 no payload, 1 Capella, 2 Deneb
+    block_roots: np.ndarray       # (nb, 12, 32) u8
+    committees: np.ndarray        # (ncomm, 24624) u8
+
+    _SPEC = dict(state_slot=(np.uint64, ()), state_header=(np.uint8, (112,)), state_fin_epoch=(np.uint64, ()),
+                 state_fin_root=(np.uint8, (32,)), state_roots=(np.uint8, (28, 32)), state_cur=(np.uint32, ()),
+                 state_nxt=(np.uint32, ()), block_slot=(np.uint64, ()), block_proposer=(np.uint64, ()),
+                 block_parent=(np.uint8, (32,)), block_state_root=(np.uint8, (32,)), block_bits=(np.uint8, (64,)),
+                 block_sig=(np.uint8, (96,)), block_exec=(np.uint8, (EXEC_RECORD_BYTES,)), block_kind=(np.uint8, ()),
+                 block_roots=(np.uint8, (12, 32)), committees=(np.uint8, (SYNC_COMMITTEE_BYTES,)))
+
+    @property
+    def ns(self) -> int:
+        return int(self.state_slot.shape[0])
+
+    @property
+    def nb(self) -> int:
+        return int(self.block_slot.shape[0])
+
+    @property
+    def ncomm(self) -> int:
+        return int(self.committees.shape[0])
+
+    def to_c(self):
+        keep = {}
+        for name, (dt, tail) in self._SPEC.items():
+            rows = self.ncomm if name == "committees" else self.ns if name.startswith("state_") else self.nb
+            a = np.ascontiguousarray(getattr(self, name), dt)
+            if a.shape != (rows,) + tail:
+                raise ValueError(f"{name}: need {np.dtype(dt).name} {(rows,) + tail}, got {a.shape}")
+            keep[name] = a
+        P = lambda name, t=C.c_uint8: ptr(keep[name], t)  # noqa: E731
+        sv = StateViews(P("state_slot", C.c_uint64), P("state_header"), P("state_fin_epoch", C.c_uint64),
+                        P("state_fin_root"), P("state_roots"), P("state_cur", C.c_uint32), P("state_nxt", C.c_uint32))
+        bv = BlockViews(P("block_slot", C.c_uint64), P("block_proposer", C.c_uint64), P("block_parent"),
+                        P("block_state_root"), P("block_bits"), P("block_sig"), P("block_exec"), P("block_kind"),
+                        P("block_roots"))
+        return sv, bv, P("committees"), keep
+
+
+def _cases_to_c(cases):
+    """(n, 5) rows of (state, block, attested_state, attested_block, finalized_block or -1) -> lcv_update_cases."""
+    a = np.asarray(cases, np.int64).reshape(-1, 5)
+    if a.size and (a[:, :4].min() < 0 or a.max() > 0x7FFFFFFF or a[:, 4].min() < -(1 << 31)):
+        raise ValueError("cases: rows are (state, block, attested_state, attested_block, finalized_block or -1)")
+    cols = [np.ascontiguousarray(a[:, k], np.uint32) for k in range(4)] + [np.ascontiguousarray(a[:, 4], np.int32)]
+    uc = UpdateCases(*[ptr(c, C.c_uint32) for c in cols[:4]], ptr(cols[4], C.c_int32))
+    return uc, cols, int(a.shape[0])
+
+
+def _writable_c(p: "PackedUpdates"):
+    b, keep = p.to_c()  # (C-contiguous arrays are passed as they are: the entries write through the pointers)
+    return b, keep
+
+
 class ResidentBatch:
     """A device-resident batch (Verifier.upload).  `stores`: it carries its store_index column, so every
     validate_resident* call validates it against the store table instead of the set_store snapshot."""
 
-    def __init__(self, verifier: "Verifier", handle: C.c_void_p, n: int, stores: bool = False):
+    def __init__(self, verifier: "Verifier", handle: C.c_void_p, n: int, stores: bool = False,
+                 npool: Optional[int] = None):
         self.v = verifier
         self.handle = handle
         self.n = n
         self.stores = stores
+        self.npool = npool  # pool rows (Verifier.download sizes its arrays by it)
 
     def free(self):
         if self.handle:
@@ -225,9 +313,9 @@ class Verifier:
                 "items": dict(zip(("lines", "miller_acc", "fexp", "h2c"), (int(x) for x in out[4:8])))}
 
     def last_timings(self) -> Dict[str, float]:
-        ms = (C.c_float * 16)()
+        ms = (C.c_float * 32)()
         n = C.c_int()
-        self._check(self.lib.lcv_last_timings(self.ctx, ms, 16, C.byref(n)), "lcv_last_timings")
+        self._check(self.lib.lcv_last_timings(self.ctx, ms, 32, C.byref(n)), "lcv_last_timings")
         return {self.lib.lcv_stage_name(i).decode(): float(ms[i]) for i in range(n.value)}
 
     # ------------------------------------------------------------------ validation
@@ -295,11 +383,86 @@ class Verifier:
         h = C.c_void_p()
         if store_index is None:
             self._check(self.lib.lcv_batch_upload(self.ctx, C.byref(b), C.byref(h)), "lcv_batch_upload")
-            return ResidentBatch(self, h, batch.n)
+            return ResidentBatch(self, h, batch.n, npool=int(batch.nsc_pool.shape[0]))
         six = self._store_index(batch, store_index)
         self._check(self.lib.lcv_batch_upload_stores(self.ctx, C.byref(b), ptr(six, C.c_uint32), C.byref(h)),
                     "lcv_batch_upload_stores")
-        return ResidentBatch(self, h, batch.n, stores=True)
+        return ResidentBatch(self, h, batch.n, stores=True, npool=int(batch.nsc_pool.shape[0]))
+
+    # ------------------------------------------------------------------ the producer side, batched (include/lcv.h)
+    @staticmethod
+    def _kind(kind) -> int:
+        k = UPDATE_KINDS.get(kind, kind) if isinstance(kind, str) else kind
+        return int(k)
+
+    def create_updates_resident(self, views: PackedViews, cases, kind=0, reason: Optional[np.ndarray] = None):
+        """create_light_client_update (kind 0 / "update"; 1 / "finality", 2 / "optimistic": the finality /
+        optimistic update made from it) for every row of `cases` — (n, 5) rows of (state, block, attested_state,
+        attested_block, finalized_block or -1) into `views` — on the device (lcv_create_updates_resident) ->
+        (ResidentBatch, reasons).  reasons[i]: 0, or the first failing check (lcv_producer_reason); such a row is
+        LightClientUpdate().  The batch's pool is views.committees and one all-zero row."""
+        sv, bv, com, keep = views.to_c()
+        uc, cols, n = _cases_to_c(cases)
+        r = reason if reason is not None else np.zeros(n, np.uint8)
+        h = C.c_void_p()
+        self._check(self.lib.lcv_create_updates_resident(self.ctx, C.byref(sv), views.ns, C.byref(bv), views.nb, com,
+                                                         views.ncomm, C.byref(uc), n, self._kind(kind), ptr(r),
+                                                         C.byref(h)), "lcv_create_updates_resident")
+        return ResidentBatch(self, h if n else None, n, npool=views.ncomm + 1), r
+
+    def create_updates(self, views: PackedViews, cases, kind=0, reason: Optional[np.ndarray] = None):
+        """The same, copied to the host (lcv_create_updates) -> (PackedUpdates, reasons)."""
+        sv, bv, com, keep = views.to_c()
+        uc, cols, n = _cases_to_c(cases)
+        r = reason if reason is not None else np.zeros(n, np.uint8)
+        out = PackedUpdates.empty(n, views.ncomm + 1)
+        b, keep_out = _writable_c(out)
+        self._check(self.lib.lcv_create_updates(self.ctx, C.byref(sv), views.ns, C.byref(bv), views.nb, com,
+                                                views.ncomm, C.byref(uc), n, self._kind(kind), C.byref(b), ptr(r)),
+                    "lcv_create_updates")
+        if n == 0:  # nothing ran: the pool is still the committees and the zero row
+            out.nsc_pool[:views.ncomm] = keep["committees"]
+        return out, r
+
+    def download(self, rb: ResidentBatch, rows=None) -> PackedUpdates:
+        """A resident batch back to the host (lcv_batch_download): every row, or `rows` in that order; the pool whole."""
+        if rb.npool is None:
+            raise ValueError("download: the batch's pool size is not known")
+        ix = None if rows is None else np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        out = PackedUpdates.empty(rb.n if ix is None else ix.shape[0], rb.npool)
+        if not rb.handle:
+            return out
+        b, keep = _writable_c(out)
+        self._check(self.lib.lcv_batch_download(self.ctx, rb.handle, None if ix is None else ptr(ix, C.c_uint32),
+                                                0 if ix is None else ix.shape[0], C.byref(b)), "lcv_batch_download")
+        return out
+
+    def rank_resident(self, rb: ResidentBatch) -> np.ndarray:
+        """rank() of a resident batch where it lies (lcv_rank_resident): the same kernel, the same records."""
+        out = np.zeros(rb.n, RANK_DTYPE)
+        if rb.n:
+            self._check(self.lib.lcv_rank_resident(self.ctx, rb.handle, ptr(out.view(np.uint8))), "lcv_rank_resident")
+        return out
+
+    def create_bootstraps(self, views: PackedViews, state_idx, block_idx, reason: Optional[np.ndarray] = None):
+        """create_light_client_bootstrap per (state_idx[i], block_idx[i]) (lcv_create_bootstraps) -> (beacon (n, 112),
+        execution (n, 832), exec_branch (n, 128), committee_index (n,), committee_branch (n, 160), reasons): the
+        columns bootstrap_check_batch takes, the committee as a row of views.committees (views.ncomm for a failed
+        row).  reasons: 0, 1 state before Altair, 2 state slot, 3 header root != block root, 4 missing payload."""
+        sv, bv, com, keep = views.to_c()
+        si = np.ascontiguousarray(state_idx, np.uint32).reshape(-1)
+        bi = np.ascontiguousarray(block_idx, np.uint32).reshape(-1)
+        if si.shape != bi.shape:
+            raise ValueError("need one block per state")
+        n = si.shape[0]
+        beacon, execution, branch = np.zeros((n, 112), np.uint8), np.zeros((n, 832), np.uint8), np.zeros((n, 128), np.uint8)
+        cidx, cbranch = np.zeros(n, np.uint32), np.zeros((n, 160), np.uint8)
+        r = reason if reason is not None else np.zeros(n, np.uint8)
+        self._check(self.lib.lcv_create_bootstraps(self.ctx, C.byref(sv), views.ns, C.byref(bv), views.nb, com,
+                                                   views.ncomm, ptr(si, C.c_uint32), ptr(bi, C.c_uint32), n, ptr(beacon),
+                                                   ptr(execution), ptr(branch), ptr(cidx, C.c_uint32), ptr(cbranch),
+                                                   ptr(r)), "lcv_create_bootstraps")
+        return beacon, execution, branch, cidx, cbranch, r
 
     def validate_resident(self, rb: ResidentBatch, current_slot: int, genesis_validators_root: bytes,
                           verdict: Optional[np.ndarray] = None, reason: Optional[np.ndarray] = None):

@@ -19,9 +19,12 @@ block_to_light_client_header use) and the other body fields by root.  Outputs ar
 include/lcv.h (`UpdateRow`, `BootstrapRow`; `pack_updates` -> PackedUpdates for the verifier and
 lcv.wire.encode_updates / encode_bootstrap for the wire).  The asserts are the reference's.
 
-Host code (hashlib SHA-256): deriving data is a per-block full-node task off the verifier's hot path;
-the 10^4-row synthetic batches of lcv.synth are built here too (pinned against the reference's exec'd
-full-node.md blocks: tests/golden/producer.npz).
+The per-object functions are host code (hashlib SHA-256), pinned against the reference's exec'd full-node.md
+blocks (tests/golden/producer.npz); the 10^4-row synthetic batches of lcv.synth are built through them.  A
+backfill over historic blocks (full-node.md:96, :184-188) takes the batched twins at the end of this module
+instead: `pack_views` turns lists of views into column tables once, and `create_light_client_updates` /
+`Verifier.create_updates_resident` derive every row on the device (csrc/lcv_producer.hpp), with
+the per-object functions as their yardstick.
 
 Views are treated as immutable once their roots are first used (roots are memoised per instance;
 `dataclasses.replace` makes a fresh view).
@@ -433,3 +436,88 @@ def pack_updates(rows: Sequence[UpdateRow]):
         sync_signature=col(lambda r: r.sync_committee_signature, L.SIGNATURE_BYTES),
         nsc_pool=pool_arr, nsc_index=idx,
         signature_slot=np.array([r.signature_slot for r in rows], np.uint64))
+
+
+# ------------------------------------------------------------------ the batched path (device)
+# reason code of the batched entries -> the check of create_light_client_update that fails (include/lcv.h
+# lcv_producer_reason): the exception the per-object function raises, and its text
+UPDATE_REASONS = {
+    1: (AssertionError, "compute_epoch_at_slot(attested_state.slot) >= ALTAIR_FORK_EPOCH"),
+    2: (AssertionError, "sum(block.message.body.sync_aggregate.sync_committee_bits) >= MIN_SYNC_COMMITTEE_PARTICIPANTS"),
+    3: (AssertionError, "state.slot == state.latest_block_header.slot"),
+    4: (AssertionError, "hash_tree_root(header) == hash_tree_root(block.message)"),
+    5: (AssertionError, "attested_state.slot == attested_state.latest_block_header.slot"),
+    6: (AssertionError, "hash_tree_root(attested_header) == hash_tree_root(attested_block.message) == block.message.parent_root"),
+    7: (ValueError, "a Capella-or-later block needs its execution payload"),
+    8: (ValueError, "a Capella-or-later block needs its execution payload"),
+    9: (AssertionError, "hash_tree_root(update.finalized_header.beacon) == attested_state.finalized_checkpoint.root"),
+    10: (AssertionError, "attested_state.finalized_checkpoint.root == Bytes32()"),
+}
+BOOTSTRAP_REASONS = {
+    1: (AssertionError, "compute_epoch_at_slot(state.slot) >= ALTAIR_FORK_EPOCH"),
+    2: (AssertionError, "state.slot == state.latest_block_header.slot"),
+    3: (AssertionError, "hash_tree_root(header) == hash_tree_root(block.message)"),
+    4: (ValueError, "a Capella-or-later block needs its execution payload"),
+}
+
+
+def raise_for_reason(reason: int, table=UPDATE_REASONS) -> None:
+    """Raise what the per-object function raises for a non-zero reason of the batched one."""
+    if int(reason):
+        exc, text = table[int(reason)]
+        raise exc(text)
+
+
+def pack_views(states: Sequence[BeaconStateView], blocks: Sequence[BeaconBlockView]):
+    """Lists of views -> lcv.device.PackedViews: the column tables of include/lcv.h (lcv_state_views,
+    lcv_block_views) and the pool of the states' distinct SyncCommittee values (deduplicated by content, like
+    pack_updates).  A block without a payload gets exec_kind 0, else 1 (Capella) or 2 (execution_deneb)."""
+    from .device import PackedViews
+    ns, nb = len(states), len(blocks)
+    pool: Dict[bytes, int] = {}
+    cur, nxt = np.zeros(ns, np.uint32), np.zeros(ns, np.uint32)
+    for i, s in enumerate(states):
+        cur[i] = pool.setdefault(bytes(s.current_sync_committee), len(pool))
+        nxt[i] = pool.setdefault(bytes(s.next_sync_committee), len(pool))
+    committees = np.zeros((len(pool), L.SYNC_COMMITTEE_BYTES), np.uint8)
+    for sc, k in pool.items():
+        committees[k] = np.frombuffer(sc, np.uint8)
+
+    def rows(items, get, width):
+        a = np.zeros((len(items), width), np.uint8)
+        for i, x in enumerate(items):
+            a[i] = np.frombuffer(bytes(get(x)), np.uint8)
+        return a
+    sroots = np.zeros((ns, STATE_FIELDS, 32), np.uint8)
+    for i, s in enumerate(states):
+        sroots[i] = np.asarray(s.field_roots, np.uint8).reshape(STATE_FIELDS, 32)
+    broots = np.zeros((nb, BODY_FIELDS, 32), np.uint8)
+    for i, b in enumerate(blocks):
+        broots[i] = np.asarray(b.body_roots, np.uint8).reshape(BODY_FIELDS, 32)
+    return PackedViews(
+        state_slot=np.array([s.slot for s in states], np.uint64),
+        state_header=rows(states, lambda s: s.latest_block_header, L.BEACON_BYTES),
+        state_fin_epoch=np.array([s.finalized_checkpoint_epoch for s in states], np.uint64),
+        state_fin_root=rows(states, lambda s: s.finalized_checkpoint_root, 32),
+        state_roots=sroots, state_cur=cur, state_nxt=nxt,
+        block_slot=np.array([b.slot for b in blocks], np.uint64),
+        block_proposer=np.array([b.proposer_index for b in blocks], np.uint64),
+        block_parent=rows(blocks, lambda b: b.parent_root, 32),
+        block_state_root=rows(blocks, lambda b: b.state_root, 32),
+        block_bits=rows(blocks, lambda b: b.sync_committee_bits, L.BITS_BYTES),
+        block_sig=rows(blocks, lambda b: b.sync_committee_signature, L.SIGNATURE_BYTES),
+        block_exec=rows(blocks, lambda b: b.execution if b.execution is not None else bytes(L.EXEC_BYTES), L.EXEC_BYTES),
+        block_kind=np.array([0 if b.execution is None else 2 if b.execution_deneb else 1 for b in blocks], np.uint8),
+        block_roots=broots, committees=committees)
+
+
+def create_light_client_updates(states: Sequence[BeaconStateView], blocks: Sequence[BeaconBlockView], cases,
+                                kind: str = "update", verifier=None):
+    """The batched twin of create_light_client_update (kind "update"), create_light_client_finality_update
+    ("finality") and create_light_client_optimistic_update ("optimistic") on the device: `cases` are rows of
+    (state, block, attested_state, attested_block, finalized_block or -1) into the two lists -> (PackedUpdates,
+    reasons).  reasons[i] is 0, or names the check that fails for row i (raise_for_reason raises what the
+    per-object function raises); such a row is UpdateRow().  The fork epochs and periods are the verifier's."""
+    from . import runtime
+    v = verifier if verifier is not None else runtime.default_verifier()
+    return v.create_updates(pack_views(states, blocks), cases, kind)

@@ -43,7 +43,8 @@ from . import config
 from . import layout as L
 from . import runtime
 from ._native import FOLD_MAX_ROWS, STORE_NEXT_UNKNOWN
-from .device import (FoldState, PackedUpdates, RANK_DTYPE, RANK_FIN, RANK_FIN_SC, RANK_REL_SC, RANK_SUPER, Verifier)
+from .device import (FoldState, PackedUpdates, RANK_DTYPE, RANK_FIN, RANK_FIN_SC, RANK_REL_SC, RANK_SUPER, ResidentBatch,
+                     Verifier)
 from .sync_protocol import REASONS, pack_updates, validate_light_client_updates, validate_under_store_keys
 
 # SLOTS_PER_EPOCH * EPOCHS_PER_SYNC_COMMITTEE_PERIOD and UPDATE_TIMEOUT (sync-protocol.md:89) come from the
@@ -489,13 +490,17 @@ def rank_updates(updates, verifier: Optional[Verifier] = None) -> np.ndarray:
     """The device's rank records (lcv.device.RANK_DTYPE, one per update) of update objects or a PackedUpdates
     batch: is_better_update(a, b) iff (key0_a, -attested_a, -signature_a) > (key0_b, -attested_b, -signature_b)."""
     v = verifier if verifier is not None else runtime.default_verifier()
+    if isinstance(updates, ResidentBatch):  # a device-resident batch is ranked where it lies
+        return v.rank_resident(updates)
     return v.rank(updates if isinstance(updates, PackedUpdates) else pack_updates(updates))
 
 
 def best_update_per_period(updates, verifier: Optional[Verifier] = None) -> dict:
     """full-node.md:184-187: the best LightClientUpdate (according to is_better_update) for each sync committee
     period -> {period: row}.  A row belongs to the period of its attested header; rows whose signature_slot lies
-    in another period are left out.  Per period the first arg-max of the device's rank records (one lexsort)."""
+    in another period are left out.  Per period the first arg-max of the device's rank records (one lexsort).
+    `updates` may be a ResidentBatch (Verifier.create_updates_resident, upload): it is ranked on the device
+    without a copy, and the rows are its rows (Verifier.download(rb, rows) fetches the winners)."""
     v = verifier if verifier is not None else runtime.default_verifier()
     rec = rank_updates(updates, v)
     spp = v.config.SLOTS_PER_PERIOD
