@@ -93,6 +93,20 @@ def test_fast_aggregate_verify_dropin(gpu_verifier):
     assert not fav(pks[:599], msg, sig600)
     sig513 = B.sign(sum(sks[:513]) % B.R, msg)
     assert fav(pks[:513], msg, sig513)
+    # 1,024 keys = two full 512-key slices whose aggregates item_agg_fold adds: the second slice the negation of
+    # the first (the sum is the identity: False), and a second slice with the first one's aggregate (the fold adds
+    # a point to itself: its doubling branch)
+    first = pks[:512]
+    negated = [B.g1_compress(B.g1_neg(B.g1_decompress(p))) for p in first]
+    assert B.aggregate_pubkeys(first + negated) is None
+    assert not fav(first + negated, msg, sig3)
+    twice = first + first[::-1]
+    agg = B.aggregate_pubkeys(twice)
+    assert agg == B.g1_add(B.aggregate_pubkeys(first), B.aggregate_pubkeys(first))
+    sig_twice = B.sign(2 * sum(sks[:512]) % B.R, msg)
+    assert B.core_verify_point(agg, msg, sig_twice)
+    assert fav(twice, msg, sig_twice)
+    assert not fav(twice, msg, B.sign(sum(sks[:512]) % B.R, msg))
     # a message that is not a 32-byte signing root (expand_message_xmd streamed on the device)
     for m in (b"", b"abc", rng.randbytes(31), rng.randbytes(33), rng.randbytes(200)):
         s = B.sign(sum(sks[:2]) % B.R, m)
