@@ -326,6 +326,54 @@ int lcv_set_latency_mode(lcv_ctx* ctx, uint64_t max_rows);
  * [3] one-lane-per-item SSWU / signature launches, [4..7] items per wave of the last batch-engine launch of
  * the line walk, Miller accumulation, final exponentiation, hash_to_G2 tail (0 = not launched) */
 int lcv_debug_engine_log(lcv_ctx* ctx, uint64_t* out8, int reset);
+/* ---- Deduplicated signatures: each distinct sync-committee signature of a chunk checked once.  A light-client
+ * server relays the same gossip messages and by-range responses to many clients: a finality update sent to 10^4
+ * clients is 10^4 rows with the same attested header, signature_slot, sync_committee_bits and signature, which
+ * differ only in store_index — and almost all of their stores hold the same current committee.  lcv_set_dedup(on)
+ * (default 0: every call launches exactly what it launches without this mode) makes the BLS half of validation —
+ * signing root, signature decode and subgroup check, hash_to_G2, masked aggregation, both Miller walks, final
+ * exponentiation — run once per distinct BLS ITEM of a chunk; every row takes its verdict from its item.
+ * The BLS item of a row is the tuple (attested beacon header 112 B, signature_slot, sync_bits 64 B,
+ * sync_signature 96 B, the committee row the signature is checked against).  Those stages read nothing else of a
+ * row (configuration and genesis_validators_root are per call), so rows with equal tuples have bytewise-equal
+ * inputs to every BLS stage and bit-identical results.  Rows are merged only on a full compare of the tuple bytes,
+ * never on a hash alone; rows whose tuples differ are never merged; and being conservative is allowed: two rows of
+ * the committee table with equal content count as different committees.  The pre-checks (slots, periods,
+ * relevance, Merkle branches, committee equality) depend on the row's own store and run for every row, as do the
+ * rank records of the fold calls; verdict and reason bytes are per row, in the same places, so the folds,
+ * lcv_slot_wait*, lcv_slot_allgather and lcv_validate_sharded work unchanged, and results equal the mode-off
+ * results byte for byte.
+ * Host side, O(n): when host columns enter the library with the mode on — lcv_validate_updates, _updates_stores,
+ * _async, _stores_async, the four _fold entries, lcv_batch_upload and lcv_batch_upload_stores — every row gets a
+ * store-independent class (equal attested beacon, signature_slot, bits, signature: a hash table, full compare on a
+ * hash match).  At validate time, per chunk, the class is refined by the committee row the signature is checked
+ * against — nothing to add for lcv_set_store (the choice depends on signature_slot only, which is in the class); for
+ * a table batch, the row item_pre_table chooses under the store table of that call (a next committee that is not
+ * known is a value like any other) — which gives rep[row] = item, urow[item] = its first row (ascending: items are
+ * numbered by first appearance) and m, the number of items.  A staged host batch carries the two columns in its
+ * one host-to-device copy; a resident batch keeps its class column on the host (4 B per row; a table batch also its
+ * store_index and signature_slot columns, 12 B per row, which the committee choice reads) and each validation
+ * sends the chunk's two columns in one small copy each.  A batch uploaded while the mode was off has no class column
+ * and is validated without deduplication.  m is known before anything is launched, and launch sizes, items per
+ * wave and the engine choice (lcv_set_latency_mode) go by m: 10^4 rows holding <= 64 distinct items run on the
+ * fan engine.
+ * Device side: after the pre-checks a gather kernel writes the items' four columns and committee ids into compact
+ * scratch of the slot (284 B per item and 8 B per row, allocated by the slot's first deduplicated call), the BLS
+ * stages run unchanged over those m items, and the verdict kernel reads the BLS flags of row i at rep[i].
+ * lcv_set_dedup(on) together with a multi-stream pipeline (lcv_set_pipeline streams > 1) is refused with
+ * LCV_EINVAL, by whichever call comes second: sliced chains would need a grouping per slice.
+ * lcv_last_dedup reports the rows and items of the last batch enqueued on work-space slot `slot` (synchronous
+ * calls: slot 0, summed over the batch's chunks); items == rows with the mode off or for a batch without a class
+ * column (and in the CPU-baseline build, whose direct path runs every row).
+ * lcv_debug_dedup_hash_bits is a test hook: the host hash is truncated to `bits` bits (default 64; 0 makes every
+ * row collide, so that only the full compare separates classes).
+ * Out of scope: resident batches made on the device (lcv_create_updates_resident: no host bytes to class; they run
+ * without deduplication); merging across chunks or across batches in flight; lcv_fast_aggregate_verify_batch;
+ * merging committee-table rows of equal content; skipping the BLS work of items all of whose rows failed a
+ * pre-check. */
+int lcv_set_dedup(lcv_ctx* ctx, int on);
+int lcv_last_dedup(lcv_ctx* ctx, int slot, uint64_t* rows, uint64_t* items);
+int lcv_debug_dedup_hash_bits(lcv_ctx* ctx, int bits);
 /* kernel time of the last validate call: total and per stage (ms); names via lcv_stage_name
  * (stage times are recorded by the serial shape only: zero under a multi-stream pipeline) */
 int lcv_last_timings(lcv_ctx* ctx, float* ms_out, int max_stages, int* nstages);

@@ -6,7 +6,9 @@
 enum { LCV_SLOTS = 8 };
 // lcv_set_latency_mode's default: batches of at most this many rows run the SOP programs on the fan engine
 enum : unsigned long long { LCV_FAN_MAX_DEFAULT = 64 };
-enum { EV_START = 0, EV_PRE, EV_H2C, EV_SIDE, EV_H2D, EV_COUNT };  // EV_H2D: the slot's staged batch has left host memory
+// EV_H2D: the slot's staged batch has left host memory.  Deduplicated chunks (lcv_set_dedup): EV_PLAN, a resident
+// chunk's grouping has left the slot's pinned buffer; EV_GATHER, the items' compact columns are written
+enum { EV_START = 0, EV_PRE, EV_H2C, EV_SIDE, EV_H2D, EV_PLAN, EV_GATHER, EV_COUNT };
 #include <stddef.h>
 #include <stdint.h>
 

@@ -15,6 +15,8 @@
 #include "lcv_items.hpp"
 #include "lcv_fold.hpp"
 #include "lcv_producer.hpp"
+#include "lcv_dedup.hpp"
+#include "lcv_dedup_plan.hpp"
 #include "lcv_sop.hpp"
 #include "lcv_build_id.h"  // LCV_BUILD_ID (Makefile: tools/build_id.py over the sources)
 
@@ -23,11 +25,12 @@ using namespace lcv;
 // One mark per kernel launch (marks never nest, so the host simulation's op counter attributes every
 // operation to exactly one stage, and a HIP event pair brackets exactly one kernel on its stream).
 enum { ST_NSC = 0, ST_PRE, ST_H2C_MAP, ST_H2C, ST_SIG, ST_AGG, ST_MILLER, ST_FEXP, ST_VERDICT, ST_SETUP,
-       ST_LINES, ST_LINES_SIG, ST_SIGROOT, ST_RANK, ST_FOLD, ST_PRODUCE_VIEWS, ST_PRODUCE_ROWS, ST_COUNT };
+       ST_LINES, ST_LINES_SIG, ST_SIGROOT, ST_RANK, ST_FOLD, ST_PRODUCE_VIEWS, ST_PRODUCE_ROWS, ST_DEDUP, ST_COUNT };
 static const char* kStageNames[ST_COUNT] = {"nsc_htr", "pre_checks", "h2c_sswu", "hash_to_g2", "sig_decode",
                                             "g1_aggregate", "miller_loop", "final_exp", "verdict",
                                             "setup", "miller_lines", "miller_lines_sig", "signing_root",
-                                            "store_rank", "store_fold", "produce_views", "produce_rows"};
+                                            "store_rank", "store_fold", "produce_views", "produce_rows",
+                                            "dedup_gather"};
 
 struct CommitteeBufs {
   uint8_t* raw = nullptr;
@@ -48,6 +51,16 @@ struct lcv_dbatch {
   // column's largest entry is recorded on the host when the column is taken, so that every later validation can
   // check it against the table of that moment in O(1), before any launch
   uint32_t max_store = 0;
+  // lcv_set_dedup.  A resident batch uploaded while the mode was on keeps its class column on the host (cls[i]: the
+  // first row whose BLS inputs equal row i's; empty: uploaded with the mode off, validated without deduplication), and
+  // a table batch also the two columns the committee choice of a row depends on, so that every validation can group
+  // the rows under the table of that moment.  A staged host batch brings its grouping along instead (batch_cols
+  // columns 18, 19; plan_m items, 0: none)
+  std::vector<uint32_t> cls, h_store;
+  std::vector<uint64_t> h_sig_slot;
+  const uint32_t* plan_rep = nullptr;
+  const uint32_t* plan_urow = nullptr;
+  uint32_t plan_m = 0;
 };
 
 // host-input serving path (lcv_validate_async): per work-space slot, a pinned host staging copy of the
@@ -149,6 +162,23 @@ struct lcv_ctx {
   // knobs, set from the environment at lcv_init (LCV_SOP_ITEMS_LINES / _ACC / _FEXP / _H2C): fewer items
   // per wave = more waves per SIMD for the same batch (DESIGN §7)
   uint32_t sop_items[4] = {0, 0, 0, 0};
+  // deduplicated BLS half (lcv_set_dedup, off by default; include/lcv.h "Deduplicated signatures"): per work-space
+  // slot the items' compact columns and a resident chunk's grouping (ensure_dedup: an allocation of its own, made by
+  // the slot's first deduplicated call), the pinned buffer that grouping is copied from, and the rows / items of
+  // the slot's last batch (lcv_last_dedup).  dd_*: the host's scratch of the call in progress.  tab_*: the store
+  // table's columns as the device holds them, for the host's committee choice (dedup_comm_rows)
+  bool dedup = false;
+  uint32_t dedup_hash_bits = 64;  // lcv_debug_dedup_hash_bits
+  void* dedup_mem[LCV_SLOTS] = {};
+  size_t dedup_cap[LCV_SLOTS] = {};
+  DedupDev Dslot[LCV_SLOTS] = {};
+  uint8_t* plan_pin[LCV_SLOTS] = {};
+  size_t plan_pin_cap[LCV_SLOTS] = {};
+  uint64_t dd_rows[LCV_SLOTS] = {}, dd_items[LCV_SLOTS] = {};
+  DedupTable dd_table;
+  std::vector<uint32_t> dd_cls, dd_comm, dd_rep, dd_urow;
+  std::vector<uint64_t> tab_fin;
+  std::vector<uint32_t> tab_cur, tab_next;
 };
 
 static uint32_t host_be32(const uint8_t* p) {
@@ -267,6 +297,29 @@ static int ensure_work(lcv_ctx* ctx, size_t cap, size_t pool_cap, int slot = 0) 
   ctx->work_cap[slot] = C;
   ctx->work_pool_cap[slot] = Pc;
   ctx->W = W;
+  return LCV_OK;
+}
+
+// the deduplication scratch of `slot` for chunks of up to `cap` rows (lcv_set_dedup): 284 bytes per item (the four
+// compact batch columns and the compact committee ids) and 8 per row (a resident chunk's rep / urow), as large as the
+// slot's work space at least; allocated by the slot's first deduplicated call (be_free waits for the streams)
+static int ensure_dedup(lcv_ctx* ctx, size_t cap, int slot) {
+  if (cap < ctx->work_cap[slot]) cap = ctx->work_cap[slot];
+  if (cap <= ctx->dedup_cap[slot] && ctx->dedup_mem[slot]) return LCV_OK;
+  if (ctx->dedup_mem[slot]) be_free(ctx, ctx->dedup_mem[slot]);
+  ctx->dedup_mem[slot] = nullptr;
+  ctx->dedup_cap[slot] = 0;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
+  const size_t o_beacon = take((size_t)K_BEACON * cap), o_slot = take(8 * cap), o_bits = take(64 * cap),
+               o_sig = take(96 * cap), o_comm = take(4 * cap), o_rep = take(4 * cap), o_urow = take(4 * cap);
+  void* mem = nullptr;
+  LCV_TRY(be_alloc(ctx, &mem, off));
+  uint8_t* m = (uint8_t*)mem;
+  ctx->Dslot[slot] = DedupDev{m + o_beacon, (uint64_t*)(m + o_slot), m + o_bits, m + o_sig, (uint32_t*)(m + o_comm),
+                              (uint32_t*)(m + o_rep), (uint32_t*)(m + o_urow)};
+  ctx->dedup_mem[slot] = mem;
+  ctx->dedup_cap[slot] = cap;
   return LCV_OK;
 }
 
@@ -544,6 +597,83 @@ static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint3
   return LCV_OK;
 }
 
+// run_bls for a deduplicated chunk of validate (lcv_set_dedup): the grouping of its n rows into R.m items (rep, urow:
+// device pointers) is known, and m sizes every BLS launch and picks the engine.
+//   side: [HTR(next_sync_committee)] item_pre over the n rows [rank records], F_dedup_gather -> EV_GATHER, then over the
+//         m items: signature decode, [masked aggregation] -> EV_PRE, (after EV_H2C) the signature's line walk -> EV_SIDE
+//   main: (after EV_GATHER) over the m items: signing root, SSWU maps, hash_to_G2 tail, (after EV_PRE) [masked
+//         aggregation] -> EV_H2C, the message's line walk, (after EV_SIDE) Miller accumulation, final exponentiation;
+//         F_verdict_dedup over the n rows
+// Everything on the BLS side follows the gather: its stages read the items' compact columns (Bu) and the compact
+// committee ids (Wu.comm_id), which the gather takes from what item_pre wrote.
+struct DedupRun { DedupDev D; const uint32_t* rep; const uint32_t* urow; uint32_t m; };
+static int run_bls_dedup(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint32_t n, const Params& P,
+                         const BatchDev* nsc, const StoreDev* S, bool rank, const DedupRun& R) {
+  const Work& W = ctx->W;
+  const uint32_t m = R.m;
+  BatchDev Bu = B;
+  Bu.att_beacon = R.D.att_beacon; Bu.sig_slot = R.D.sig_slot; Bu.bits = R.D.bits; Bu.sig = R.D.sig;
+  Bu.n = m;
+  Work Wu = W;
+  Wu.comm_id = R.D.comm_id;
+  LCV_TRY(be_mark(ctx, EV_START, 0));
+  LCV_TRY(be_wait(ctx, 1, EV_START));
+  be_use_stream(ctx, 1);
+  if (nsc) {
+    be_stage_begin(ctx, ST_NSC);
+    LCV_TRY(be_launch_team(ctx, F_nsc_team{*nsc, C, W}, nsc->npool));
+    be_stage_end(ctx, ST_NSC);
+  }
+  be_stage_begin(ctx, ST_PRE);
+  LCV_TRY(pre_stage(ctx, B, C, P, S, W, n));
+  be_stage_end(ctx, ST_PRE);
+  if (rank) LCV_TRY(rank_stage(ctx, B, P, W, n));
+  be_stage_begin(ctx, ST_DEDUP);
+  LCV_TRY(be_launch_team(ctx, F_dedup_gather{B, W, R.urow, R.D}, m));
+  be_stage_end(ctx, ST_DEDUP);
+  LCV_TRY(be_mark(ctx, EV_GATHER, 1));
+  be_stage_begin(ctx, ST_SIG);
+  LCV_TRY(launch_items(ctx, F_sig{Bu, Wu}, m, m));
+  be_stage_end(ctx, ST_SIG);
+  const bool agg_side = nsc == nullptr || nsc->npool < 64;  // (run_bls)
+  if (agg_side) LCV_TRY(agg_stage(ctx, Bu, C, Wu, m, 0));
+  LCV_TRY(be_mark(ctx, EV_PRE, 1));
+  be_use_stream(ctx, 0);
+  LCV_TRY(be_wait(ctx, 0, EV_GATHER));
+  be_stage_begin(ctx, ST_SIGROOT);
+  LCV_TRY(be_launch(ctx, F_sigroot{Bu, P, Wu}, m));
+  be_stage_end(ctx, ST_SIGROOT);
+  be_stage_begin(ctx, ST_H2C_MAP);
+  LCV_TRY(launch_items(ctx, F_h2c_map{Wu}, 2 * m, m));
+  be_stage_end(ctx, ST_H2C_MAP);
+  be_stage_begin(ctx, ST_H2C);
+  LCV_TRY(launch_sop(ctx, F_sop_h2c{Wu, ctx->sop_h2c}, m, m));
+  be_stage_end(ctx, ST_H2C);
+  LCV_TRY(be_wait(ctx, 0, EV_PRE));
+  if (!agg_side) LCV_TRY(agg_stage(ctx, Bu, C, Wu, m, 0));
+  if (fused_miller(ctx, m)) {
+    LCV_TRY(fused_pairing(ctx, Wu, m));
+  } else {
+    LCV_TRY(be_mark(ctx, EV_H2C, 0));
+    be_use_stream(ctx, 1);
+    LCV_TRY(be_wait(ctx, 1, EV_H2C));
+    be_stage_begin(ctx, ST_LINES_SIG);
+    LCV_TRY(launch_sop(ctx, F_sop_lines{Wu, ctx->sop_lines, 1u}, m, m));
+    be_stage_end(ctx, ST_LINES_SIG);
+    LCV_TRY(be_mark(ctx, EV_SIDE, 1));
+    be_use_stream(ctx, 0);
+    be_stage_begin(ctx, ST_LINES);
+    LCV_TRY(launch_sop(ctx, F_sop_lines{Wu, ctx->sop_lines, 2u}, m, m));
+    be_stage_end(ctx, ST_LINES);
+    LCV_TRY(be_wait(ctx, 0, EV_SIDE));
+    LCV_TRY(pairing_tail(ctx, Wu, m));
+  }
+  be_stage_begin(ctx, ST_VERDICT);
+  LCV_TRY(be_launch(ctx, F_verdict_dedup{W, R.rep}, n));
+  be_stage_end(ctx, ST_VERDICT);
+  return LCV_OK;
+}
+
 // The whole per-update chain (pre-checks, signature decode + subgroup check, hash_to_G2, masked
 // aggregation, Miller loop, final exponentiation, verdict) for one slice, on the current stream.
 // Slices are independent, so validate_impl runs slice k on stream k % pipe_streams: the kernels of
@@ -606,6 +736,8 @@ void lcv_destroy(lcv_ctx* ctx) {
   for (int k = 0; k < LCV_SLOTS; ++k) {
     if (ctx->work_mem[k]) be_free(ctx, ctx->work_mem[k]);
     if (ctx->seg_mem[k]) be_free(ctx, ctx->seg_mem[k]);
+    if (ctx->dedup_mem[k]) be_free(ctx, ctx->dedup_mem[k]);
+    if (ctx->plan_pin[k]) be_host_free(ctx, ctx->plan_pin[k]);
   }
   if (ctx->sop_mem) be_free(ctx, ctx->sop_mem);
   if (ctx->comm_buf) be_free(ctx, ctx->comm_buf);
@@ -644,19 +776,23 @@ int lcv_set_store(lcv_ctx* ctx, uint64_t finalized_slot, const uint8_t* cur, con
 // the 13 columns of a packed batch, and the per-update store-table rows of lcv_validate_updates_stores (column
 // 13: empty otherwise), each at a 256-byte aligned offset of one device allocation.  Columns 14-17 (a segmented
 // fold, lcv_validate_stores_fold: empty otherwise) are the grouping of the rows by store and the present stores'
-// fold states (FoldSegs: store, off, row, in), which so travel with the batch in its one copy
-enum { BATCH_COLS = 18 };
+// fold states (FoldSegs: store, off, row, in), which so travel with the batch in its one copy.  Columns 18, 19 (a
+// staged batch under lcv_set_dedup: empty otherwise) are the grouping of its rows into BLS items (DedupCols: rep, urow)
+enum { BATCH_COLS = 20 };
+struct DedupCols { const uint32_t* rep; const uint32_t* urow; uint32_t m; };
 struct BatchCols {
   const void* src[BATCH_COLS];
   size_t bytes[BATCH_COLS], off[BATCH_COLS];
   size_t total = 0, n = 0, np = 0;
 };
 
-// the layout alone (no host sources): n rows, np pool rows, with a store_index column or not, ng fold segments
-static void batch_layout(BatchCols& c, size_t n, size_t np, bool stores, size_t ng) {
+// the layout alone (no host sources): n rows, np pool rows, with a store_index column or not, ng fold segments,
+// nd BLS items (0: no grouping)
+static void batch_layout(BatchCols& c, size_t n, size_t np, bool stores, size_t ng, size_t nd = 0) {
   const size_t bytes[BATCH_COLS] = {112 * n, 832 * n, 128 * n, 112 * n, 832 * n, 128 * n, (size_t)K_SC * np, 4 * n,
                                     160 * n, 192 * n, 64 * n, 96 * n, 8 * n, stores ? 4 * n : 0,
-                                    4 * ng, ng ? 4 * (ng + 1) : 0, ng ? 4 * n : 0, sizeof(FoldState) * ng};
+                                    4 * ng, ng ? 4 * (ng + 1) : 0, ng ? 4 * n : 0, sizeof(FoldState) * ng,
+                                    nd ? 4 * n : 0, 4 * nd};
   c.total = 0;
   for (int k = 0; k < BATCH_COLS; ++k) {
     c.src[k] = nullptr;
@@ -669,7 +805,8 @@ static void batch_layout(BatchCols& c, size_t n, size_t np, bool stores, size_t 
 }
 
 static int batch_cols(lcv_ctx* ctx, const lcv_update_batch* hb, BatchCols& c, const char* who,
-                      const uint32_t* store_index = nullptr, const FoldSegs* segs = nullptr) {
+                      const uint32_t* store_index = nullptr, const FoldSegs* segs = nullptr,
+                      const DedupCols* dd = nullptr) {
   const size_t n = hb->n, np = hb->npool, ng = segs ? segs->nseg : 0;
   if (n == 0 || np == 0 || n > 0xffffffffull || np > 0xffffffffull)
     return fail(ctx, LCV_EINVAL, std::string(who) + ": need 0 < n, 0 < npool < 2^32");
@@ -678,10 +815,11 @@ static int batch_cols(lcv_ctx* ctx, const lcv_update_batch* hb, BatchCols& c, co
                          hb->nsc_pool, hb->nsc_index, hb->nsc_branch, hb->finality_branch,
                          hb->sync_bits, hb->sync_signature, hb->signature_slot, store_index,
                          ng ? segs->store.data() : nullptr, ng ? segs->off.data() : nullptr,
-                         ng ? segs->row.data() : nullptr, ng ? segs->in.data() : nullptr};
+                         ng ? segs->row.data() : nullptr, ng ? segs->in.data() : nullptr,
+                         dd ? dd->rep : nullptr, dd ? dd->urow : nullptr};
   for (int k = 0; k < 13; ++k)
     if (!src[k]) return fail(ctx, LCV_EINVAL, std::string(who) + ": null column");
-  batch_layout(c, n, np, store_index != nullptr, ng);
+  batch_layout(c, n, np, store_index != nullptr, ng, dd ? dd->m : 0);
   for (int k = 0; k < BATCH_COLS; ++k) c.src[k] = src[k];
   for (size_t i = 0; i < n; ++i)
     if (hb->nsc_index[i] >= np) return fail(ctx, LCV_EINVAL, std::string(who) + ": nsc_index out of range");
@@ -707,6 +845,91 @@ static void bind_batch(lcv_dbatch* db, uint8_t* m, const BatchCols& c) {
     for (size_t i = 0; i < c.n; ++i)
       if (ix[i] > db->max_store) db->max_store = ix[i];
   }
+  // a staged batch's grouping into BLS items (lcv_set_dedup), where it was staged
+  db->plan_rep = c.bytes[19] ? (const uint32_t*)(m + c.off[18]) : nullptr;
+  db->plan_urow = c.bytes[19] ? (const uint32_t*)(m + c.off[19]) : nullptr;
+  db->plan_m = (uint32_t)(c.bytes[19] / 4);
+}
+
+// ---- deduplicated BLS half, host side (lcv_set_dedup; lcv_dedup_plan.hpp).  The CPU-baseline build's direct branch
+// of run_bls runs every row, so there the mode groups nothing (lcv_last_dedup: items == rows)
+#if defined(LCV_CPU_FAST)
+static bool dedup_on(const lcv_ctx*) { return false; }
+#else
+static bool dedup_on(const lcv_ctx* ctx) { return ctx->dedup; }
+#endif
+// comm[i] = the committee-table row the signature of row i is checked against, as item_pre_table chooses it under
+// the store table that is set (every store_index has been checked against it)
+static void dedup_comm_rows(const lcv_ctx* ctx, const uint32_t* store_index, const uint64_t* sig_slot, size_t n, uint32_t* comm) {
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t s = store_index[i], cur = ctx->tab_cur[s];
+    comm[i] = sig_committee_row(period_of_slot(sig_slot[i], ctx->cfg), period_of_slot(ctx->tab_fin[s], ctx->cfg), cur,
+                                table_next_row(cur, ctx->tab_next[s]));
+  }
+}
+// the grouping of a one-chunk host batch about to be staged: classes, then items by (class, committee row), into
+// the context's scratch; `dd` then names the two columns that travel with the batch.  Off (dd.m == 0) while the mode
+// is, and for a batch batch_cols is about to refuse
+static int dedup_stage(lcv_ctx* ctx, const char* who, const lcv_update_batch* hb, const uint32_t* store_index, DedupCols& dd) {
+  dd = DedupCols{nullptr, nullptr, 0};
+  if (!dedup_on(ctx) || hb->n == 0 || hb->n > ctx->chunk || !hb->attested.beacon || !hb->signature_slot || !hb->sync_bits ||
+      !hb->sync_signature)
+    return LCV_OK;
+  const uint32_t n = (uint32_t)hb->n;
+  try {
+    ctx->dd_cls.resize(n);
+    ctx->dd_rep.resize(n);
+    ctx->dd_urow.resize(n);
+    if (store_index) ctx->dd_comm.resize(n);
+    dedup_classes(hb->attested.beacon, hb->signature_slot, hb->sync_bits, hb->sync_signature, n, ctx->dedup_hash_bits,
+                  ctx->dd_cls.data(), ctx->dd_table);
+    if (store_index) dedup_comm_rows(ctx, store_index, hb->signature_slot, n, ctx->dd_comm.data());
+    dd.m = dedup_plan(ctx->dd_cls.data(), store_index ? ctx->dd_comm.data() : nullptr, n, ctx->dedup_hash_bits,
+                      ctx->dd_rep.data(), ctx->dd_urow.data(), ctx->dd_table);
+  } catch (...) {  // an extern "C" entry point must not let an exception out
+    return fail(ctx, LCV_ENOMEM, std::string(who) + ": out of host memory");
+  }
+  dd.rep = ctx->dd_rep.data();
+  dd.urow = ctx->dd_urow.data();
+  return LCV_OK;
+}
+// the grouping of rows [base, base + n) of a batch for this validation, and the slot's scratch: a staged batch
+// brought it along; a resident batch's chunk is grouped here from the columns it keeps on the host, under the table
+// of this call, and the two columns go to the device through the slot's pinned buffer in one small copy each
+extern "C" {
+static int host_alloc_grow(lcv_ctx* ctx, uint8_t** p, size_t* cap, size_t bytes);
+}
+static int dedup_chunk(lcv_ctx* ctx, const lcv_dbatch* db, int slot, size_t base, uint32_t n, DedupRun& R) {
+  LCV_TRY(ensure_dedup(ctx, n, slot));
+  be_set_slot(ctx, slot);
+  R.D = ctx->Dslot[slot];
+  if (db->plan_m) {
+    R.rep = db->plan_rep;
+    R.urow = db->plan_urow;
+    R.m = db->plan_m;
+    return LCV_OK;
+  }
+  LCV_TRY(be_wait_event(ctx, EV_PLAN));  // the slot's previous grouping has left the pinned buffer
+  LCV_TRY(host_alloc_grow(ctx, &ctx->plan_pin[slot], &ctx->plan_pin_cap[slot], 8 * (size_t)n));
+  uint32_t* rep = (uint32_t*)ctx->plan_pin[slot];
+  uint32_t* urow = rep + n;
+  const bool table = !db->h_store.empty();
+  try {
+    if (table) {
+      ctx->dd_comm.resize(n);
+      dedup_comm_rows(ctx, db->h_store.data() + base, db->h_sig_slot.data() + base, n, ctx->dd_comm.data());
+    }
+    R.m = dedup_plan(db->cls.data() + base, table ? ctx->dd_comm.data() : nullptr, n, ctx->dedup_hash_bits, rep, urow,
+                     ctx->dd_table);
+  } catch (...) {
+    return fail(ctx, LCV_ENOMEM, "validate: out of host memory");
+  }
+  LCV_TRY(be_h2d(ctx, R.D.rep, rep, 4 * (size_t)n));
+  LCV_TRY(be_h2d(ctx, R.D.urow, urow, 4 * (size_t)R.m));
+  LCV_TRY(be_mark(ctx, EV_PLAN, 0));
+  R.rep = R.D.rep;
+  R.urow = R.D.urow;
+  return LCV_OK;
 }
 
 extern "C" {
@@ -718,6 +941,20 @@ static int batch_upload(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t
   LCV_TRY(batch_cols(ctx, hb, c, "lcv_batch_upload", store_index));
   lcv_dbatch* db = new (std::nothrow) lcv_dbatch();
   if (!db) return LCV_ENOMEM;
+  if (dedup_on(ctx)) {  // the class column, and what a table batch's committee choice reads, stay on the host
+    try {
+      db->cls.resize(c.n);
+      dedup_classes(hb->attested.beacon, hb->signature_slot, hb->sync_bits, hb->sync_signature, (uint32_t)c.n,
+                    ctx->dedup_hash_bits, db->cls.data(), ctx->dd_table);
+      if (store_index) {
+        db->h_store.assign(store_index, store_index + c.n);
+        db->h_sig_slot.assign(hb->signature_slot, hb->signature_slot + c.n);
+      }
+    } catch (...) {  // an extern "C" entry point must not let an exception out
+      delete db;
+      return fail(ctx, LCV_ENOMEM, "lcv_batch_upload: out of host memory");
+    }
+  }
   int rc = be_alloc(ctx, &db->mem, c.total);
   if (rc != LCV_OK) { delete db; return rc; }
   uint8_t* m = (uint8_t*)db->mem;
@@ -865,6 +1102,23 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
   const int ns = ctx->pipe_streams < 4 ? ctx->pipe_streams : 4;  // lcv_set_pipeline: min(streams, 4)
   const bool piped = !async && ns > 1 && ctx->pipe_chunks > 1;
   bool pinned_out = false;
+  // lcv_set_dedup: a chunk of a batch that has its grouping (staged) or its class column (resident) runs the BLS
+  // half once per distinct item (run_bls_dedup); otherwise, and always with the mode off, run_bls as ever.  The
+  // rows and items of the batch are summed over its chunks for lcv_last_dedup (synchronous calls: slot 0)
+  const bool dedup = dedup_on(ctx) && !piped && (db->plan_m > 0 || !db->cls.empty());
+  const int dd_slot = async ? slot : 0;
+  ctx->dd_rows[dd_slot] = ctx->dd_items[dd_slot] = 0;
+  auto bls_chunk = [&](int sl, const BatchDev& Bc, size_t base, uint32_t m, const BatchDev* nsc, bool rank) -> int {
+    ctx->dd_rows[dd_slot] += m;
+    if (!dedup) {
+      ctx->dd_items[dd_slot] += m;
+      return run_bls(ctx, Bc, C, m, 0, &P, nsc, S, rank);
+    }
+    DedupRun R;
+    LCV_TRY(dedup_chunk(ctx, db, sl, base, m, R));
+    ctx->dd_items[dd_slot] += R.m;
+    return run_bls_dedup(ctx, Bc, C, m, P, nsc, S, rank, R);
+  };
   auto body = [&]() -> int {
     if (piped) {  // sliced chains on `ns` streams (lcv_set_pipeline): the committee roots come first
       be_stage_begin(ctx, ST_NSC);
@@ -893,7 +1147,7 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
         const size_t base = c * cap;
         const uint32_t m = (uint32_t)((n - base) < cap ? (n - base) : cap);
         // every slot's first chunk also hashes the committee pool into that slot's work space
-        LCV_TRY(run_bls(ctx, chunk_view(db->B, base, m), C, m, 0, &P, c < (size_t)LCV_SLOTS ? &db->B : nullptr, S));
+        LCV_TRY(bls_chunk(sl, chunk_view(db->B, base, m), base, m, c < (size_t)LCV_SLOTS ? &db->B : nullptr, false));
       }
       for (size_t c = nchunks > (size_t)LCV_SLOTS ? nchunks - LCV_SLOTS : 0; c < nchunks; ++c) LCV_TRY(finish(c));
       LCV_TRY(be_sync(ctx));
@@ -907,6 +1161,8 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
         // slices of a whole number of waves (64 items), spread over `ns` streams
         const uint32_t nc = (uint32_t)ctx->pipe_chunks;
         const uint32_t sl = ((m + nc - 1) / nc + 63u) & ~63u;
+        ctx->dd_rows[dd_slot] += m;  // (never deduplicated: lcv_set_dedup refuses a multi-stream pipeline)
+        ctx->dd_items[dd_slot] += m;
         for (int k = 1; k < ns; ++k) LCV_TRY(be_fork_to(ctx, k));
         uint32_t c = 0;
         for (uint32_t o = 0; o < m; o += sl, ++c) {
@@ -920,7 +1176,7 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
         be_use_stream(ctx, 0);
         for (int k = 1; k < ns; ++k) LCV_TRY(be_join_from(ctx, k));
       } else {
-        LCV_TRY(run_bls(ctx, B, C, m, 0, &P, (!piped && base == 0) ? &db->B : nullptr, S, fold != nullptr));
+        LCV_TRY(bls_chunk(dd_slot, B, base, m, (!piped && base == 0) ? &db->B : nullptr, fold != nullptr));
       }
       // the fold follows the verdicts of the whole batch (one chunk) on the main stream: after F_verdict in
       // stream order on both engines, after every slice has joined under a pipeline
@@ -1040,8 +1296,10 @@ static int validate_async_host(lcv_ctx* ctx, const char* who, const lcv_update_b
                                uint64_t current_slot, const uint8_t* gvr, int slot, FoldReq* fold = nullptr) {
   const FoldSegs* segs = fold ? fold->segs : nullptr;  // (a segmented fold's grouping has checked every index)
   if (store_index && !segs) LCV_TRY(store_index_check(ctx, who, store_index, hb->n));  // before the DMA
+  DedupCols dd;
+  LCV_TRY(dedup_stage(ctx, who, hb, store_index, dd));  // lcv_set_dedup: the grouping travels with the batch
   BatchCols c;
-  LCV_TRY(batch_cols(ctx, hb, c, who, store_index, segs));
+  LCV_TRY(batch_cols(ctx, hb, c, who, store_index, segs, dd.m ? &dd : nullptr));
   HostSlot& h = ctx->hslot[slot];
   be_set_slot(ctx, slot);
   // the staging buffer is reused only after the slot's previous batch has left it
@@ -1144,8 +1402,10 @@ static int validate_host(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_
     // one chunk (the reference's per-update call shape among them): the columns go through a reused pinned
     // staging buffer and ONE DMA into a reused device copy (lcv_validate_async's path, waited for here)
     // instead of a device allocation, one copy per column and a free per call
+    DedupCols dd;
+    LCV_TRY(dedup_stage(ctx, "lcv_validate_updates", hb, store_index, dd));  // lcv_set_dedup
     BatchCols c;
-    LCV_TRY(batch_cols(ctx, hb, c, "lcv_validate_updates", store_index, fold ? fold->segs : nullptr));
+    LCV_TRY(batch_cols(ctx, hb, c, "lcv_validate_updates", store_index, fold ? fold->segs : nullptr, dd.m ? &dd : nullptr));
     HostSlot& h = ctx->hsync;
     be_set_slot(ctx, 0);
     int rc = host_alloc_grow(ctx, &h.pinned, &h.pinned_cap, c.total);
@@ -1331,6 +1591,10 @@ int lcv_set_store_table(lcv_ctx* ctx, const lcv_store_table* t, uint8_t* key_sta
   std::vector<uint32_t> next(ns);
   for (size_t s = 0; s < ns; ++s)
     next[s] = (t->next[s] == LCV_STORE_NEXT_UNKNOWN || zero_row[t->next[s]]) ? (uint32_t)STORE_NEXT_UNKNOWN : t->next[s];
+  // the store columns also stay on the host, as the device gets them: lcv_set_dedup's grouping makes item_pre_table's
+  // committee choice there (dedup_comm_rows)
+  std::vector<uint64_t> host_fin(t->finalized_slot, t->finalized_slot + ns);
+  std::vector<uint32_t> host_cur(t->current, t->current + ns);
   // drain: batches in flight on any work-space slot read the table's committees and store columns, so every
   // slot's streams are waited for before that memory is rewritten or freed.  A batch already enqueued thus
   // finishes under the table it was enqueued under; work enqueued after this call sees the new one
@@ -1362,6 +1626,9 @@ int lcv_set_store_table(lcv_ctx* ctx, const lcv_store_table* t, uint8_t* key_sta
   if (rc == LCV_OK) rc = rs;
   if (rc != LCV_OK) return rc;
   be_collect_timings(ctx);  // the table build's kernel time: lcv_last_timings' setup stage
+  ctx->tab_fin.swap(host_fin);
+  ctx->tab_cur.swap(host_cur);
+  ctx->tab_next.swap(next);
   ctx->table_set = true;
   return LCV_OK;
 }
@@ -1703,9 +1970,12 @@ int lcv_debug_set_chunk(lcv_ctx* ctx, uint64_t rows) {
 // base + index(i, r).
 // kind 0 SoA (stride cap), 1 f, 2 lines, 3 committee-pool SoA (stride pool_cap, one item per distinct committee;
 // work_view does not advance these: they are not per update), 4 the rank records (item-major, lcv_fold.hpp
-// rank_index), 5 one per work space (the fold's result: a single item, not advanced by work_view either)
+// rank_index), 5 one per work space (the fold's result: a single item, not advanced by work_view either), 6 the
+// slot's deduplication scratch (lcv_set_dedup, ensure_dedup: item-major rows, one item per row of the work space;
+// a deduplicated chunk is never sliced, so work_view does not advance these)
 struct FieldRef { const char* name; const uint8_t* base; size_t esize, rows; int kind; size_t pool_cap = 0; };
-static int work_fields(const Work& W, FieldRef* f) {
+enum { WORK_FIELDS_MAX = 32 };
+static int work_fields(const Work& W, FieldRef* f, const DedupDev* D = nullptr) {
   int n = 0;
   f[n++] = {"msg", (const uint8_t*)W.msg, 4, 8, 0};
   f[n++] = {"pre_reason", W.pre_reason, 1, 1, 0};
@@ -1727,6 +1997,15 @@ static int work_fields(const Work& W, FieldRef* f) {
   f[n++] = {"nsc_flags", W.nsc_flags, 1, 1, 3, W.pool_cap};
   f[n++] = {"rank", W.rank, 1, RANK_BYTES, 4};
   f[n++] = {"fold_out", W.fold_out, 1, FOLD_RESULT_BYTES, 5, 1};
+  if (D) {
+    f[n++] = {"dedup_att_beacon", D->att_beacon, 1, K_BEACON, 6};
+    f[n++] = {"dedup_sig_slot", (const uint8_t*)D->sig_slot, 8, 1, 6};
+    f[n++] = {"dedup_bits", D->bits, 1, 64, 6};
+    f[n++] = {"dedup_sig", D->sig, 1, 96, 6};
+    f[n++] = {"dedup_comm_id", (const uint8_t*)D->comm_id, 4, 1, 6};
+    f[n++] = {"dedup_rep", (const uint8_t*)D->rep, 4, 1, 6};
+    f[n++] = {"dedup_urow", (const uint8_t*)D->urow, 4, 1, 6};
+  }
   return n;
 }
 // byte address of element r of item i (cap: the stride of the SoA fields)
@@ -1737,6 +2016,7 @@ static const uint8_t* field_addr(const FieldRef& f, size_t cap, size_t i, size_t
   else if (f.kind == 3) idx = soa_index(f.pool_cap, i, r);
   else if (f.kind == 4) idx = rank_index(i) + r;
   else if (f.kind == 5) idx = r;
+  else if (f.kind == 6) idx = i * f.rows + r;
   else idx = lines_index(i) + r;
   return f.base + idx * f.esize;
 }
@@ -1744,13 +2024,16 @@ static const uint8_t* field_addr(const FieldRef& f, size_t cap, size_t i, size_t
 extern "C" int lcv_debug_work_check(lcv_ctx* ctx, uint64_t cap, uint64_t slice, int nslots) {
   if (!ctx || cap == 0 || slice == 0 || nslots < 1 || nslots > LCV_SLOTS)
     return fail(ctx, LCV_EINVAL, "lcv_debug_work_check: cap, slice > 0, 1 <= nslots <= 8");
-  for (int s = 0; s < nslots; ++s) LCV_TRY(ensure_work(ctx, cap, 5, s));  // a committee pool of 5
+  for (int s = 0; s < nslots; ++s) {
+    LCV_TRY(ensure_work(ctx, cap, 5, s));  // a committee pool of 5
+    LCV_TRY(ensure_dedup(ctx, cap, s));    // and the slot's deduplication scratch (lcv_set_dedup), checked in (2)
+  }
   ctx->W = ctx->Wslot[0];
   // (1) slices: item j of work_view(W, b) is item b + j of W, element for element, in every field
   for (int s = 0; s < nslots; ++s) {
     const Work& W = ctx->Wslot[s];
     const size_t C = W.cap;
-    FieldRef full[24], part[24];
+    FieldRef full[WORK_FIELDS_MAX], part[WORK_FIELDS_MAX];
     const int nf = work_fields(W, full);
     for (size_t b = 0; b < C; b += slice) {
       work_fields(work_view(W, b), part);
@@ -1773,8 +2056,8 @@ extern "C" int lcv_debug_work_check(lcv_ctx* ctx, uint64_t cap, uint64_t slice, 
   for (int s = 0; s < nslots; ++s) {
     const Work& W = ctx->Wslot[s];
     const size_t C = W.cap;
-    FieldRef fr[24];
-    const int nf = work_fields(W, fr);
+    FieldRef fr[WORK_FIELDS_MAX];
+    const int nf = work_fields(W, fr, &ctx->Dslot[s]);
     for (int k = 0; k < nf; ++k) {
       const uint8_t* lo = field_addr(fr[k], C, 0, 0);
       const uint8_t* hi = lo;
@@ -1822,8 +2105,32 @@ int lcv_debug_engine_log(lcv_ctx* ctx, uint64_t* out8, int reset) {
 
 int lcv_set_pipeline(lcv_ctx* ctx, int streams, int chunks) {
   if (!ctx || streams < 1 || chunks < 1 || chunks > 4096) return fail(ctx, LCV_EINVAL, "lcv_set_pipeline: streams >= 1, 1 <= chunks <= 4096");
+  if (streams > 1 && ctx->dedup)
+    return fail(ctx, LCV_EINVAL, "lcv_set_pipeline: no multi-stream pipeline while lcv_set_dedup is on (sliced chains would need a grouping per slice)");
   ctx->pipe_streams = streams < 4 ? streams : 4;
   ctx->pipe_chunks = chunks;
+  return LCV_OK;
+}
+
+// ---- deduplicated BLS half (include/lcv.h "Deduplicated signatures")
+int lcv_set_dedup(lcv_ctx* ctx, int on) {
+  if (!ctx) return LCV_EINVAL;
+  if (on && ctx->pipe_streams > 1)
+    return fail(ctx, LCV_EINVAL, "lcv_set_dedup: not with a multi-stream pipeline (lcv_set_pipeline streams > 1): sliced chains would need a grouping per slice");
+  ctx->dedup = on != 0;
+  return LCV_OK;
+}
+
+int lcv_last_dedup(lcv_ctx* ctx, int slot, uint64_t* rows, uint64_t* items) {
+  if (!ctx || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_last_dedup: slot must be 0..7");
+  if (rows) *rows = ctx->dd_rows[slot];
+  if (items) *items = ctx->dd_items[slot];
+  return LCV_OK;
+}
+
+int lcv_debug_dedup_hash_bits(lcv_ctx* ctx, int bits) {
+  if (!ctx || bits < 0 || bits > 64) return fail(ctx, LCV_EINVAL, "lcv_debug_dedup_hash_bits: 0 <= bits <= 64");
+  ctx->dedup_hash_bits = (uint32_t)bits;
   return LCV_OK;
 }
 

@@ -223,6 +223,15 @@ LCV_FN uint32_t popcount_bits(const uint8_t* bits) {
   return pc;
 }
 
+// :452-459 committee selection: the committee-table row a signature is checked against, under a store whose
+// committees are the rows cur_row / next_row.  table_next_row: the next row item_pre_table passes for a table store
+// (the current row where the next committee is unknown, see there).  One rule for the device (item_pre_body) and for
+// the host, which groups rows by it (lcv_set_dedup, lcv_driver.inc dedup_comm_rows).
+LCV_HDFN uint32_t sig_committee_row(uint64_t sig_period, uint64_t store_period, uint32_t cur_row, uint32_t next_row) {
+  return sig_period != store_period ? next_row : cur_row;
+}
+LCV_HDFN uint32_t table_next_row(uint32_t cur, uint32_t nxt) { return nxt != STORE_NEXT_UNKNOWN ? nxt : cur; }
+
 // The non-BLS asserts of one update against one store snapshot: finalized slot `store_fin_slot`, next committee
 // known or not, and the committee-table rows the signature is checked against (`cur_row`, or `next_row` for a
 // signature of the next period).  Two front ends: item_pre (the context's single store: the :442 equality is a
@@ -293,7 +302,7 @@ LCV_FN void item_pre_body(uint32_t i, const BatchDev& B, const Params& P, const 
   }
 #undef LCV_FAIL
   // :452-459 committee selection (the signing root is item_sigroot's)
-  W.comm_id[i] = sig_period != store_period ? next_row : cur_row;
+  W.comm_id[i] = sig_committee_row(sig_period, store_period, cur_row, next_row);
   W.pre_reason[i] = (uint8_t)reason;
 }
 
@@ -309,7 +318,7 @@ LCV_FN void item_pre_table(uint32_t i, const BatchDev& B, const StoreDev& S, con
   const uint32_t s = B.store_index[i];
   const uint32_t cur = S.cur[s], nxt = S.next[s];
   const bool known = nxt != STORE_NEXT_UNKNOWN;
-  item_pre_body<true>(i, B, P, W, S.fin_slot[s], known, cur, known ? nxt : cur);
+  item_pre_body<true>(i, B, P, W, S.fin_slot[s], known, cur, table_next_row(cur, nxt));
 }
 
 // :442 with a store per update: next_sync_committee == store.next_sync_committee is no property of the pool row

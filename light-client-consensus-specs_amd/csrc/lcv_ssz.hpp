@@ -51,7 +51,7 @@ inline NetConfig net_config_mainnet() {
 }
 
 LCV_FN uint64_t epoch_of_slot(uint64_t slot, const NetConfig& c) { return slot / c.slots_per_epoch; }
-LCV_FN uint64_t period_of_slot(uint64_t slot, const NetConfig& c) {
+LCV_HDFN uint64_t period_of_slot(uint64_t slot, const NetConfig& c) {  // (the host groups rows by it: lcv_set_dedup)
   return slot / (c.slots_per_epoch * c.epochs_per_period);
 }
 

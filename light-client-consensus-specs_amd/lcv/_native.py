@@ -154,6 +154,9 @@ SIGNATURES = {
     "lcv_set_pipeline": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "lcv_set_latency_mode": (C.c_int, [C.c_void_p, C.c_uint64]),
     "lcv_debug_engine_log": (C.c_int, [C.c_void_p, u64p, C.c_int]),
+    "lcv_set_dedup": (C.c_int, [C.c_void_p, C.c_int]),
+    "lcv_last_dedup": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p]),
+    "lcv_debug_dedup_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
     "lcv_set_config": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lcv_stage_name": (C.c_char_p, [C.c_int]),
     "lcv_comm_unique_id": (C.c_int, [u8p]),

@@ -254,6 +254,7 @@ class Verifier:
         self.latency_mode = 64  # lcv_set_latency_mode's value (lcv_init's default: the fan engine up to 64 rows)
         self.pipeline = (1, 1)  # lcv_set_pipeline's (streams, chunks)
         self.chunk_rows = 65536  # rows per validate chunk, and the most one asynchronous call takes (debug_set_chunk)
+        self.dedup = False  # lcv_set_dedup's value
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc: int, what: str):
@@ -296,6 +297,28 @@ class Verifier:
         0 = the batch engine always."""
         self._check(self.lib.lcv_set_latency_mode(self.ctx, int(max_rows)), "lcv_set_latency_mode")
         self.latency_mode = int(max_rows)
+
+    def set_dedup(self, on: bool) -> None:
+        """Check each distinct sync-committee signature of a chunk once (lcv_set_dedup; off by default): rows whose
+        attested beacon header, signature_slot, sync bits, signature and signing committee are bytewise equal — one
+        update relayed to many stores — share one run of the BLS half, and every row keeps its own pre-checks.
+        Verdicts and reasons are those of the mode off.  Batches taken (validate*, upload) while the mode is on are
+        grouped; a ResidentBatch uploaded with it off is validated without deduplication.  LcvError (status -1)
+        together with a multi-stream pipeline (set_pipeline streams > 1), from whichever call comes second."""
+        self._check(self.lib.lcv_set_dedup(self.ctx, 1 if on else 0), "lcv_set_dedup")
+        self.dedup = bool(on)
+
+    def last_dedup(self, slot: int = 0) -> Tuple[int, int]:
+        """(rows, distinct BLS items) of the last batch enqueued on work-space slot `slot` (lcv_last_dedup);
+        synchronous calls use slot 0, summed over the batch's chunks.  items == rows without deduplication."""
+        rows, items = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.lcv_last_dedup(self.ctx, int(slot), C.byref(rows), C.byref(items)), "lcv_last_dedup")
+        return int(rows.value), int(items.value)
+
+    def debug_dedup_hash_bits(self, bits: int) -> None:
+        """Test hook (lcv_debug_dedup_hash_bits): set_dedup's host hash truncated to `bits` bits (64: whole; 0:
+        every row collides, so only the full compare of the rows' bytes separates them)."""
+        self._check(self.lib.lcv_debug_dedup_hash_bits(self.ctx, int(bits)), "lcv_debug_dedup_hash_bits")
 
     def debug_set_chunk(self, rows: int) -> None:
         """Test hook (lcv_debug_set_chunk): rows per validate chunk, a multiple of 64 up to the default 65536."""

@@ -9,7 +9,7 @@ update) may be mixed in one stream.
 from __future__ import annotations
 
 from collections import deque
-from typing import Iterable, Iterator, Tuple, Union
+from typing import Iterable, Iterator, Optional, Tuple, Union
 
 import numpy as np
 
@@ -22,7 +22,7 @@ Item = Union[PackedUpdates, Tuple[PackedUpdates, np.ndarray]]
 
 
 def validate_stream(verifier: Verifier, items: Iterable[Item], current_slot: int, genesis_validators_root: bytes,
-                    in_flight: int = SLOTS) -> Iterator[Tuple[np.ndarray, np.ndarray]]:
+                    in_flight: int = SLOTS, dedup: Optional[bool] = None) -> Iterator[Tuple[np.ndarray, np.ndarray]]:
     """Validate every item of `items` and yield its (verdicts: bool array, reason codes: uint8 array), in input
     order.  An item is a PackedUpdates — validated against the store of Verifier.set_store, as
     Verifier.validate does — or (PackedUpdates, store_index) — update i against row store_index[i] of the table
@@ -34,7 +34,11 @@ def validate_stream(verifier: Verifier, items: Iterable[Item], current_slot: int
     Verifier.validate_async / validate_stores_async; the generator waits for a slot only when it is about to
     reuse it (and, after the last item, for what is left).  Items above 65,536 rows — the rows of one
     asynchronous call — are cut into pieces, and an item's result is yielded whole.  No other call may use the
-    verifier's slots while the generator is live; closing it early waits for the slots in flight."""
+    verifier's slots while the generator is live; closing it early waits for the slots in flight.
+
+    `dedup`: None leaves the verifier's setting (Verifier.set_dedup) alone; a bool sets it for the stream — every
+    distinct signature of a piece checked once, for streams that relay one update to many stores — and restores
+    the previous setting when the generator ends."""
     in_flight = int(in_flight)
     if not 1 <= in_flight <= SLOTS:
         raise ValueError(f"in_flight must be 1..{SLOTS}")
@@ -43,6 +47,9 @@ def validate_stream(verifier: Verifier, items: Iterable[Item], current_slot: int
     pending = deque()  # (slot or None for an empty item, rows, last piece of its item), oldest first
     parts = []         # the pieces of the oldest item waited for so far
     next_slot = 0
+    dedup_before = bool(getattr(verifier, "dedup", False))
+    if dedup is not None:
+        verifier.set_dedup(bool(dedup))
 
     def finish_oldest():
         slot, rows, last = pending.popleft()
@@ -92,3 +99,5 @@ def validate_stream(verifier: Verifier, items: Iterable[Item], current_slot: int
                     verifier.slot_wait(slot, 0)
                 except Exception:
                     pass
+        if dedup is not None:
+            verifier.set_dedup(dedup_before)
