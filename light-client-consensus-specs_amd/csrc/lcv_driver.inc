@@ -1,9 +1,8 @@
 // lcv_driver.inc — implementation of include/lcv.h over an abstract execution backend.
 // Included by lcv_hip.hip (HIP streams / kernels on gfx950: the product, liblcv.so) and by
-// lcv_hostsim.cpp (plain host loops: test-only liblcv_hostsim.so).  The including file provides:
-//   struct Backend; be_init/be_destroy/be_alloc/be_free/be_h2d/be_d2h/be_d2d/be_memset/be_sync,
-//   be_launch<F>(ctx, functor, n), be_stage_begin/be_stage_end(ctx, stage), be_collect_timings(ctx)
-// and the LCV_HD qualifier for functor call operators.
+// lcv_hostsim.cpp (plain host loops: test-only liblcv_hostsim.so).  The including file provides
+// `struct Backend`, the LCV_HD qualifier for functor call operators, and the be_* interface that
+// lcv_backend.hpp declares.
 #include <string.h>
 
 #include <algorithm>
@@ -55,7 +54,7 @@ struct lcv_dbatch {
   // first row whose BLS inputs equal row i's; empty: uploaded with the mode off, validated without deduplication), and
   // a table batch also the two columns the committee choice of a row depends on, so that every validation can group
   // the rows under the table of that moment.  A staged host batch brings its grouping along instead (batch_cols
-  // columns 18, 19; plan_m items, 0: none)
+  // COL_DEDUP_REP, COL_DEDUP_UROW; plan_m items, 0: none)
   std::vector<uint32_t> cls, h_store;
   std::vector<uint64_t> h_sig_slot;
   const uint32_t* plan_rep = nullptr;
@@ -196,6 +195,41 @@ static int fail(lcv_ctx* ctx, int code, const std::string& msg) {
     if (_rc != LCV_OK) return _rc;    \
   } while (0)
 
+static const size_t kChunk = 65536;  // the largest chunk of validate, and of every entry that takes one chunk per call
+
+// A stage: one mark around its launches (marks never nest, see ST_*).  A launch that fails returns its code with
+// the mark left open: nothing collects the timings of a failed call.  bench.py's per-kernel roofline reads the
+// marks by name, so every marked launch goes through here
+template <class L> static int stage(lcv_ctx* ctx, int st, L&& launch) {
+  be_stage_begin(ctx, st);
+  LCV_TRY(launch());
+  be_stage_end(ctx, st);
+  return LCV_OK;
+}
+
+// buffers that only grow.  Pinned host memory: at least `bytes`.  Device memory: `bytes` for a capacity of
+// `new_cap` in the caller's unit — the growth policy is the caller's (be_free waits for the streams)
+static int host_alloc_grow(lcv_ctx* ctx, uint8_t** p, size_t* cap, size_t bytes) {
+  if (bytes <= *cap && *p) return LCV_OK;
+  if (*p) be_host_free(ctx, *p);
+  *p = nullptr;
+  *cap = 0;
+  void* q = nullptr;
+  LCV_TRY(be_host_alloc(ctx, &q, bytes));
+  *p = (uint8_t*)q;
+  *cap = bytes;
+  return LCV_OK;
+}
+static int dev_alloc_grow(lcv_ctx* ctx, void** p, size_t* cap, size_t new_cap, size_t bytes) {
+  if (new_cap <= *cap && *p) return LCV_OK;
+  if (*p) be_free(ctx, *p);
+  *p = nullptr;
+  *cap = 0;
+  LCV_TRY(be_alloc(ctx, p, bytes));
+  *cap = new_cap;
+  return LCV_OK;
+}
+
 #include "lcv_functors_sop.hpp"
 #if defined(LCV_CPU_FAST)
 #include "lcv_cpu_direct.hpp"
@@ -306,20 +340,14 @@ static int ensure_work(lcv_ctx* ctx, size_t cap, size_t pool_cap, int slot = 0) 
 static int ensure_dedup(lcv_ctx* ctx, size_t cap, int slot) {
   if (cap < ctx->work_cap[slot]) cap = ctx->work_cap[slot];
   if (cap <= ctx->dedup_cap[slot] && ctx->dedup_mem[slot]) return LCV_OK;
-  if (ctx->dedup_mem[slot]) be_free(ctx, ctx->dedup_mem[slot]);
-  ctx->dedup_mem[slot] = nullptr;
-  ctx->dedup_cap[slot] = 0;
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
   const size_t o_beacon = take((size_t)K_BEACON * cap), o_slot = take(8 * cap), o_bits = take(64 * cap),
                o_sig = take(96 * cap), o_comm = take(4 * cap), o_rep = take(4 * cap), o_urow = take(4 * cap);
-  void* mem = nullptr;
-  LCV_TRY(be_alloc(ctx, &mem, off));
-  uint8_t* m = (uint8_t*)mem;
+  LCV_TRY(dev_alloc_grow(ctx, &ctx->dedup_mem[slot], &ctx->dedup_cap[slot], cap, off));
+  uint8_t* m = (uint8_t*)ctx->dedup_mem[slot];
   ctx->Dslot[slot] = DedupDev{m + o_beacon, (uint64_t*)(m + o_slot), m + o_bits, m + o_sig, (uint32_t*)(m + o_comm),
                               (uint32_t*)(m + o_rep), (uint32_t*)(m + o_urow)};
-  ctx->dedup_mem[slot] = mem;
-  ctx->dedup_cap[slot] = cap;
   return LCV_OK;
 }
 
@@ -358,11 +386,10 @@ static CommitteeDev committee_view(const CommitteeBufs& cb, const uint8_t* next_
 // decode + KeyValidate every key, then per-committee sums / invalid-key masks
 static int build_committees(lcv_ctx* ctx, CommitteeBufs& cb) {
   CommitteeDev C = committee_view(cb, nullptr);
-  be_stage_begin(ctx, ST_SETUP);
-  LCV_TRY(be_launch(ctx, F_key{C}, cb.ncomm * 512));
-  LCV_TRY(be_launch_team(ctx, F_sum{C}, cb.ncomm));
-  be_stage_end(ctx, ST_SETUP);
-  return LCV_OK;
+  return stage(ctx, ST_SETUP, [&] {
+    LCV_TRY(be_launch(ctx, F_key{C}, cb.ncomm * 512));
+    return be_launch_team(ctx, F_sum{C}, cb.ncomm);
+  });
 }
 
 #define LCV_SOP_SRC(name) {kSop_##name##_hdr, sizeof(kSop_##name##_hdr)}, \
@@ -401,42 +428,25 @@ static Work work_view(const Work& W, size_t base) {
   return v;
 }
 
-static int pairing_tail(lcv_ctx* ctx, const Work& W, uint32_t n);
-static bool fused_miller(const lcv_ctx* ctx, uint64_t rows);
-static int fused_pairing(lcv_ctx* ctx, const Work& W, uint32_t n);
-// pairing check of W.qh / W.qs / W.pk for items [0, n): the SOP programs (lcv_functors_sop.hpp) —
-// lines of both pairings (2n teams), Miller accumulation, final exponentiation
-static int pairing_check(lcv_ctx* ctx, const Work& W, uint32_t n) {
-  if (fused_miller(ctx, n)) return fused_pairing(ctx, W, n);
-  be_stage_begin(ctx, ST_LINES);
-  LCV_TRY(launch_sop(ctx, F_sop_lines{W, ctx->sop_lines, 0u}, 2 * n, n));
-  be_stage_end(ctx, ST_LINES);
-  return pairing_tail(ctx, W, n);
-}
-
-// latency mode: both walks and the accumulation as one fan-engine program (F_sop_miller), then the final
-// exponentiation; the signature's G2 subgroup check happens inside (W.sig_status)
+// The end of every pairing check, written once: the Miller value of items [0, n) — the accumulation over both
+// pairings' lines in W.lines, or (fused; latency mode) both walks and the accumulation as one fan-engine program
+// (F_sop_miller; the signature's G2 subgroup check happens inside: W.sig_status) — then the final exponentiation
 static bool fused_miller(const lcv_ctx* ctx, uint64_t rows) { return fan_on(ctx, rows); }
-static int fused_pairing(lcv_ctx* ctx, const Work& W, uint32_t n) {
-  be_stage_begin(ctx, ST_MILLER);
-  ctx->eng_count[0] += 1;
-  LCV_TRY(be_launch_sop_fan(ctx, F_sop_miller{W, ctx->sop_miller}, n));
-  be_stage_end(ctx, ST_MILLER);
-  be_stage_begin(ctx, ST_FEXP);
-  LCV_TRY(launch_sop(ctx, F_sop_fexp{W, ctx->sop_fexp}, n, n));
-  be_stage_end(ctx, ST_FEXP);
-  return LCV_OK;
+static int miller_fexp(lcv_ctx* ctx, const Work& W, uint32_t n, bool fused) {
+  LCV_TRY(stage(ctx, ST_MILLER, [&] {
+    if (!fused) return launch_sop(ctx, F_sop_acc{W, ctx->sop_acc}, n, n);
+    ctx->eng_count[0] += 1;
+    return be_launch_sop_fan(ctx, F_sop_miller{W, ctx->sop_miller}, n);
+  }));
+  return stage(ctx, ST_FEXP, [&] { return launch_sop(ctx, F_sop_fexp{W, ctx->sop_fexp}, n, n); });
 }
 
-// Miller accumulation (both pairings' lines in W.lines) + final exponentiation
-static int pairing_tail(lcv_ctx* ctx, const Work& W, uint32_t n) {
-  be_stage_begin(ctx, ST_MILLER);
-  LCV_TRY(launch_sop(ctx, F_sop_acc{W, ctx->sop_acc}, n, n));
-  be_stage_end(ctx, ST_MILLER);
-  be_stage_begin(ctx, ST_FEXP);
-  LCV_TRY(launch_sop(ctx, F_sop_fexp{W, ctx->sop_fexp}, n, n));
-  be_stage_end(ctx, ST_FEXP);
-  return LCV_OK;
+// pairing check of W.qh / W.qs / W.pk for items [0, n), on one stream (lcv_debug_pairing): the SOP programs
+// (lcv_functors_sop.hpp) — the lines of both pairings in one launch (2n teams), then miller_fexp
+static int pairing_check(lcv_ctx* ctx, const Work& W, uint32_t n) {
+  if (fused_miller(ctx, n)) return miller_fexp(ctx, W, n, true);
+  LCV_TRY(stage(ctx, ST_LINES, [&] { return launch_sop(ctx, F_sop_lines{W, ctx->sop_lines, 0u}, 2 * n, n); }));
+  return miller_fexp(ctx, W, n, false);
 }
 
 // hash_to_G2 of W.msg for items [0, n) -> W.qh, W.qh_inf: two SSWU lanes per update, then the
@@ -456,15 +466,11 @@ static int sig_decode_check(lcv_ctx* ctx, const BatchDev& B, const Work& W, uint
 // masked aggregation of the participants' keys (team kernel; agg_items > n: slices folded into item 0)
 static int agg_stage(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, const Work& W, uint32_t n,
                      uint32_t agg_items) {
-  be_stage_begin(ctx, ST_AGG);
-  if (agg_items > n) {
+  return stage(ctx, ST_AGG, [&] {
+    if (agg_items <= n) return be_launch_team(ctx, F_agg_team{B, C, W}, n);
     LCV_TRY(be_launch_team(ctx, F_agg_team{B, C, W}, agg_items));
-    LCV_TRY(be_launch(ctx, F_agg_fold{W, agg_items}, 1));
-  } else {
-    LCV_TRY(be_launch_team(ctx, F_agg_team{B, C, W}, n));
-  }
-  be_stage_end(ctx, ST_AGG);
-  return LCV_OK;
+    return be_launch(ctx, F_agg_fold{W, agg_items}, 1);
+  });
 }
 
 // the non-BLS asserts of items [0, n): against the context's store, or (S: a batch with a store_index) each update
@@ -477,9 +483,41 @@ static int pre_stage(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, con
   return be_launch(ctx, F_pre_table{B, *S, P, W}, n);
 }
 
-// The BLS half of the pipeline for items [0, n) on two streams of the active slot (a main stream and a
+// the rank records of items [0, n) (the _fold calls, lcv_rank_*)
+static int rank_stage(lcv_ctx* ctx, const BatchDev& B, const Params& P, const Work& W, uint32_t n) {
+  return stage(ctx, ST_RANK, [&] { return be_launch(ctx, F_rank{B, P, W}, n); });
+}
+
+#if defined(LCV_CPU_FAST)
+// run_bls of the CPU-baseline build: direct per-update code (lcv_cpu_direct.hpp), one core per update, in
+// program order (never deduplicated: dedup_on)
+static int run_bls_direct(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint32_t n, uint32_t agg_items,
+                          const Params* P, const BatchDev* nsc, const StoreDev* S, bool rank) {
+  const Work& W = ctx->W;
+  if (nsc) LCV_TRY(be_launch_team(ctx, F_nsc_team{*nsc, C, W}, nsc->npool));
+  if (P) {
+    LCV_TRY(pre_stage(ctx, B, C, *P, S, W, n));
+    if (rank) LCV_TRY(rank_stage(ctx, B, *P, W, n));
+    LCV_TRY(be_launch(ctx, F_sigroot{B, *P, W}, n));
+  }
+  LCV_TRY(stage(ctx, ST_SIG, [&] { return be_launch(ctx, F_sig_direct{B, W}, n); }));
+  LCV_TRY(stage(ctx, ST_H2C, [&] { return be_launch(ctx, F_h2c_direct{W}, n); }));
+  LCV_TRY(stage(ctx, ST_AGG, [&] {
+    LCV_TRY(be_launch(ctx, F_agg{B, C, W}, agg_items > n ? agg_items : n));
+    return agg_items > n ? be_launch(ctx, F_agg_fold{W, agg_items}, 1) : LCV_OK;
+  }));
+  LCV_TRY(stage(ctx, ST_MILLER, [&] { return be_launch(ctx, F_pair_direct{W}, n); }));
+  return stage(ctx, ST_VERDICT, [&] { return be_launch(ctx, F_verdict{W}, n); });
+}
+#endif
+
+// A deduplicated chunk of validate (lcv_set_dedup): the grouping of its n rows into m items (rep, urow: device
+// pointers) is known, D is the slot's scratch for the items' compact columns
+struct DedupRun { DedupDev D; const uint32_t* rep; const uint32_t* urow; uint32_t m; };
+
+// The BLS half of the pipeline for rows [0, n) on two streams of the active slot (a main stream and a
 // side stream), ordered by events:
-//   side: [HTR(next_sync_committee)] [item_pre: reasons, committee ids], signature decode, [masked
+//   side: [HTR(next_sync_committee)] [item_pre: reasons, committee ids] [rank records], signature decode, [masked
 //         aggregation, without committee hashing] -> EV_PRE, (after EV_H2C) the signature pairing's line
 //         walk with the fused G2 subgroup check -> EV_SIDE
 //   main: [signing root] SSWU maps, hash_to_G2 tail, (after EV_PRE) [masked aggregation, with committee
@@ -492,194 +530,81 @@ static int pre_stage(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, con
 // agg_items > n (FastAggregateVerify of > 512 keys, n == 1): the aggregation runs over agg_items
 // slices and item_agg_fold sums them into item 0.  S: the store table of a batch with a store_index (pre_stage).
 // rank (the _fold calls only): the rank records of the slice (F_rank) follow the pre-checks on the side stream.
-static int rank_stage(lcv_ctx* ctx, const BatchDev& B, const Params& P, const Work& W, uint32_t n) {
-  be_stage_begin(ctx, ST_RANK);
-  LCV_TRY(be_launch(ctx, F_rank{B, P, W}, n));
-  be_stage_end(ctx, ST_RANK);
-  return LCV_OK;
-}
+//
+// R (a deduplicated chunk; with P): the pre-checks and the rank records run over the n rows as ever, then
+//   side: F_dedup_gather -> EV_GATHER, and the main stream's work waits for EV_GATHER
+// and from there every BLS stage runs over the R->m items — m sizes every launch and picks the engine — on the
+// items' compact columns (Bu) and compact committee ids (Wu.comm_id), which the gather takes from what item_pre
+// wrote; F_verdict_dedup then gives each of the n rows its item's verdict.  Without R the items are the rows.
 static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint32_t n, uint32_t agg_items = 0,
                    const Params* P = nullptr, const BatchDev* nsc = nullptr, const StoreDev* S = nullptr,
-                   bool rank = false) {
+                   bool rank = false, const DedupRun* R = nullptr) {
   const Work& W = ctx->W;
 #if defined(LCV_CPU_FAST)
-  if (!W.msg_b0) {  // CPU-baseline build: direct per-update code (lcv_cpu_direct.hpp), one core per update
-    if (nsc) LCV_TRY(be_launch_team(ctx, F_nsc_team{*nsc, C, W}, nsc->npool));
-    if (P) {
-      LCV_TRY(pre_stage(ctx, B, C, *P, S, W, n));
-      if (rank) LCV_TRY(rank_stage(ctx, B, *P, W, n));
-      LCV_TRY(be_launch(ctx, F_sigroot{B, *P, W}, n));
-    }
-    be_stage_begin(ctx, ST_SIG);
-    LCV_TRY(be_launch(ctx, F_sig_direct{B, W}, n));
-    be_stage_end(ctx, ST_SIG);
-    be_stage_begin(ctx, ST_H2C);
-    LCV_TRY(be_launch(ctx, F_h2c_direct{W}, n));
-    be_stage_end(ctx, ST_H2C);
-    be_stage_begin(ctx, ST_AGG);
-    LCV_TRY(be_launch(ctx, F_agg{B, C, W}, agg_items > n ? agg_items : n));
-    if (agg_items > n) LCV_TRY(be_launch(ctx, F_agg_fold{W, agg_items}, 1));
-    be_stage_end(ctx, ST_AGG);
-    be_stage_begin(ctx, ST_MILLER);
-    LCV_TRY(be_launch(ctx, F_pair_direct{W}, n));
-    be_stage_end(ctx, ST_MILLER);
-    be_stage_begin(ctx, ST_VERDICT);
-    LCV_TRY(be_launch(ctx, F_verdict{W}, n));
-    be_stage_end(ctx, ST_VERDICT);
-    return LCV_OK;
-  }
+  if (!W.msg_b0) return run_bls_direct(ctx, B, C, n, agg_items, P, nsc, S, rank);
 #endif
+  const uint32_t m = R ? R->m : n;
+  BatchDev Bu = B;
+  Work Wu = W;
+  if (R) {
+    Bu.att_beacon = R->D.att_beacon; Bu.sig_slot = R->D.sig_slot; Bu.bits = R->D.bits; Bu.sig = R->D.sig;
+    Bu.n = m;
+    Wu.comm_id = R->D.comm_id;
+  }
   LCV_TRY(be_mark(ctx, EV_START, 0));
   LCV_TRY(be_wait(ctx, 1, EV_START));  // the side stream starts after the slot's earlier main-stream work
   be_use_stream(ctx, 1);
-  if (nsc) {
-    be_stage_begin(ctx, ST_NSC);
-    LCV_TRY(be_launch_team(ctx, F_nsc_team{*nsc, C, W}, nsc->npool));
-    be_stage_end(ctx, ST_NSC);
-  }
+  if (nsc) LCV_TRY(stage(ctx, ST_NSC, [&] { return be_launch_team(ctx, F_nsc_team{*nsc, C, W}, nsc->npool); }));
   if (P) {
-    be_stage_begin(ctx, ST_PRE);
-    LCV_TRY(pre_stage(ctx, B, C, *P, S, W, n));
-    be_stage_end(ctx, ST_PRE);
+    LCV_TRY(stage(ctx, ST_PRE, [&] { return pre_stage(ctx, B, C, *P, S, W, n); }));
     if (rank) LCV_TRY(rank_stage(ctx, B, *P, W, n));
   }
-  be_stage_begin(ctx, ST_SIG);
-  LCV_TRY(launch_items(ctx, F_sig{B, W}, n, n));
-  be_stage_end(ctx, ST_SIG);
+  if (R) {
+    LCV_TRY(stage(ctx, ST_DEDUP, [&] { return be_launch_team(ctx, F_dedup_gather{B, W, R->urow, R->D}, m); }));
+    LCV_TRY(be_mark(ctx, EV_GATHER, 1));
+  }
+  LCV_TRY(stage(ctx, ST_SIG, [&] { return launch_items(ctx, F_sig{Bu, Wu}, m, m); }));
   // the masked aggregation needs item_pre's committee ids only.  It runs here, off the main stream's
   // SSWU -> hash_to_G2 chain, the longer one (one update: 2.4 ms against 2.2 on this stream with the
   // committee hashed) — unless the slice hashes a large pool of distinct committees (configs[3]: one per
   // update), which makes this stream the longer one: then it stays on the main stream, after EV_PRE
   const bool agg_side = nsc == nullptr || nsc->npool < 64;
-  if (agg_side) LCV_TRY(agg_stage(ctx, B, C, W, n, agg_items));
+  if (agg_side) LCV_TRY(agg_stage(ctx, Bu, C, Wu, m, agg_items));
   LCV_TRY(be_mark(ctx, EV_PRE, 1));
   be_use_stream(ctx, 0);
-  if (P) {
-    be_stage_begin(ctx, ST_SIGROOT);
-    LCV_TRY(be_launch(ctx, F_sigroot{B, *P, W}, n));
-    be_stage_end(ctx, ST_SIGROOT);
-  }
-  be_stage_begin(ctx, ST_H2C_MAP);
-  LCV_TRY(launch_items(ctx, F_h2c_map{W}, 2 * n, n));
-  be_stage_end(ctx, ST_H2C_MAP);
-  be_stage_begin(ctx, ST_H2C);
-  LCV_TRY(launch_sop(ctx, F_sop_h2c{W, ctx->sop_h2c}, n, n));
-  be_stage_end(ctx, ST_H2C);
+  if (R) LCV_TRY(be_wait(ctx, 0, EV_GATHER));
+  if (P) LCV_TRY(stage(ctx, ST_SIGROOT, [&] { return be_launch(ctx, F_sigroot{Bu, *P, Wu}, m); }));
+  LCV_TRY(stage(ctx, ST_H2C_MAP, [&] { return launch_items(ctx, F_h2c_map{Wu}, 2 * m, m); }));
+  LCV_TRY(stage(ctx, ST_H2C, [&] { return launch_sop(ctx, F_sop_h2c{Wu, ctx->sop_h2c}, m, m); }));
   // item_pre's ids and (agg_side) the aggregate key, before EV_H2C: the message pairing's walk then follows
   // hash_to_G2 in stream order, with no wait of its own, and is dispatched ahead of the signature's walk
   // (which waits on EV_H2C) — with both behind cross-stream waits they share the CUs evenly and the Miller
   // accumulation after them measured 1.75 -> 1.9-2.3 ms per 10^4 batch (profiles/r05_v3/serial_ab.txt)
   LCV_TRY(be_wait(ctx, 0, EV_PRE));
-  if (!agg_side) LCV_TRY(agg_stage(ctx, B, C, W, n, agg_items));
-  if (fused_miller(ctx, n)) {  // latency mode: EV_PRE (after the side stream's last kernel) joins it
-    LCV_TRY(fused_pairing(ctx, W, n));
-    be_stage_begin(ctx, ST_VERDICT);
-    LCV_TRY(be_launch(ctx, F_verdict{W}, n));
-    be_stage_end(ctx, ST_VERDICT);
-    return LCV_OK;
-  }
-  LCV_TRY(be_mark(ctx, EV_H2C, 0));
-  be_use_stream(ctx, 1);
-  LCV_TRY(be_wait(ctx, 1, EV_H2C));
-  be_stage_begin(ctx, ST_LINES_SIG);
-  LCV_TRY(launch_sop(ctx, F_sop_lines{W, ctx->sop_lines, 1u}, n, n));
-  be_stage_end(ctx, ST_LINES_SIG);
-  LCV_TRY(be_mark(ctx, EV_SIDE, 1));
-  be_use_stream(ctx, 0);
-  be_stage_begin(ctx, ST_LINES);
-  LCV_TRY(launch_sop(ctx, F_sop_lines{W, ctx->sop_lines, 2u}, n, n));
-  be_stage_end(ctx, ST_LINES);
-  LCV_TRY(be_wait(ctx, 0, EV_SIDE));
-  LCV_TRY(pairing_tail(ctx, W, n));
-  be_stage_begin(ctx, ST_VERDICT);
-  LCV_TRY(be_launch(ctx, F_verdict{W}, n));
-  be_stage_end(ctx, ST_VERDICT);
-  return LCV_OK;
-}
-
-// run_bls for a deduplicated chunk of validate (lcv_set_dedup): the grouping of its n rows into R.m items (rep, urow:
-// device pointers) is known, and m sizes every BLS launch and picks the engine.
-//   side: [HTR(next_sync_committee)] item_pre over the n rows [rank records], F_dedup_gather -> EV_GATHER, then over the
-//         m items: signature decode, [masked aggregation] -> EV_PRE, (after EV_H2C) the signature's line walk -> EV_SIDE
-//   main: (after EV_GATHER) over the m items: signing root, SSWU maps, hash_to_G2 tail, (after EV_PRE) [masked
-//         aggregation] -> EV_H2C, the message's line walk, (after EV_SIDE) Miller accumulation, final exponentiation;
-//         F_verdict_dedup over the n rows
-// Everything on the BLS side follows the gather: its stages read the items' compact columns (Bu) and the compact
-// committee ids (Wu.comm_id), which the gather takes from what item_pre wrote.
-struct DedupRun { DedupDev D; const uint32_t* rep; const uint32_t* urow; uint32_t m; };
-static int run_bls_dedup(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint32_t n, const Params& P,
-                         const BatchDev* nsc, const StoreDev* S, bool rank, const DedupRun& R) {
-  const Work& W = ctx->W;
-  const uint32_t m = R.m;
-  BatchDev Bu = B;
-  Bu.att_beacon = R.D.att_beacon; Bu.sig_slot = R.D.sig_slot; Bu.bits = R.D.bits; Bu.sig = R.D.sig;
-  Bu.n = m;
-  Work Wu = W;
-  Wu.comm_id = R.D.comm_id;
-  LCV_TRY(be_mark(ctx, EV_START, 0));
-  LCV_TRY(be_wait(ctx, 1, EV_START));
-  be_use_stream(ctx, 1);
-  if (nsc) {
-    be_stage_begin(ctx, ST_NSC);
-    LCV_TRY(be_launch_team(ctx, F_nsc_team{*nsc, C, W}, nsc->npool));
-    be_stage_end(ctx, ST_NSC);
-  }
-  be_stage_begin(ctx, ST_PRE);
-  LCV_TRY(pre_stage(ctx, B, C, P, S, W, n));
-  be_stage_end(ctx, ST_PRE);
-  if (rank) LCV_TRY(rank_stage(ctx, B, P, W, n));
-  be_stage_begin(ctx, ST_DEDUP);
-  LCV_TRY(be_launch_team(ctx, F_dedup_gather{B, W, R.urow, R.D}, m));
-  be_stage_end(ctx, ST_DEDUP);
-  LCV_TRY(be_mark(ctx, EV_GATHER, 1));
-  be_stage_begin(ctx, ST_SIG);
-  LCV_TRY(launch_items(ctx, F_sig{Bu, Wu}, m, m));
-  be_stage_end(ctx, ST_SIG);
-  const bool agg_side = nsc == nullptr || nsc->npool < 64;  // (run_bls)
-  if (agg_side) LCV_TRY(agg_stage(ctx, Bu, C, Wu, m, 0));
-  LCV_TRY(be_mark(ctx, EV_PRE, 1));
-  be_use_stream(ctx, 0);
-  LCV_TRY(be_wait(ctx, 0, EV_GATHER));
-  be_stage_begin(ctx, ST_SIGROOT);
-  LCV_TRY(be_launch(ctx, F_sigroot{Bu, P, Wu}, m));
-  be_stage_end(ctx, ST_SIGROOT);
-  be_stage_begin(ctx, ST_H2C_MAP);
-  LCV_TRY(launch_items(ctx, F_h2c_map{Wu}, 2 * m, m));
-  be_stage_end(ctx, ST_H2C_MAP);
-  be_stage_begin(ctx, ST_H2C);
-  LCV_TRY(launch_sop(ctx, F_sop_h2c{Wu, ctx->sop_h2c}, m, m));
-  be_stage_end(ctx, ST_H2C);
-  LCV_TRY(be_wait(ctx, 0, EV_PRE));
-  if (!agg_side) LCV_TRY(agg_stage(ctx, Bu, C, Wu, m, 0));
-  if (fused_miller(ctx, m)) {
-    LCV_TRY(fused_pairing(ctx, Wu, m));
-  } else {
+  if (!agg_side) LCV_TRY(agg_stage(ctx, Bu, C, Wu, m, agg_items));
+  const bool fused = fused_miller(ctx, m);  // latency mode: EV_PRE (after the side stream's last kernel) joins it
+  if (!fused) {
     LCV_TRY(be_mark(ctx, EV_H2C, 0));
     be_use_stream(ctx, 1);
     LCV_TRY(be_wait(ctx, 1, EV_H2C));
-    be_stage_begin(ctx, ST_LINES_SIG);
-    LCV_TRY(launch_sop(ctx, F_sop_lines{Wu, ctx->sop_lines, 1u}, m, m));
-    be_stage_end(ctx, ST_LINES_SIG);
+    LCV_TRY(stage(ctx, ST_LINES_SIG, [&] { return launch_sop(ctx, F_sop_lines{Wu, ctx->sop_lines, 1u}, m, m); }));
     LCV_TRY(be_mark(ctx, EV_SIDE, 1));
     be_use_stream(ctx, 0);
-    be_stage_begin(ctx, ST_LINES);
-    LCV_TRY(launch_sop(ctx, F_sop_lines{Wu, ctx->sop_lines, 2u}, m, m));
-    be_stage_end(ctx, ST_LINES);
+    LCV_TRY(stage(ctx, ST_LINES, [&] { return launch_sop(ctx, F_sop_lines{Wu, ctx->sop_lines, 2u}, m, m); }));
     LCV_TRY(be_wait(ctx, 0, EV_SIDE));
-    LCV_TRY(pairing_tail(ctx, Wu, m));
   }
-  be_stage_begin(ctx, ST_VERDICT);
-  LCV_TRY(be_launch(ctx, F_verdict_dedup{W, R.rep}, n));
-  be_stage_end(ctx, ST_VERDICT);
-  return LCV_OK;
+  LCV_TRY(miller_fexp(ctx, Wu, m, fused));
+  return stage(ctx, ST_VERDICT, [&] {
+    return R ? be_launch(ctx, F_verdict_dedup{W, R->rep}, n) : be_launch(ctx, F_verdict{W}, n);
+  });
 }
 
 // The whole per-update chain (pre-checks, signature decode + subgroup check, hash_to_G2, masked
 // aggregation, Miller loop, final exponentiation, verdict) for one slice, on the current stream.
-// Slices are independent, so validate_impl runs slice k on stream k % pipe_streams: the kernels of
-// different slices overlap, filling the CUs that one stage's tail (or a one-lane-per-update stage)
-// leaves idle.  No stage marks: concurrent kernels would inflate each other's event times.  S: the store
-// table of a batch that carries its store_index (pre_stage).
+// Slices are independent, so the sliced pipeline of validate runs slice k on stream k % pipe_streams: the
+// kernels of different slices overlap, filling the CUs that one stage's tail (or a one-lane-per-update stage)
+// leaves idle.  No stage marks of its own: concurrent kernels would inflate each other's event times.  S: the
+// store table of a batch that carries its store_index (pre_stage).
 static int run_slice(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, const Params& P, const StoreDev* S,
                      const Work& W, uint32_t n, bool rank = false) {
   LCV_TRY(pre_stage(ctx, B, C, P, S, W, n));
@@ -689,11 +614,9 @@ static int run_slice(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, con
   LCV_TRY(hash_to_g2_stage(ctx, W, n));
   LCV_TRY(be_launch_team(ctx, F_agg_team{B, C, W}, n));
   LCV_TRY(launch_sop(ctx, F_sop_lines{W, ctx->sop_lines, 2u}, n, n));
-  LCV_TRY(pairing_tail(ctx, W, n));
+  LCV_TRY(miller_fexp(ctx, W, n, false));
   return be_launch(ctx, F_verdict{W}, n);
 }
-
-static const size_t kChunk = 65536;
 
 // ------------------------------------------------------------------ API
 extern "C" {
@@ -773,12 +696,17 @@ int lcv_set_store(lcv_ctx* ctx, uint64_t finalized_slot, const uint8_t* cur, con
 
 }  // extern "C"
 
-// the 13 columns of a packed batch, and the per-update store-table rows of lcv_validate_updates_stores (column
-// 13: empty otherwise), each at a 256-byte aligned offset of one device allocation.  Columns 14-17 (a segmented
-// fold, lcv_validate_stores_fold: empty otherwise) are the grouping of the rows by store and the present stores'
-// fold states (FoldSegs: store, off, row, in), which so travel with the batch in its one copy.  Columns 18, 19 (a
-// staged batch under lcv_set_dedup: empty otherwise) are the grouping of its rows into BLS items (DedupCols: rep, urow)
-enum { BATCH_COLS = 20 };
+// The columns of a packed batch, each at a 256-byte aligned offset of one device allocation: the 13 of
+// lcv_update_batch, which every batch has, then the optional ones, empty where unused, which so travel with the
+// batch in its one copy — the per-update store-table rows of lcv_validate_updates_stores; the grouping of the rows
+// by store and the present stores' fold states of a segmented fold (lcv_validate_stores_fold; FoldSegs: store,
+// off, row, in); the grouping of a staged batch's rows into BLS items under lcv_set_dedup (DedupCols: rep, urow)
+enum BatchCol {
+  COL_ATT_BEACON = 0, COL_ATT_EXEC, COL_ATT_BRANCH, COL_FIN_BEACON, COL_FIN_EXEC, COL_FIN_BRANCH, COL_NSC_POOL,
+  COL_NSC_INDEX, COL_NSC_BRANCH, COL_FINALITY_BRANCH, COL_BITS, COL_SIG, COL_SIG_SLOT,
+  COL_STORE_INDEX, COL_SEG_STORE, COL_SEG_OFF, COL_SEG_ROW, COL_SEG_IN, COL_DEDUP_REP, COL_DEDUP_UROW,
+  BATCH_COLS, BATCH_COLS_REQUIRED = COL_STORE_INDEX
+};
 struct DedupCols { const uint32_t* rep; const uint32_t* urow; uint32_t m; };
 struct BatchCols {
   const void* src[BATCH_COLS];
@@ -789,16 +717,20 @@ struct BatchCols {
 // the layout alone (no host sources): n rows, np pool rows, with a store_index column or not, ng fold segments,
 // nd BLS items (0: no grouping)
 static void batch_layout(BatchCols& c, size_t n, size_t np, bool stores, size_t ng, size_t nd = 0) {
-  const size_t bytes[BATCH_COLS] = {112 * n, 832 * n, 128 * n, 112 * n, 832 * n, 128 * n, (size_t)K_SC * np, 4 * n,
-                                    160 * n, 192 * n, 64 * n, 96 * n, 8 * n, stores ? 4 * n : 0,
-                                    4 * ng, ng ? 4 * (ng + 1) : 0, ng ? 4 * n : 0, sizeof(FoldState) * ng,
-                                    nd ? 4 * n : 0, 4 * nd};
+  size_t* b = c.bytes;
+  b[COL_ATT_BEACON] = b[COL_FIN_BEACON] = 112 * n; b[COL_ATT_EXEC] = b[COL_FIN_EXEC] = 832 * n;
+  b[COL_ATT_BRANCH] = b[COL_FIN_BRANCH] = 128 * n;
+  b[COL_NSC_POOL] = (size_t)K_SC * np; b[COL_NSC_INDEX] = 4 * n; b[COL_NSC_BRANCH] = 160 * n;
+  b[COL_FINALITY_BRANCH] = 192 * n; b[COL_BITS] = 64 * n; b[COL_SIG] = 96 * n; b[COL_SIG_SLOT] = 8 * n;
+  b[COL_STORE_INDEX] = stores ? 4 * n : 0;
+  b[COL_SEG_STORE] = 4 * ng; b[COL_SEG_OFF] = ng ? 4 * (ng + 1) : 0; b[COL_SEG_ROW] = ng ? 4 * n : 0;
+  b[COL_SEG_IN] = sizeof(FoldState) * ng;
+  b[COL_DEDUP_REP] = nd ? 4 * n : 0; b[COL_DEDUP_UROW] = 4 * nd;
   c.total = 0;
   for (int k = 0; k < BATCH_COLS; ++k) {
     c.src[k] = nullptr;
-    c.bytes[k] = bytes[k];
     c.off[k] = c.total;
-    c.total += (bytes[k] + 255) & ~(size_t)255;
+    c.total += (b[k] + 255) & ~(size_t)255;
   }
   c.n = n;
   c.np = np;
@@ -810,14 +742,21 @@ static int batch_cols(lcv_ctx* ctx, const lcv_update_batch* hb, BatchCols& c, co
   const size_t n = hb->n, np = hb->npool, ng = segs ? segs->nseg : 0;
   if (n == 0 || np == 0 || n > 0xffffffffull || np > 0xffffffffull)
     return fail(ctx, LCV_EINVAL, std::string(who) + ": need 0 < n, 0 < npool < 2^32");
-  const void* src[BATCH_COLS] = {hb->attested.beacon, hb->attested.execution, hb->attested.exec_branch,
-                         hb->finalized.beacon, hb->finalized.execution, hb->finalized.exec_branch,
-                         hb->nsc_pool, hb->nsc_index, hb->nsc_branch, hb->finality_branch,
-                         hb->sync_bits, hb->sync_signature, hb->signature_slot, store_index,
-                         ng ? segs->store.data() : nullptr, ng ? segs->off.data() : nullptr,
-                         ng ? segs->row.data() : nullptr, ng ? segs->in.data() : nullptr,
-                         dd ? dd->rep : nullptr, dd ? dd->urow : nullptr};
-  for (int k = 0; k < 13; ++k)
+  const void* src[BATCH_COLS] = {};
+  src[COL_ATT_BEACON] = hb->attested.beacon; src[COL_ATT_EXEC] = hb->attested.execution;
+  src[COL_ATT_BRANCH] = hb->attested.exec_branch;
+  src[COL_FIN_BEACON] = hb->finalized.beacon; src[COL_FIN_EXEC] = hb->finalized.execution;
+  src[COL_FIN_BRANCH] = hb->finalized.exec_branch;
+  src[COL_NSC_POOL] = hb->nsc_pool; src[COL_NSC_INDEX] = hb->nsc_index; src[COL_NSC_BRANCH] = hb->nsc_branch;
+  src[COL_FINALITY_BRANCH] = hb->finality_branch;
+  src[COL_BITS] = hb->sync_bits; src[COL_SIG] = hb->sync_signature; src[COL_SIG_SLOT] = hb->signature_slot;
+  src[COL_STORE_INDEX] = store_index;
+  if (ng) {
+    src[COL_SEG_STORE] = segs->store.data(); src[COL_SEG_OFF] = segs->off.data();
+    src[COL_SEG_ROW] = segs->row.data(); src[COL_SEG_IN] = segs->in.data();
+  }
+  if (dd) { src[COL_DEDUP_REP] = dd->rep; src[COL_DEDUP_UROW] = dd->urow; }
+  for (int k = 0; k < BATCH_COLS_REQUIRED; ++k)
     if (!src[k]) return fail(ctx, LCV_EINVAL, std::string(who) + ": null column");
   batch_layout(c, n, np, store_index != nullptr, ng, dd ? dd->m : 0);
   for (int k = 0; k < BATCH_COLS; ++k) c.src[k] = src[k];
@@ -828,27 +767,29 @@ static int batch_cols(lcv_ctx* ctx, const lcv_update_batch* hb, BatchCols& c, co
 
 // db's column pointers into device memory m laid out as c
 static void bind_batch(lcv_dbatch* db, uint8_t* m, const BatchCols& c) {
+  auto at = [&](BatchCol k) { return m + c.off[k]; };
   BatchDev& B = db->B;
-  B.att_beacon = m + c.off[0]; B.att_exec = m + c.off[1]; B.att_branch = m + c.off[2];
-  B.fin_beacon = m + c.off[3]; B.fin_exec = m + c.off[4]; B.fin_branch = m + c.off[5];
-  B.nsc_pool = m + c.off[6]; B.nsc_index = (const uint32_t*)(m + c.off[7]); B.nsc_branch = m + c.off[8];
-  B.finality_branch = m + c.off[9]; B.bits = m + c.off[10]; B.sig = m + c.off[11];
-  B.sig_slot = (const uint64_t*)(m + c.off[12]);
-  B.store_index = c.bytes[13] ? (const uint32_t*)(m + c.off[13]) : nullptr;
+  B.att_beacon = at(COL_ATT_BEACON); B.att_exec = at(COL_ATT_EXEC); B.att_branch = at(COL_ATT_BRANCH);
+  B.fin_beacon = at(COL_FIN_BEACON); B.fin_exec = at(COL_FIN_EXEC); B.fin_branch = at(COL_FIN_BRANCH);
+  B.nsc_pool = at(COL_NSC_POOL); B.nsc_index = (const uint32_t*)at(COL_NSC_INDEX); B.nsc_branch = at(COL_NSC_BRANCH);
+  B.finality_branch = at(COL_FINALITY_BRANCH); B.bits = at(COL_BITS); B.sig = at(COL_SIG);
+  B.sig_slot = (const uint64_t*)at(COL_SIG_SLOT);
+  B.store_index = c.bytes[COL_STORE_INDEX] ? (const uint32_t*)at(COL_STORE_INDEX) : nullptr;
   B.n = (uint32_t)c.n;
   B.npool = (uint32_t)c.np;
   db->n = c.n;
   db->npool = c.np;
   db->max_store = 0;
-  if (c.bytes[13]) {
-    const uint32_t* ix = (const uint32_t*)c.src[13];
+  if (c.bytes[COL_STORE_INDEX]) {
+    const uint32_t* ix = (const uint32_t*)c.src[COL_STORE_INDEX];
     for (size_t i = 0; i < c.n; ++i)
       if (ix[i] > db->max_store) db->max_store = ix[i];
   }
   // a staged batch's grouping into BLS items (lcv_set_dedup), where it was staged
-  db->plan_rep = c.bytes[19] ? (const uint32_t*)(m + c.off[18]) : nullptr;
-  db->plan_urow = c.bytes[19] ? (const uint32_t*)(m + c.off[19]) : nullptr;
-  db->plan_m = (uint32_t)(c.bytes[19] / 4);
+  const bool plan = c.bytes[COL_DEDUP_UROW] != 0;
+  db->plan_rep = plan ? (const uint32_t*)at(COL_DEDUP_REP) : nullptr;
+  db->plan_urow = plan ? (const uint32_t*)at(COL_DEDUP_UROW) : nullptr;
+  db->plan_m = (uint32_t)(c.bytes[COL_DEDUP_UROW] / 4);
 }
 
 // ---- deduplicated BLS half, host side (lcv_set_dedup; lcv_dedup_plan.hpp).  The CPU-baseline build's direct branch
@@ -896,9 +837,6 @@ static int dedup_stage(lcv_ctx* ctx, const char* who, const lcv_update_batch* hb
 // the grouping of rows [base, base + n) of a batch for this validation, and the slot's scratch: a staged batch
 // brought it along; a resident batch's chunk is grouped here from the columns it keeps on the host, under the table
 // of this call, and the two columns go to the device through the slot's pinned buffer in one small copy each
-extern "C" {
-static int host_alloc_grow(lcv_ctx* ctx, uint8_t** p, size_t* cap, size_t bytes);
-}
 static int dedup_chunk(lcv_ctx* ctx, const lcv_dbatch* db, int slot, size_t base, uint32_t n, DedupRun& R) {
   LCV_TRY(ensure_dedup(ctx, n, slot));
   be_set_slot(ctx, slot);
@@ -974,7 +912,7 @@ int lcv_batch_upload(lcv_ctx* ctx, const lcv_update_batch* hb, lcv_dbatch** out)
 }
 
 // a resident batch that carries its store_index column: every resident entry validates it against the store
-// table of the moment of the call (validate_impl checks the recorded largest index against that table)
+// table of the moment of the call (validate_prepare checks the recorded largest index against that table)
 int lcv_batch_upload_stores(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index, lcv_dbatch** out) {
   if (!store_index) return fail(ctx, LCV_EINVAL, "lcv_batch_upload_stores: null argument");
   return batch_upload(ctx, hb, store_index, out);
@@ -997,8 +935,6 @@ static BatchDev chunk_view(const BatchDev& B, size_t base, uint32_t n) {
   return c;
 }
 
-// out_host: verdict/reason to host memory; out_dev: verdicts to a device buffer
-static int host_alloc_grow(lcv_ctx* ctx, uint8_t** p, size_t* cap, size_t bytes);
 // a fold request of the _fold entries: the state going in and (synchronous form) where the result goes
 // segs (lcv_validate_stores_fold): a segmented fold of a store-table batch — `in` is unused, `out` is indexed by
 // store row, and seg_dev points at the grouping's columns in the batch's device copy (seg_bind)
@@ -1014,36 +950,25 @@ static int fold_state_in(lcv_ctx* ctx, const char* who, const lcv_fold_state* in
 }
 // F_fold over the first n rows of the active work space, on the current stream (after F_verdict in stream order)
 static int fold_stage(lcv_ctx* ctx, const FoldState& in, uint64_t store_fin_slot, uint32_t next_known, uint32_t n) {
-  be_stage_begin(ctx, ST_FOLD);
-  LCV_TRY(be_launch_team(ctx, F_fold{ctx->W, in, store_fin_slot, next_known, n}, 1));
-  be_stage_end(ctx, ST_FOLD);
-  return LCV_OK;
+  return stage(ctx, ST_FOLD, [&] { return be_launch_team(ctx, F_fold{ctx->W, in, store_fin_slot, next_known, n}, 1); });
 }
-// the segmented fold's device side.  seg_bind: the grouping's columns of a staged batch (batch_cols 14-17) in its
+// the segmented fold's device side.  seg_bind: the grouping's columns of a staged batch (COL_SEG_*) in its
 // device copy m.  ensure_fold_seg: the slot's result buffer (be_free waits for the streams).  fold_seg_stage:
 // F_fold_seg, one team per store present, where fold_stage would run F_fold
 static void seg_bind(FoldReq& f, uint8_t* m, const BatchCols& c) {
-  f.seg_dev.seg_store = (const uint32_t*)(m + c.off[14]);
-  f.seg_dev.seg_off = (const uint32_t*)(m + c.off[15]);
-  f.seg_dev.seg_row = (const uint32_t*)(m + c.off[16]);
-  f.seg_dev.in = m + c.off[17];
+  f.seg_dev.seg_store = (const uint32_t*)(m + c.off[COL_SEG_STORE]);
+  f.seg_dev.seg_off = (const uint32_t*)(m + c.off[COL_SEG_OFF]);
+  f.seg_dev.seg_row = (const uint32_t*)(m + c.off[COL_SEG_ROW]);
+  f.seg_dev.in = m + c.off[COL_SEG_IN];
 }
 static int ensure_fold_seg(lcv_ctx* ctx, int slot, size_t nseg) {
   if (nseg <= ctx->seg_cap[slot] && ctx->seg_mem[slot]) return LCV_OK;
   size_t cap = 2 * ctx->seg_cap[slot] > nseg ? 2 * ctx->seg_cap[slot] : nseg;
   if (cap < 64) cap = 64;
-  if (ctx->seg_mem[slot]) be_free(ctx, ctx->seg_mem[slot]);
-  ctx->seg_mem[slot] = nullptr;
-  ctx->seg_cap[slot] = 0;
-  LCV_TRY(be_alloc(ctx, &ctx->seg_mem[slot], cap * FOLD_RESULT_BYTES));
-  ctx->seg_cap[slot] = cap;
-  return LCV_OK;
+  return dev_alloc_grow(ctx, &ctx->seg_mem[slot], &ctx->seg_cap[slot], cap, cap * FOLD_RESULT_BYTES);
 }
 static int fold_seg_stage(lcv_ctx* ctx, const Work& W, const StoreDev& S, const FoldSegDev& G, uint32_t nseg) {
-  be_stage_begin(ctx, ST_FOLD);
-  LCV_TRY(be_launch_team(ctx, F_fold_seg{W, S, G}, nseg));
-  be_stage_end(ctx, ST_FOLD);
-  return LCV_OK;
+  return stage(ctx, ST_FOLD, [&] { return be_launch_team(ctx, F_fold_seg{W, S, G}, nseg); });
 }
 // the results of a segmented fold, as they arrived (128 bytes per store present), to the caller's array indexed
 // by store row: only the present stores' entries are written
@@ -1051,10 +976,39 @@ static void fold_seg_scatter(lcv_fold_result* out, const uint8_t* res, const uin
   for (size_t g = 0; g < nseg; ++g) memcpy(&out[seg_store[g]], res + FOLD_RESULT_BYTES * g, sizeof(FoldResult));
 }
 
-static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, const uint8_t* gvr, uint8_t* verdict_host,
-                         uint8_t* reason_host, uint8_t* verdict_dev, int slot = -1, const FoldReq* fold = nullptr) {
+// What a validation is asked for: where the verdicts and reasons go — to host memory, to a device buffer, or
+// (neither) nowhere: they stay in the slot's work space — how it runs, and the fold behind it, if any
+struct ValidateReq {
+  uint8_t* verdict_host = nullptr;
+  uint8_t* reason_host = nullptr;
+  uint8_t* verdict_dev = nullptr;
+  int slot = -1;  // -1: synchronous, on slot 0 (and more for several chunks); 0..7: enqueued on that slot's streams, no wait
+  const FoldReq* fold = nullptr;
+};
+// ... and what validate_prepare settles for the schedule that serves it
+struct ValidateRun {
+  lcv_ctx* ctx;
+  lcv_dbatch* db;
+  ValidateReq q;
+  bool async;       // q.slot >= 0
+  int slot;         // the work-space slot of a one-chunk batch; its rows and items are counted there (lcv_last_dedup)
+  size_t n, cap;    // rows; rows per chunk
+  Params P;
+  CommitteeDev C;
+  const StoreDev* S;       // the store table of a batch that carries its store_index, else null
+  const FoldSegs* segs;    // a segmented fold: a table batch, its rows grouped by store
+  FoldSegDev seg_dev;
+  size_t fold_bytes;
+  bool dedup;       // lcv_set_dedup: the chunks run the BLS half once per distinct item
+  bool pinned_out = false;  // the results wait in ctx->hsync.out for validate_finish
+};
+
+// argument and state checks, the slot's work space, Params and the committee view
+static int validate_prepare(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, const uint8_t* gvr, const ValidateReq& q,
+                            ValidateRun& v) {
   if (!ctx || !db || !gvr) return fail(ctx, LCV_EINVAL, "validate: null argument");
-  const FoldSegs* segs = fold ? fold->segs : nullptr;  // a segmented fold: a table batch, its rows grouped by store
+  const FoldReq* fold = q.fold;
+  const FoldSegs* segs = fold ? fold->segs : nullptr;
   if (fold && !segs && db->B.store_index) return fail(ctx, LCV_EINVAL, "validate: no fold of a store-table batch");
   if (segs && !db->B.store_index) return fail(ctx, LCV_EINVAL, "validate: a segmented fold needs a store-table batch");
   if (fold && (db->n > LCV_FOLD_MAX_ROWS || db->n > ctx->chunk))
@@ -1072,152 +1026,192 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
   } else if (!ctx->store_set) {
     return fail(ctx, LCV_ESTATE, "validate: lcv_set_store has not been called");
   }
-  const bool async = slot >= 0;  // lcv_validate_resident_async: enqueue on the slot's streams, no wait
-  const size_t n = db->n;
-  if (async && n > ctx->chunk) return fail(ctx, LCV_EINVAL, "lcv_validate_resident_async: at most 65536 updates per call");
-  const size_t cap = n < ctx->chunk ? n : ctx->chunk;
-  be_set_slot(ctx, async ? slot : 0);
-  int rc = ensure_work(ctx, cap, db->npool, async ? slot : 0);
-  if (rc == LCV_OK && segs) rc = ensure_fold_seg(ctx, async ? slot : 0, segs->nseg);
+  v.ctx = ctx;
+  v.db = db;
+  v.q = q;
+  v.async = q.slot >= 0;  // lcv_validate_resident_async: enqueue on the slot's streams, no wait
+  v.slot = v.async ? q.slot : 0;
+  v.n = db->n;
+  if (v.async && v.n > ctx->chunk) return fail(ctx, LCV_EINVAL, "lcv_validate_resident_async: at most 65536 updates per call");
+  v.cap = v.n < ctx->chunk ? v.n : ctx->chunk;
+  be_set_slot(ctx, v.slot);
+  int rc = ensure_work(ctx, v.cap, db->npool, v.slot);
+  if (rc == LCV_OK && segs) rc = ensure_fold_seg(ctx, v.slot, segs->nseg);
   if (rc != LCV_OK) {
     be_set_slot(ctx, 0);
     return rc;
   }
-  FoldSegDev seg_dev = {};
+  v.segs = segs;
+  v.seg_dev = FoldSegDev{};
   if (segs) {
-    seg_dev = fold->seg_dev;
-    seg_dev.out = (uint8_t*)ctx->seg_mem[async ? slot : 0];
+    v.seg_dev = fold->seg_dev;
+    v.seg_dev.out = (uint8_t*)ctx->seg_mem[v.slot];
   }
-  const size_t fold_bytes = segs ? (size_t)FOLD_RESULT_BYTES * segs->nseg : (size_t)FOLD_RESULT_BYTES;
-  Params P;
-  P.cfg = ctx->cfg;
-  P.current_slot = current_slot;
-  P.store_fin_slot = ctx->store_fin_slot;
-  P.next_known = ctx->next_known;
-  for (int k = 0; k < 8; ++k) P.gvr[k] = host_be32(gvr + 4 * k);
+  v.fold_bytes = segs ? (size_t)FOLD_RESULT_BYTES * segs->nseg : (size_t)FOLD_RESULT_BYTES;
+  v.P.cfg = ctx->cfg;
+  v.P.current_slot = current_slot;
+  v.P.store_fin_slot = ctx->store_fin_slot;
+  v.P.next_known = ctx->next_known;
+  for (int k = 0; k < 8; ++k) v.P.gvr[k] = host_be32(gvr + 4 * k);
   // (the table path never reads the pool rows' store-equality flag: item_nsc_team gets a valid row to compare)
-  CommitteeDev C = table ? committee_view(ctx->table, ctx->table.raw) : committee_view(ctx->store, ctx->store.raw + K_SC);
-  const StoreDev* S = table ? &ctx->table_dev : nullptr;
-  if (!async) be_reset_timings(ctx);
-  const int ns = ctx->pipe_streams < 4 ? ctx->pipe_streams : 4;  // lcv_set_pipeline: min(streams, 4)
-  const bool piped = !async && ns > 1 && ctx->pipe_chunks > 1;
-  bool pinned_out = false;
-  // lcv_set_dedup: a chunk of a batch that has its grouping (staged) or its class column (resident) runs the BLS
-  // half once per distinct item (run_bls_dedup); otherwise, and always with the mode off, run_bls as ever.  The
-  // rows and items of the batch are summed over its chunks for lcv_last_dedup (synchronous calls: slot 0)
-  const bool dedup = dedup_on(ctx) && !piped && (db->plan_m > 0 || !db->cls.empty());
-  const int dd_slot = async ? slot : 0;
-  ctx->dd_rows[dd_slot] = ctx->dd_items[dd_slot] = 0;
-  auto bls_chunk = [&](int sl, const BatchDev& Bc, size_t base, uint32_t m, const BatchDev* nsc, bool rank) -> int {
-    ctx->dd_rows[dd_slot] += m;
-    if (!dedup) {
-      ctx->dd_items[dd_slot] += m;
-      return run_bls(ctx, Bc, C, m, 0, &P, nsc, S, rank);
-    }
-    DedupRun R;
-    LCV_TRY(dedup_chunk(ctx, db, sl, base, m, R));
-    ctx->dd_items[dd_slot] += R.m;
-    return run_bls_dedup(ctx, Bc, C, m, P, nsc, S, rank, R);
-  };
-  auto body = [&]() -> int {
-    if (piped) {  // sliced chains on `ns` streams (lcv_set_pipeline): the committee roots come first
-      be_stage_begin(ctx, ST_NSC);
-      LCV_TRY(be_launch_team(ctx, F_nsc_team{db->B, C, ctx->W}, (uint32_t)db->npool));
-      be_stage_end(ctx, ST_NSC);
-    }
-    const size_t nchunks = (n + cap - 1) / cap;
-    if (!piped && !async && nchunks > 1) {
-      // a batch of several 64k chunks: the chunks rotate over the work-space slots, up to LCV_SLOTS in
-      // flight; a slot's results are copied out (waiting for it) before the slot takes its next chunk
-      auto finish = [&](size_t c) -> int {
-        const size_t base = c * cap;
-        const uint32_t m = (uint32_t)((n - base) < cap ? (n - base) : cap);
-        be_set_slot(ctx, (int)(c % LCV_SLOTS));
-        const Work& Wc = ctx->Wslot[c % LCV_SLOTS];
-        if (verdict_host) LCV_TRY(be_d2h(ctx, verdict_host + base, Wc.verdict, m));
-        if (reason_host) LCV_TRY(be_d2h(ctx, reason_host + base, Wc.reason, m));
-        if (verdict_dev) LCV_TRY(be_d2d(ctx, verdict_dev + base, Wc.verdict, m));
-        return LCV_OK;
-      };
-      for (size_t c = 0; c < nchunks; ++c) {
-        const int sl = (int)(c % LCV_SLOTS);
-        if (c >= (size_t)LCV_SLOTS) LCV_TRY(finish(c - LCV_SLOTS));
-        be_set_slot(ctx, sl);
-        LCV_TRY(ensure_work(ctx, cap, db->npool, sl));
-        const size_t base = c * cap;
-        const uint32_t m = (uint32_t)((n - base) < cap ? (n - base) : cap);
-        // every slot's first chunk also hashes the committee pool into that slot's work space
-        LCV_TRY(bls_chunk(sl, chunk_view(db->B, base, m), base, m, c < (size_t)LCV_SLOTS ? &db->B : nullptr, false));
-      }
-      for (size_t c = nchunks > (size_t)LCV_SLOTS ? nchunks - LCV_SLOTS : 0; c < nchunks; ++c) LCV_TRY(finish(c));
-      LCV_TRY(be_sync(ctx));
-      be_collect_timings(ctx);
-      return LCV_OK;
-    }
-    for (size_t base = 0; base < n; base += cap) {
-      const uint32_t m = (uint32_t)((n - base) < cap ? (n - base) : cap);
-      BatchDev B = chunk_view(db->B, base, m);
-      if (piped && m >= 128u * (uint32_t)ctx->pipe_chunks) {
-        // slices of a whole number of waves (64 items), spread over `ns` streams
-        const uint32_t nc = (uint32_t)ctx->pipe_chunks;
-        const uint32_t sl = ((m + nc - 1) / nc + 63u) & ~63u;
-        ctx->dd_rows[dd_slot] += m;  // (never deduplicated: lcv_set_dedup refuses a multi-stream pipeline)
-        ctx->dd_items[dd_slot] += m;
-        for (int k = 1; k < ns; ++k) LCV_TRY(be_fork_to(ctx, k));
-        uint32_t c = 0;
-        for (uint32_t o = 0; o < m; o += sl, ++c) {
-          const uint32_t len = (m - o) < sl ? (m - o) : sl;
-          be_use_stream(ctx, (int)(c % (uint32_t)ns));
-          const Work Wc = work_view(ctx->W, o);
-          LCV_TRY(run_slice(ctx, chunk_view(B, o, len), C, P, S, Wc, len, fold != nullptr));
-        }
-        // results leave from the main stream once every slice has joined: a copy to pageable host
-        // memory on a slice's stream would block the host and serialise the slices
-        be_use_stream(ctx, 0);
-        for (int k = 1; k < ns; ++k) LCV_TRY(be_join_from(ctx, k));
-      } else {
-        LCV_TRY(bls_chunk(dd_slot, B, base, m, (!piped && base == 0) ? &db->B : nullptr, fold != nullptr));
-      }
-      // the fold follows the verdicts of the whole batch (one chunk) on the main stream: after F_verdict in
-      // stream order on both engines, after every slice has joined under a pipeline
-      // (a segmented fold: one team per store present, each against its own row of the table)
-      if (segs) LCV_TRY(fold_seg_stage(ctx, ctx->W, ctx->table_dev, seg_dev, segs->nseg));
-      else if (fold) LCV_TRY(fold_stage(ctx, fold->in, P.store_fin_slot, P.next_known, m));
-      if (!async && n <= cap && (verdict_host || reason_host || fold)) {
-        // one chunk: both arrays (and a fold's result) into pinned memory without a wait each, handed out after
-        // the sync below
-        HostSlot& h = ctx->hsync;
-        LCV_TRY(host_alloc_grow(ctx, &h.out, &h.out_cap, 2 * (size_t)m + fold_bytes));
-        LCV_TRY(be_d2h(ctx, h.out, ctx->W.verdict, m));
-        LCV_TRY(be_d2h(ctx, h.out + m, ctx->W.reason, m));
-        if (segs) LCV_TRY(be_d2h(ctx, h.out + 2 * (size_t)m, seg_dev.out, fold_bytes));
-        else if (fold) LCV_TRY(be_d2h(ctx, h.out + 2 * (size_t)m, ctx->W.fold_out, sizeof(FoldResult)));
-        pinned_out = true;
-      } else {
-        if (verdict_host) LCV_TRY(be_d2h(ctx, verdict_host + base, ctx->W.verdict, m));
-        if (reason_host) LCV_TRY(be_d2h(ctx, reason_host + base, ctx->W.reason, m));
-      }
-      if (verdict_dev) LCV_TRY(be_d2d(ctx, verdict_dev + base, ctx->W.verdict, m));
-    }
-    if (async) return LCV_OK;
-    LCV_TRY(be_sync(ctx));
-    if (pinned_out) {
-      if (verdict_host) memcpy(verdict_host, ctx->hsync.out, n);
-      if (reason_host) memcpy(reason_host, ctx->hsync.out + n, n);
-      if (segs && fold->out) fold_seg_scatter(fold->out, ctx->hsync.out + 2 * n, segs->store.data(), segs->nseg);
-      else if (fold && fold->out) memcpy(fold->out, ctx->hsync.out + 2 * n, sizeof(FoldResult));
-    }
-    be_collect_timings(ctx);
+  v.C = table ? committee_view(ctx->table, ctx->table.raw) : committee_view(ctx->store, ctx->store.raw + K_SC);
+  v.S = table ? &ctx->table_dev : nullptr;
+  return LCV_OK;
+}
+
+// The rows and items of the batch, summed over its chunks for lcv_last_dedup (synchronous calls: slot 0), in
+// one place.  bls_chunk: a chunk of a batch that has its grouping (staged) or its class column (resident) runs the
+// BLS half once per distinct item under lcv_set_dedup; otherwise, and always with the mode off, once per row
+static void count_items(ValidateRun& v, uint64_t rows, uint64_t items) {
+  v.ctx->dd_rows[v.slot] += rows;
+  v.ctx->dd_items[v.slot] += items;
+}
+static int bls_chunk(ValidateRun& v, int sl, const BatchDev& Bc, size_t base, uint32_t m, const BatchDev* nsc, bool rank) {
+  if (!v.dedup) {
+    count_items(v, m, m);
+    return run_bls(v.ctx, Bc, v.C, m, 0, &v.P, nsc, v.S, rank);
+  }
+  DedupRun R;
+  count_items(v, m, 0);  // (the rows count even where the grouping fails)
+  LCV_TRY(dedup_chunk(v.ctx, v.db, sl, base, m, R));
+  count_items(v, 0, R.m);
+  return run_bls(v.ctx, Bc, v.C, m, 0, &v.P, nsc, v.S, rank, &R);
+}
+
+// what follows the verdicts of rows [base, base + m) in the active work space, on the main stream: the fold
+// (after F_verdict in stream order on both engines, after every slice has joined under a pipeline; a segmented
+// fold: one team per store present, each against its own row of the table), then the copies out
+static int chunk_results(ValidateRun& v, size_t base, uint32_t m) {
+  lcv_ctx* ctx = v.ctx;
+  const ValidateReq& q = v.q;
+  if (v.segs) LCV_TRY(fold_seg_stage(ctx, ctx->W, ctx->table_dev, v.seg_dev, v.segs->nseg));
+  else if (q.fold) LCV_TRY(fold_stage(ctx, q.fold->in, v.P.store_fin_slot, v.P.next_known, m));
+  if (!v.async && v.n <= v.cap && (q.verdict_host || q.reason_host || q.fold)) {
+    // one chunk: both arrays (and a fold's result) into pinned memory without a wait each, handed out by
+    // validate_finish after its sync
+    HostSlot& h = ctx->hsync;
+    LCV_TRY(host_alloc_grow(ctx, &h.out, &h.out_cap, 2 * (size_t)m + v.fold_bytes));
+    LCV_TRY(be_d2h(ctx, h.out, ctx->W.verdict, m));
+    LCV_TRY(be_d2h(ctx, h.out + m, ctx->W.reason, m));
+    if (v.segs) LCV_TRY(be_d2h(ctx, h.out + 2 * (size_t)m, v.seg_dev.out, v.fold_bytes));
+    else if (q.fold) LCV_TRY(be_d2h(ctx, h.out + 2 * (size_t)m, ctx->W.fold_out, sizeof(FoldResult)));
+    v.pinned_out = true;
+  } else {
+    if (q.verdict_host) LCV_TRY(be_d2h(ctx, q.verdict_host + base, ctx->W.verdict, m));
+    if (q.reason_host) LCV_TRY(be_d2h(ctx, q.reason_host + base, ctx->W.reason, m));
+  }
+  if (q.verdict_dev) LCV_TRY(be_d2d(ctx, q.verdict_dev + base, ctx->W.verdict, m));
+  return LCV_OK;
+}
+// the end of a synchronous call: the wait, the results out of pinned memory, the stage timings
+static int validate_finish(ValidateRun& v) {
+  lcv_ctx* ctx = v.ctx;
+  const ValidateReq& q = v.q;
+  LCV_TRY(be_sync(ctx));
+  if (v.pinned_out) {
+    const uint8_t* out = ctx->hsync.out;
+    if (q.verdict_host) memcpy(q.verdict_host, out, v.n);
+    if (q.reason_host) memcpy(q.reason_host, out + v.n, v.n);
+    if (v.segs && q.fold->out) fold_seg_scatter(q.fold->out, out + 2 * v.n, v.segs->store.data(), v.segs->nseg);
+    else if (q.fold && q.fold->out) memcpy(q.fold->out, out + 2 * v.n, sizeof(FoldResult));
+  }
+  be_collect_timings(ctx);
+  return LCV_OK;
+}
+
+// Schedule 1, a synchronous batch of several chunks: the chunks rotate over the work-space slots, up to LCV_SLOTS
+// in flight; a slot's results are copied out (waiting for it) before the slot takes its next chunk
+static int validate_rotating(ValidateRun& v) {
+  lcv_ctx* ctx = v.ctx;
+  const ValidateReq& q = v.q;
+  const size_t n = v.n, cap = v.cap, nchunks = (n + cap - 1) / cap;
+  auto finish = [&](size_t c) -> int {
+    const size_t base = c * cap;
+    const uint32_t m = (uint32_t)((n - base) < cap ? (n - base) : cap);
+    be_set_slot(ctx, (int)(c % LCV_SLOTS));
+    const Work& Wc = ctx->Wslot[c % LCV_SLOTS];
+    if (q.verdict_host) LCV_TRY(be_d2h(ctx, q.verdict_host + base, Wc.verdict, m));
+    if (q.reason_host) LCV_TRY(be_d2h(ctx, q.reason_host + base, Wc.reason, m));
+    if (q.verdict_dev) LCV_TRY(be_d2d(ctx, q.verdict_dev + base, Wc.verdict, m));
     return LCV_OK;
   };
-  const bool marks_were_off = ctx->marks_off;
-  if (async) {
-    ctx->marks_off = true;  // nothing collects an asynchronous batch's stage marks
-    ctx->hslot[slot].staged = false;
-    ctx->hslot[slot].folded = false;
-    ctx->hslot[slot].seg_folded = false;
+  for (size_t c = 0; c < nchunks; ++c) {
+    const int sl = (int)(c % LCV_SLOTS);
+    if (c >= (size_t)LCV_SLOTS) LCV_TRY(finish(c - LCV_SLOTS));
+    be_set_slot(ctx, sl);
+    LCV_TRY(ensure_work(ctx, cap, v.db->npool, sl));
+    const size_t base = c * cap;
+    const uint32_t m = (uint32_t)((n - base) < cap ? (n - base) : cap);
+    // every slot's first chunk also hashes the committee pool into that slot's work space
+    LCV_TRY(bls_chunk(v, sl, chunk_view(v.db->B, base, m), base, m, c < (size_t)LCV_SLOTS ? &v.db->B : nullptr, false));
   }
-  rc = body();
+  for (size_t c = nchunks > (size_t)LCV_SLOTS ? nchunks - LCV_SLOTS : 0; c < nchunks; ++c) LCV_TRY(finish(c));
+  LCV_TRY(be_sync(ctx));
+  be_collect_timings(ctx);
+  return LCV_OK;
+}
+
+// Schedule 2, the sliced pipeline (lcv_set_pipeline, synchronous, never deduplicated): the committee roots come
+// first; then each chunk is cut into pipe_chunks slices of a whole number of waves (64 items), whose chains
+// (run_slice) are spread over `ns` streams.  A chunk too small to slice runs the two-stream schedule
+static int validate_sliced(ValidateRun& v, int ns) {
+  lcv_ctx* ctx = v.ctx;
+  lcv_dbatch* db = v.db;
+  const bool rank = v.q.fold != nullptr;
+  LCV_TRY(stage(ctx, ST_NSC, [&] { return be_launch_team(ctx, F_nsc_team{db->B, v.C, ctx->W}, (uint32_t)db->npool); }));
+  for (size_t base = 0; base < v.n; base += v.cap) {
+    const uint32_t m = (uint32_t)((v.n - base) < v.cap ? (v.n - base) : v.cap);
+    BatchDev B = chunk_view(db->B, base, m);
+    if (m >= 128u * (uint32_t)ctx->pipe_chunks) {
+      const uint32_t nc = (uint32_t)ctx->pipe_chunks;
+      const uint32_t sl = ((m + nc - 1) / nc + 63u) & ~63u;
+      count_items(v, m, m);
+      for (int k = 1; k < ns; ++k) LCV_TRY(be_fork_to(ctx, k));
+      uint32_t c = 0;
+      for (uint32_t o = 0; o < m; o += sl, ++c) {
+        const uint32_t len = (m - o) < sl ? (m - o) : sl;
+        be_use_stream(ctx, (int)(c % (uint32_t)ns));
+        const Work Wc = work_view(ctx->W, o);
+        LCV_TRY(run_slice(ctx, chunk_view(B, o, len), v.C, v.P, v.S, Wc, len, rank));
+      }
+      // results leave from the main stream once every slice has joined: a copy to pageable host
+      // memory on a slice's stream would block the host and serialise the slices
+      be_use_stream(ctx, 0);
+      for (int k = 1; k < ns; ++k) LCV_TRY(be_join_from(ctx, k));
+    } else {
+      LCV_TRY(bls_chunk(v, v.slot, B, base, m, nullptr, rank));
+    }
+    LCV_TRY(chunk_results(v, base, m));
+  }
+  return validate_finish(v);
+}
+
+// Schedule 3, one chunk on the two streams of its slot: synchronous on slot 0, or (async) enqueued on the caller's
+// slot with no wait, the results left in the slot's work space
+static int validate_single(ValidateRun& v) {
+  const uint32_t m = (uint32_t)v.n;
+  LCV_TRY(bls_chunk(v, v.slot, chunk_view(v.db->B, 0, m), 0, m, &v.db->B, v.q.fold != nullptr));
+  LCV_TRY(chunk_results(v, 0, m));
+  return v.async ? LCV_OK : validate_finish(v);
+}
+
+static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, const uint8_t* gvr, const ValidateReq& q) {
+  ValidateRun v;
+  LCV_TRY(validate_prepare(ctx, db, current_slot, gvr, q, v));
+  if (!v.async) be_reset_timings(ctx);
+  const int ns = ctx->pipe_streams < 4 ? ctx->pipe_streams : 4;  // lcv_set_pipeline: min(streams, 4)
+  const bool piped = !v.async && ns > 1 && ctx->pipe_chunks > 1;
+  v.dedup = dedup_on(ctx) && !piped && (db->plan_m > 0 || !db->cls.empty());
+  ctx->dd_rows[v.slot] = ctx->dd_items[v.slot] = 0;
+  const bool marks_were_off = ctx->marks_off;
+  if (v.async) {
+    ctx->marks_off = true;  // nothing collects an asynchronous batch's stage marks
+    ctx->hslot[v.slot].staged = false;
+    ctx->hslot[v.slot].folded = false;
+    ctx->hslot[v.slot].seg_folded = false;
+  }
+  const int rc = piped ? validate_sliced(v, ns) : (!v.async && v.n > v.cap) ? validate_rotating(v) : validate_single(v);
+  // whatever the schedule and its outcome: the caller's marks setting, slot 0 and its work space are the active ones again
   ctx->marks_off = marks_were_off;
   be_set_slot(ctx, 0);
   if (ctx->work_mem[0]) ctx->W = ctx->Wslot[0];
@@ -1226,12 +1220,17 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
 
 int lcv_validate_resident(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, const uint8_t* gvr, uint8_t* verdict_out,
                           uint8_t* reason_out) {
-  return validate_impl(ctx, db, current_slot, gvr, verdict_out, reason_out, nullptr);
+  ValidateReq q;
+  q.verdict_host = verdict_out;
+  q.reason_host = reason_out;
+  return validate_impl(ctx, db, current_slot, gvr, q);
 }
 
 int lcv_validate_resident_dev(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, const uint8_t* gvr,
                               uint8_t* verdict_dev) {
-  return validate_impl(ctx, db, current_slot, gvr, nullptr, nullptr, verdict_dev);
+  ValidateReq q;
+  q.verdict_dev = verdict_dev;
+  return validate_impl(ctx, db, current_slot, gvr, q);
 }
 
 // Several batches in flight: the call enqueues the whole pipeline for `db` on the streams of work-space slot
@@ -1240,7 +1239,9 @@ int lcv_validate_resident_dev(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slo
 // caller alternates slots and waits for a slot before reusing it, as a double-buffered serving loop.
 int lcv_validate_resident_async(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, const uint8_t* gvr, int slot) {
   if (!ctx || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_validate_resident_async: slot must be 0..7");
-  return validate_impl(ctx, db, current_slot, gvr, nullptr, nullptr, nullptr, slot);
+  ValidateReq q;
+  q.slot = slot;
+  return validate_impl(ctx, db, current_slot, gvr, q);
 }
 
 // Host-input form of lcv_validate_resident_async (the serving path of SURVEY §8(d): host batch in, verdicts
@@ -1248,18 +1249,6 @@ int lcv_validate_resident_async(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_s
 // them to the slot's device copy on the slot's main stream — overlapping the kernels of the other slots'
 // batches — then the whole pipeline is enqueued, and the verdicts and reasons are copied back into pinned
 // host memory at the end of the slot's stream; lcv_slot_wait waits and hands them out.
-static int host_alloc_grow(lcv_ctx* ctx, uint8_t** p, size_t* cap, size_t bytes) {
-  if (bytes <= *cap && *p) return LCV_OK;
-  if (*p) be_host_free(ctx, *p);
-  *p = nullptr;
-  *cap = 0;
-  void* q = nullptr;
-  LCV_TRY(be_host_alloc(ctx, &q, bytes));
-  *p = (uint8_t*)q;
-  *cap = bytes;
-  return LCV_OK;
-}
-
 // the columns of c into dst (laid out as c), on up to 4 host threads for large batches
 static void stage_columns(uint8_t* dst, const BatchCols& c) {
   struct Piece { uint8_t* d; const uint8_t* s; size_t b; };
@@ -1289,49 +1278,67 @@ static void stage_columns(uint8_t* dst, const BatchCols& c) {
   for (auto& x : th) x.join();
 }
 
-static int store_index_check(lcv_ctx* ctx, const char* who, const uint32_t* store_index, uint64_t n);
+// A one-chunk host batch into the HostSlot h: its columns (with a segmented fold's grouping `segs` and, under
+// lcv_set_dedup, its grouping into BLS items: both travel with the batch) go through h's reused pinned staging
+// buffer and ONE DMA into h's reused device copy, on the slot's main stream, instead of a device allocation, one
+// copy per column and a free per call; h.db then names the device columns, and fold->seg_dev the grouping's.
+// slot < 0: the synchronous entries, h = ctx->hsync, on slot 0.  slot >= 0 (lcv_validate_async and its kin, h =
+// ctx->hslot[slot]): the staging buffer is reused only after the slot's previous batch has left it (EV_H2D,
+// recorded behind the copy), the slot is waited for before a buffer it may still use is regrown, h.out is grown
+// for the verdicts, the reasons and a fold's result (a segmented fold's: one per store present), and slot 0 is
+// the active one again on return
+static int stage_host_batch(lcv_ctx* ctx, const char* who, const lcv_update_batch* hb, const uint32_t* store_index,
+                            FoldReq* fold, int slot, HostSlot& h, BatchCols& c) {
+  const bool async = slot >= 0;
+  const FoldSegs* segs = fold ? fold->segs : nullptr;
+  DedupCols dd;
+  LCV_TRY(dedup_stage(ctx, who, hb, store_index, dd));
+  LCV_TRY(batch_cols(ctx, hb, c, who, store_index, segs, dd.m ? &dd : nullptr));
+  be_set_slot(ctx, async ? slot : 0);
+  const size_t out_bytes = 2 * c.n + (size_t)FOLD_RESULT_BYTES * (segs ? segs->nseg : 1);
+  int rc = async ? be_wait_event(ctx, EV_H2D) : LCV_OK;
+  if (async && rc == LCV_OK && (c.total > h.pinned_cap || out_bytes > h.out_cap)) rc = be_sync_slot(ctx);
+  if (rc == LCV_OK) rc = host_alloc_grow(ctx, &h.pinned, &h.pinned_cap, c.total);
+  if (async && rc == LCV_OK) rc = host_alloc_grow(ctx, &h.out, &h.out_cap, out_bytes);
+  if (rc == LCV_OK) rc = dev_alloc_grow(ctx, &h.dev, &h.dev_cap, c.total, c.total);
+  if (rc == LCV_OK) {
+    stage_columns(h.pinned, c);
+    be_set_slot(ctx, async ? slot : 0);  // (be_free above may not keep the slot)
+    rc = be_h2d(ctx, h.dev, h.pinned, c.total);
+    if (async && rc == LCV_OK) rc = be_mark(ctx, EV_H2D, 0);
+  }
+  if (async) be_set_slot(ctx, 0);
+  if (rc != LCV_OK) return rc;
+  bind_batch(&h.db, (uint8_t*)h.dev, c);
+  if (segs) seg_bind(*fold, (uint8_t*)h.dev, c);
+  return LCV_OK;
+}
+
+// every store_index of a host batch against the table that is set, naming the first offending row
+static int store_index_check(lcv_ctx* ctx, const char* who, const uint32_t* store_index, uint64_t n) {
+  for (uint64_t i = 0; i < n; ++i)
+    if (store_index[i] >= ctx->table_dev.nstore)
+      return fail(ctx, LCV_EINVAL, std::string(who) + ": store_index[" + std::to_string(i) + "] = " +
+                                       std::to_string(store_index[i]) + " is not a store row (nstore " +
+                                       std::to_string(ctx->table_dev.nstore) + ")");
+  return LCV_OK;
+}
 // store_index null: against the context's store (lcv_validate_async); else row by row against the store table
 // (lcv_validate_stores_async), the 14th column staged with the others
 static int validate_async_host(lcv_ctx* ctx, const char* who, const lcv_update_batch* hb, const uint32_t* store_index,
                                uint64_t current_slot, const uint8_t* gvr, int slot, FoldReq* fold = nullptr) {
   const FoldSegs* segs = fold ? fold->segs : nullptr;  // (a segmented fold's grouping has checked every index)
   if (store_index && !segs) LCV_TRY(store_index_check(ctx, who, store_index, hb->n));  // before the DMA
-  DedupCols dd;
-  LCV_TRY(dedup_stage(ctx, who, hb, store_index, dd));  // lcv_set_dedup: the grouping travels with the batch
-  BatchCols c;
-  LCV_TRY(batch_cols(ctx, hb, c, who, store_index, segs, dd.m ? &dd : nullptr));
   HostSlot& h = ctx->hslot[slot];
-  be_set_slot(ctx, slot);
-  // the staging buffer is reused only after the slot's previous batch has left it
-  int rc = be_wait_event(ctx, EV_H2D);
-  // verdicts, reasons, a fold's result (a segmented fold's: one per store present)
-  const size_t out_bytes = 2 * c.n + (size_t)FOLD_RESULT_BYTES * (segs ? segs->nseg : 1);
-  if (rc == LCV_OK && (c.total > h.pinned_cap || out_bytes > h.out_cap)) rc = be_sync_slot(ctx);
-  if (rc == LCV_OK) rc = host_alloc_grow(ctx, &h.pinned, &h.pinned_cap, c.total);
-  if (rc == LCV_OK) rc = host_alloc_grow(ctx, &h.out, &h.out_cap, out_bytes);
-  if (rc == LCV_OK && (c.total > h.dev_cap || !h.dev)) {
-    if (h.dev) be_free(ctx, h.dev);
-    h.dev = nullptr;
-    h.dev_cap = 0;
-    rc = be_alloc(ctx, &h.dev, c.total);
-    if (rc == LCV_OK) h.dev_cap = c.total;
-  }
-  if (rc != LCV_OK) {
-    be_set_slot(ctx, 0);
-    return rc;
-  }
-  stage_columns(h.pinned, c);
-  be_set_slot(ctx, slot);  // (be_free above may not keep the slot)
-  rc = be_h2d(ctx, h.dev, h.pinned, c.total);
-  if (rc == LCV_OK) rc = be_mark(ctx, EV_H2D, 0);
-  be_set_slot(ctx, 0);
-  if (rc != LCV_OK) return rc;
-  bind_batch(&h.db, (uint8_t*)h.dev, c);
-  if (segs) seg_bind(*fold, (uint8_t*)h.dev, c);
-  LCV_TRY(validate_impl(ctx, &h.db, current_slot, gvr, nullptr, nullptr, nullptr, slot, fold));
+  BatchCols c;
+  LCV_TRY(stage_host_batch(ctx, who, hb, store_index, fold, slot, h, c));
+  ValidateReq q;
+  q.slot = slot;
+  q.fold = fold;
+  LCV_TRY(validate_impl(ctx, &h.db, current_slot, gvr, q));
   be_set_slot(ctx, slot);
   const Work& W = ctx->Wslot[slot];
-  rc = be_d2h(ctx, h.out, W.verdict, c.n);
+  int rc = be_d2h(ctx, h.out, W.verdict, c.n);
   if (rc == LCV_OK) rc = be_d2h(ctx, h.out + c.n, W.reason, c.n);
   if (rc == LCV_OK && segs) rc = be_d2h(ctx, h.out + 2 * c.n, ctx->seg_mem[slot], (size_t)FOLD_RESULT_BYTES * segs->nseg);
   else if (rc == LCV_OK && fold) rc = be_d2h(ctx, h.out + 2 * c.n, W.fold_out, sizeof(FoldResult));
@@ -1398,37 +1405,21 @@ int lcv_slot_wait(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint
 static int validate_host(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index, uint64_t current_slot,
                          const uint8_t* gvr, uint8_t* verdict_out, uint8_t* reason_out, FoldReq* fold = nullptr) {
   const bool table = store_index != nullptr;
+  ValidateReq q;
+  q.verdict_host = verdict_out;
+  q.reason_host = reason_out;
+  q.fold = fold;
   if (ctx && hb && gvr && (table ? ctx->table_set : ctx->store_set) && hb->n > 0 && hb->n <= ctx->chunk) {
-    // one chunk (the reference's per-update call shape among them): the columns go through a reused pinned
-    // staging buffer and ONE DMA into a reused device copy (lcv_validate_async's path, waited for here)
-    // instead of a device allocation, one copy per column and a free per call
-    DedupCols dd;
-    LCV_TRY(dedup_stage(ctx, "lcv_validate_updates", hb, store_index, dd));  // lcv_set_dedup
+    // one chunk (the reference's per-update call shape among them): staged like lcv_validate_async's, waited for here
     BatchCols c;
-    LCV_TRY(batch_cols(ctx, hb, c, "lcv_validate_updates", store_index, fold ? fold->segs : nullptr, dd.m ? &dd : nullptr));
-    HostSlot& h = ctx->hsync;
-    be_set_slot(ctx, 0);
-    int rc = host_alloc_grow(ctx, &h.pinned, &h.pinned_cap, c.total);
-    if (rc == LCV_OK && (c.total > h.dev_cap || !h.dev)) {
-      if (h.dev) be_free(ctx, h.dev);
-      h.dev = nullptr;
-      h.dev_cap = 0;
-      rc = be_alloc(ctx, &h.dev, c.total);
-      if (rc == LCV_OK) h.dev_cap = c.total;
-    }
-    if (rc != LCV_OK) return rc;
-    stage_columns(h.pinned, c);
-    be_set_slot(ctx, 0);
-    LCV_TRY(be_h2d(ctx, h.dev, h.pinned, c.total));
-    bind_batch(&h.db, (uint8_t*)h.dev, c);
-    if (fold && fold->segs) seg_bind(*fold, (uint8_t*)h.dev, c);
-    return validate_impl(ctx, &h.db, current_slot, gvr, verdict_out, reason_out, nullptr, -1, fold);  // returns synced
+    LCV_TRY(stage_host_batch(ctx, "lcv_validate_updates", hb, store_index, fold, -1, ctx->hsync, c));
+    return validate_impl(ctx, &ctx->hsync.db, current_slot, gvr, q);  // returns synced
   }
   if (fold) return fail(ctx, LCV_EINVAL, "lcv_validate_fold: null argument, no store set, or not 0 < n <= one chunk");
   // larger batches (and invalid arguments, reported by the upload): a device batch per call
   lcv_dbatch* db = nullptr;
   LCV_TRY(batch_upload(ctx, hb, store_index, &db));
-  int rc = validate_impl(ctx, db, current_slot, gvr, verdict_out, reason_out, nullptr);
+  int rc = validate_impl(ctx, db, current_slot, gvr, q);
   lcv_batch_free(ctx, db);
   return rc;
 }
@@ -1497,9 +1488,9 @@ int lcv_debug_fold(lcv_ctx* ctx, const uint8_t* rank, const uint8_t* verdict, ui
   auto body = [&]() -> int {
     LCV_TRY(be_h2d(ctx, W.rank, rank, rank_index((size_t)n)));
     LCV_TRY(be_h2d(ctx, W.verdict, verdict, (size_t)n));
-    be_stage_begin(ctx, ST_FOLD);
-    LCV_TRY(be_launch_team(ctx, F_fold{W, s, store_finalized_slot, next_known ? 1u : 0u, (uint32_t)n}, 1));
-    be_stage_end(ctx, ST_FOLD);
+    LCV_TRY(stage(ctx, ST_FOLD, [&] {
+      return be_launch_team(ctx, F_fold{W, s, store_finalized_slot, next_known ? 1u : 0u, (uint32_t)n}, 1);
+    }));
     LCV_TRY(be_d2h(ctx, &res, W.fold_out, sizeof(res)));
     return be_sync(ctx);
   };
@@ -1630,16 +1621,6 @@ int lcv_set_store_table(lcv_ctx* ctx, const lcv_store_table* t, uint8_t* key_sta
   ctx->tab_cur.swap(host_cur);
   ctx->tab_next.swap(next);
   ctx->table_set = true;
-  return LCV_OK;
-}
-
-// every store_index of a host batch against the table that is set, naming the first offending row
-static int store_index_check(lcv_ctx* ctx, const char* who, const uint32_t* store_index, uint64_t n) {
-  for (uint64_t i = 0; i < n; ++i)
-    if (store_index[i] >= ctx->table_dev.nstore)
-      return fail(ctx, LCV_EINVAL, std::string(who) + ": store_index[" + std::to_string(i) + "] = " +
-                                       std::to_string(store_index[i]) + " is not a store row (nstore " +
-                                       std::to_string(ctx->table_dev.nstore) + ")");
   return LCV_OK;
 }
 
@@ -1933,9 +1914,11 @@ int lcv_validate_sharded(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
   uint8_t* send = ctx->comm_buf;
   uint8_t* recv = ctx->comm_buf + per_rank;
   // only the padding tail is zeroed: the verdicts [0, n) are written by the chunks' own slot streams
-  // (validate_impl), which nothing orders after a memset on this stream
+  // (validate_rotating), which nothing orders after a memset on this stream
   LCV_TRY(be_memset(ctx, send + db->n, 0, per_rank - db->n));
-  LCV_TRY(validate_impl(ctx, db, current_slot, gvr, nullptr, nullptr, send));
+  ValidateReq q;
+  q.verdict_dev = send;
+  LCV_TRY(validate_impl(ctx, db, current_slot, gvr, q));
   LCV_TRY(be_comm_allgather(ctx, send, recv, per_rank));
   LCV_TRY(be_comm_wait(ctx));  // bounded, and before the copy into pageable caller memory (lcv_slot_allgather)
   LCV_TRY(be_d2h(ctx, verdict_all_out, recv, per_rank * R));
@@ -2495,16 +2478,9 @@ static int prod_views(lcv_ctx* ctx, const lcv_state_views* s, uint64_t ns, const
   PW.pool_cap = (uint32_t)ncomm;
   PW.nsc_root = (uint32_t*)(m + o_root);
   PW.nsc_flags = m + o_flag;
-  be_stage_begin(ctx, ST_PRODUCE_VIEWS);
-  LCV_TRY(be_launch_team(ctx, F_nsc_team{PB, PC, PW}, (uint32_t)ncomm));
-  be_stage_end(ctx, ST_PRODUCE_VIEWS);
-  be_stage_begin(ctx, ST_PRODUCE_VIEWS);
-  LCV_TRY(be_launch(ctx, F_prod_block{R.K, R.X}, (uint32_t)nb));
-  be_stage_end(ctx, ST_PRODUCE_VIEWS);
-  be_stage_begin(ctx, ST_PRODUCE_VIEWS);
-  LCV_TRY(be_launch(ctx, F_prod_state{R.S, R.X}, (uint32_t)ns));
-  be_stage_end(ctx, ST_PRODUCE_VIEWS);
-  return LCV_OK;
+  LCV_TRY(stage(ctx, ST_PRODUCE_VIEWS, [&] { return be_launch_team(ctx, F_nsc_team{PB, PC, PW}, (uint32_t)ncomm); }));
+  LCV_TRY(stage(ctx, ST_PRODUCE_VIEWS, [&] { return be_launch(ctx, F_prod_block{R.K, R.X}, (uint32_t)nb); }));
+  return stage(ctx, ST_PRODUCE_VIEWS, [&] { return be_launch(ctx, F_prod_state{R.S, R.X}, (uint32_t)ns); });
 }
 
 static ProdOut prod_out(const BatchDev& B) {
@@ -2570,14 +2546,14 @@ int lcv_create_updates_resident(lcv_ctx* ctx, const lcv_state_views* states, uin
   ProdRun R;
   be_reset_timings(ctx);
   auto body = [&]() -> int {
-    LCV_TRY(be_h2d(ctx, m + c.off[6], committees, (size_t)K_SC * ncomm));
-    LCV_TRY(be_memset(ctx, m + c.off[6] + (size_t)K_SC * ncomm, 0, K_SC));
+    LCV_TRY(be_h2d(ctx, m + c.off[COL_NSC_POOL], committees, (size_t)K_SC * ncomm));
+    LCV_TRY(be_memset(ctx, m + c.off[COL_NSC_POOL] + (size_t)K_SC * ncomm, 0, K_SC));
     const void* ix[5] = {cases->state, cases->block, cases->attested_state, cases->attested_block, cases->finalized_block};
     LCV_TRY(prod_views(ctx, states, ns, blocks, nb, committees, db->B.nsc_pool, ncomm, ix, 5, n, 0, R));
-    be_stage_begin(ctx, ST_PRODUCE_ROWS);
-    LCV_TRY(be_launch_team(ctx, F_prod_rows{R.S, R.K, R.C, R.X, prod_out(db->B), ctx->cfg, (uint32_t)kind,
-                                            (uint32_t)ncomm, R.reason}, (uint32_t)n));
-    be_stage_end(ctx, ST_PRODUCE_ROWS);
+    LCV_TRY(stage(ctx, ST_PRODUCE_ROWS, [&] {
+      return be_launch_team(ctx, F_prod_rows{R.S, R.K, R.C, R.X, prod_out(db->B), ctx->cfg, (uint32_t)kind,
+                                             (uint32_t)ncomm, R.reason}, (uint32_t)n);
+    }));
     LCV_TRY(be_d2h(ctx, reason_out, R.reason, n));
     LCV_TRY(be_sync(ctx));
     be_collect_timings(ctx);
@@ -2681,9 +2657,9 @@ int lcv_create_bootstraps(lcv_ctx* ctx, const lcv_state_views* states, uint64_t 
     LCV_TRY(prod_views(ctx, states, ns, blocks, nb, committees, nullptr, ncomm, ix, 2, n, extra, R));
     uint8_t* e = R.extra;
     const ProdBootOut O = {e + off[0], e + off[1], e + off[2], (uint32_t*)(e + off[3]), e + off[4], R.reason};
-    be_stage_begin(ctx, ST_PRODUCE_ROWS);
-    LCV_TRY(be_launch_team(ctx, F_prod_boot{R.S, R.K, R.idx0, R.idx1, R.X, O, ctx->cfg, (uint32_t)ncomm}, (uint32_t)n));
-    be_stage_end(ctx, ST_PRODUCE_ROWS);
+    LCV_TRY(stage(ctx, ST_PRODUCE_ROWS, [&] {
+      return be_launch_team(ctx, F_prod_boot{R.S, R.K, R.idx0, R.idx1, R.X, O, ctx->cfg, (uint32_t)ncomm}, (uint32_t)n);
+    }));
     void* dst[5] = {beacon112, exec832, exec_branch128, committee_index, committee_branch160};
     for (int k = 0; k < 5; ++k) LCV_TRY(be_d2h(ctx, dst[k], e + off[k], width[k] * n));
     LCV_TRY(be_d2h(ctx, reason_out, R.reason, n));

@@ -1,5 +1,5 @@
-// lcv_hip.hip — HIP/gfx950 backend of liblcv.so (the product): streams, memory, events and the
-// C ABI (lcv_driver.inc).  One lane per item; every stage of lcv_items.hpp is one kernel launch on
+// lcv_hip.hip — HIP/gfx950 backend of liblcv.so (the product): streams, memory, events (lcv_backend.hpp)
+// under the C ABI (lcv_driver.inc).  One lane per item; every stage of lcv_items.hpp is one kernel launch on
 // the context's stream; HIP events bracket the stages so the per-stage kernel time is reported by
 // lcv_last_timings() (and cross-checked with rocprofv3).  The kernels themselves live in the
 // lcv_k_*.hip units (one heavy stage per unit so they compile in parallel).
@@ -35,53 +35,14 @@ struct Backend {
   hipEvent_t open_ev[BE_STREAMS] = {};
   hipEvent_t fork_ev[BE_STREAMS] = {}, join_ev[BE_STREAMS] = {};
   int base = 0;                          // work-space slot s uses streams st[2s] (main), st[2s + 1] (side)
-  hipEvent_t ev[LCV_SLOTS][EV_COUNT] = {};  // run_bls's ordering events, per slot
+  hipEvent_t ev[LCV_SLOTS][EV_COUNT] = {};  // the ordering events of run_bls and of staging, per slot
   ncclComm_t comm = nullptr;  // RCCL communicator (lcv_comm_init), collectives on st[0]
   double* comm_scalar = nullptr;       // device scalar of lcv_comm_allreduce_max
   double* comm_host_scalar = nullptr;  // its pinned host staging (copies never block the bounded wait)
   uint32_t* hold_flag = nullptr;       // lcv_debug_hold_slot's release word: pinned, mapped, this context's
 };
 
-static int be_init(lcv_ctx* ctx, int device);
-static void be_destroy(lcv_ctx* ctx);
-static int be_alloc(lcv_ctx* ctx, void** p, size_t bytes);
-static void be_free(lcv_ctx* ctx, void* p);
-static int be_h2d(lcv_ctx* ctx, void* dst, const void* src, size_t bytes);
-static int be_d2h(lcv_ctx* ctx, void* dst, const void* src, size_t bytes);
-static int be_d2d(lcv_ctx* ctx, void* dst, const void* src, size_t bytes);
-static int be_memset(lcv_ctx* ctx, void* p, int v, size_t bytes);
-static int be_sync(lcv_ctx* ctx);
-static int be_fork_to(lcv_ctx* ctx, int k);
-static int be_join_from(lcv_ctx* ctx, int k);
-static int be_nstreams() { return BE_STREAMS; }
-template <class F> static int be_launch(lcv_ctx* ctx, const F& f, uint32_t n);
-template <class F> static int be_launch_team(lcv_ctx* ctx, const F& f, uint32_t n);
-template <class F> static int be_launch_sop(lcv_ctx* ctx, const F& f, uint32_t n, uint32_t g);
-template <class F> static int be_launch_sop_fan(lcv_ctx* ctx, const F& f, uint32_t n);
-static int be_fork(lcv_ctx* ctx);
-static int be_join(lcv_ctx* ctx);
-static void be_use_stream(lcv_ctx* ctx, int k);
-static void be_set_slot(lcv_ctx* ctx, int slot);
-static int be_mark(lcv_ctx* ctx, int ev, int k);
-static int be_wait(lcv_ctx* ctx, int k, int ev);
-static int be_sync_slot(lcv_ctx* ctx);
-static void be_stage_begin(lcv_ctx* ctx, int stage);
-static void be_stage_end(lcv_ctx* ctx, int stage);
-static void be_reset_timings(lcv_ctx* ctx);
-static void be_collect_timings(lcv_ctx* ctx);
-static int be_comm_unique_id(uint8_t* id);
-static int be_comm_init(lcv_ctx* ctx, int nranks, int rank, const uint8_t* id);
-static void be_comm_destroy(lcv_ctx* ctx);
-static int be_comm_allgather(lcv_ctx* ctx, const uint8_t* send, uint8_t* recv, size_t per_rank);
-static int be_comm_allreduce_max(lcv_ctx* ctx, double* inout);
-static int be_comm_count(lcv_ctx* ctx, int* out);
-static int be_comm_wait(lcv_ctx* ctx);
-static int be_comm_shrink(lcv_ctx* ctx, const int* exclude, int nexclude, int* rank, int* nranks);
-static void be_comm_abort(lcv_ctx* ctx);
-static int be_host_alloc(lcv_ctx* ctx, void** p, size_t bytes);
-static void be_host_free(lcv_ctx* ctx, void* p);
-static int be_wait_event(lcv_ctx* ctx, int ev);
-static size_t be_event_pool_size(lcv_ctx* ctx);
+#include "lcv_backend.hpp"
 
 #include "lcv_driver.inc"
 #include "lcv_launch.hpp"
@@ -221,8 +182,6 @@ static int be_join_from(lcv_ctx* ctx, int k) {
   HIPCHK(ctx, hipStreamWaitEvent(ctx->be.st[b], ctx->be.join_ev[b + k], 0));
   return LCV_OK;
 }
-static int be_fork(lcv_ctx* ctx) { return be_fork_to(ctx, 1); }
-static int be_join(lcv_ctx* ctx) { return be_join_from(ctx, 1); }
 
 template <class F> static int be_launch(lcv_ctx* ctx, const F& f, uint32_t n) {
   if (n == 0) return LCV_OK;

@@ -38,48 +38,19 @@ struct Backend {
   unsigned long long comm_round = 0;
 };
 
-static int be_init(lcv_ctx* ctx, int device);
-static void be_destroy(lcv_ctx* ctx);
-static int be_alloc(lcv_ctx* ctx, void** p, size_t bytes);
-static void be_free(lcv_ctx* ctx, void* p);
-static int be_h2d(lcv_ctx* ctx, void* dst, const void* src, size_t bytes);
-static int be_d2h(lcv_ctx* ctx, void* dst, const void* src, size_t bytes);
-static int be_d2d(lcv_ctx* ctx, void* dst, const void* src, size_t bytes);
-static int be_memset(lcv_ctx* ctx, void* p, int v, size_t bytes);
-static int be_sync(lcv_ctx* ctx);
-template <class F> static int be_launch(lcv_ctx* ctx, const F& f, uint32_t n);
-template <class F> static int be_launch_team(lcv_ctx* ctx, const F& f, uint32_t n);
-template <class F> static int be_launch_sop(lcv_ctx* ctx, const F& f, uint32_t n, uint32_t g = 0);
-// the latency engine's launches run the same per-item code (the device spreads products over lanes)
+#include "lcv_backend.hpp"
+
 // the fan engine (device latency mode) computes the batch engine's values: the simulation runs the latter
-template <class F> static int be_launch_sop_fan(lcv_ctx* ctx, const F& f, uint32_t n) { return be_launch_sop(ctx, f, n); }
-static int be_fork(lcv_ctx*) { return 0; }
-static int be_join(lcv_ctx*) { return 0; }
-static void be_use_stream(lcv_ctx* ctx, int k);
-static int be_fork_to(lcv_ctx*, int) { return 0; }
-static int be_join_from(lcv_ctx*, int) { return 0; }
-static int be_nstreams() { return 4; }
-// the host simulation runs every launch in program order: slots and events order nothing
+template <class F> static int be_launch_sop_fan(lcv_ctx* ctx, const F& f, uint32_t n) { return be_launch_sop(ctx, f, n, 0u); }
+// the host simulation runs every launch in program order: slots, events, forks and joins order nothing
 static void be_set_slot(lcv_ctx*, int) {}
 static int be_mark(lcv_ctx*, int, int) { return 0; }
 static int be_wait(lcv_ctx*, int, int) { return 0; }
-static int be_sync_slot(lcv_ctx*) { return 0; }
-static void be_stage_begin(lcv_ctx* ctx, int stage);
-static void be_stage_end(lcv_ctx* ctx, int stage);
-static void be_reset_timings(lcv_ctx* ctx);
-static void be_collect_timings(lcv_ctx* ctx);
-static int be_comm_unique_id(uint8_t* id);
-static int be_comm_init(lcv_ctx* ctx, int nranks, int rank, const uint8_t* id);
-static void be_comm_destroy(lcv_ctx* ctx);
-static int be_comm_allgather(lcv_ctx* ctx, const uint8_t* send, uint8_t* recv, size_t per_rank);
-static int be_comm_allreduce_max(lcv_ctx* ctx, double* inout);
-static int be_comm_count(lcv_ctx* ctx, int* out);
-static int be_comm_wait(lcv_ctx* ctx);
-static int be_comm_shrink(lcv_ctx* ctx, const int* exclude, int nexclude, int* rank, int* nranks);
-static void be_comm_abort(lcv_ctx* ctx);
-static int be_host_alloc(lcv_ctx* ctx, void** p, size_t bytes);
-static void be_host_free(lcv_ctx*, void* p) { free(p); }
 static int be_wait_event(lcv_ctx*, int) { return 0; }
+static int be_fork_to(lcv_ctx*, int) { return 0; }
+static int be_join_from(lcv_ctx*, int) { return 0; }
+static int be_sync_slot(lcv_ctx*) { return 0; }
+static void be_host_free(lcv_ctx*, void* p) { free(p); }
 static size_t be_event_pool_size(lcv_ctx*) { return 0; }
 
 #include "lcv_driver.inc"
