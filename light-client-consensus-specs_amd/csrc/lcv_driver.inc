@@ -75,7 +75,7 @@ struct HostSlot {
   uint64_t out_n = 0;
   bool staged = false;     // out holds the slot's last batch (lcv_slot_wait reads it)
   bool folded = false;     // ... and, after its 2 out_n bytes, that batch's fold result (lcv_slot_wait_fold)
-  // ... or (lcv_validate_stores_async_fold) one 128-byte result per store present, for the store rows seg_store
+  // ... or (lcv_validate_stores_async_fold) one result (FOLD_RESULT_BYTES) per store present, for the store rows seg_store
   bool seg_folded = false;
   std::vector<uint32_t> seg_store;
   lcv_dbatch db;
@@ -115,7 +115,7 @@ struct lcv_ctx {
   size_t work_cap[LCV_SLOTS] = {}, work_pool_cap[LCV_SLOTS] = {};
   Work Wslot[LCV_SLOTS];
   Work W;  // the active slot's work space
-  // the per-store results of a segmented fold (lcv_validate_stores_fold), 128 bytes per store present: an
+  // the per-store results of a segmented fold (lcv_validate_stores_fold), FOLD_RESULT_BYTES per store present: an
   // allocation of its own per work-space slot, made by the slot's first segmented fold and grown on demand
   void* seg_mem[LCV_SLOTS] = {};
   size_t seg_cap[LCV_SLOTS] = {};
@@ -278,6 +278,74 @@ template <class F> static int launch_sop(lcv_ctx* ctx, const F& f, uint32_t n, u
   return be_launch_sop(ctx, f, n, g);
 }
 
+// ---- the work space and the deduplication scratch, each described once: one row per array of a Work (lcv_items.hpp)
+// and of a DedupDev (lcv_dedup.hpp), in allocation order — the pointer member, the element size, the elements per
+// item (`rows`) and the kind, which names the kernels' own index function.  Allocation (ensure_work, ensure_dedup),
+// slicing (work_view) and the layout check (lcv_debug_work_check) are derived from these rows and those functions;
+// nothing else states a stride.  A new array is a new member and a new row here
+enum { K_BITS = 64, K_SIG = 96 };  // Bitvector[512], a compressed G2 point: the row widths lcv_ssz.hpp does not name
+enum FieldKind { FK_SOA, FK_F, FK_LINES, FK_POOL, FK_RANK, FK_SPACE, FK_ITEM };  // (field_index)
+struct Field { const char* name; size_t slot, esize, rows; FieldKind kind; };
+#define LCV_FIELD(T, m, rows, kind) {#m, offsetof(T, m), sizeof(*T().m), rows, kind}
+static constexpr Field kWorkFields[] = {
+    LCV_FIELD(Work, msg, 8, FK_SOA),           LCV_FIELD(Work, pre_reason, 1, FK_SOA),
+    LCV_FIELD(Work, comm_id, 1, FK_SOA),       LCV_FIELD(Work, nsc_eq, 1, FK_SOA),
+    LCV_FIELD(Work, nsc_root, 8, FK_POOL),     LCV_FIELD(Work, nsc_flags, 1, FK_POOL),
+    LCV_FIELD(Work, qmap, 96, FK_SOA),         LCV_FIELD(Work, qh, 48, FK_SOA),
+    LCV_FIELD(Work, qh_inf, 1, FK_SOA),        LCV_FIELD(Work, qs, 48, FK_SOA),
+    LCV_FIELD(Work, sig_status, 1, FK_SOA),    LCV_FIELD(Work, pk, 24, FK_SOA),
+    LCV_FIELD(Work, agg_status, 1, FK_SOA),    LCV_FIELD(Work, f, F12_ITEM_WORDS, FK_F),
+    LCV_FIELD(Work, pair_ok, 1, FK_SOA),       LCV_FIELD(Work, verdict, 1, FK_SOA),
+    LCV_FIELD(Work, reason, 1, FK_SOA),        LCV_FIELD(Work, lines, SOP_LINE_WORDS, FK_LINES),
+    LCV_FIELD(Work, rank, RANK_BYTES, FK_RANK), LCV_FIELD(Work, fold_out, FOLD_RESULT_BYTES, FK_SPACE),
+};
+static constexpr Field kDedupFields[] = {
+    LCV_FIELD(DedupDev, att_beacon, K_BEACON, FK_ITEM), LCV_FIELD(DedupDev, sig_slot, 1, FK_ITEM),
+    LCV_FIELD(DedupDev, bits, K_BITS, FK_ITEM),         LCV_FIELD(DedupDev, sig, K_SIG, FK_ITEM),
+    LCV_FIELD(DedupDev, comm_id, 1, FK_ITEM),           LCV_FIELD(DedupDev, rep, 1, FK_ITEM),
+    LCV_FIELD(DedupDev, urow, 1, FK_ITEM),
+};
+// every pointer member has its row (a Work also holds cap and pool_cap in one pointer-sized word, msg_b0 in another)
+static_assert(sizeof(Work) == (2 + sizeof(kWorkFields) / sizeof(Field)) * sizeof(void*), "a Work array without a row in kWorkFields");
+static_assert(sizeof(DedupDev) == sizeof(kDedupFields) / sizeof(Field) * sizeof(void*), "a DedupDev array without a row in kDedupFields");
+
+// a pointer member of a device struct by its offset (every table here names members that way)
+static uint8_t* slot_get(const void* obj, size_t slot) {
+  uint8_t* p;
+  memcpy(&p, (const uint8_t*)obj + slot, sizeof(p));
+  return p;
+}
+static void slot_set(void* obj, size_t slot, const void* p) { memcpy((uint8_t*)obj + slot, &p, sizeof(p)); }
+
+// element r of item i of a field, in elements, as the kernels address it
+static size_t field_index(const Field& f, size_t cap, size_t pool_cap, size_t i, size_t r) {
+  switch (f.kind) {
+    case FK_SOA: return soa_index(cap, i, r);  // stride cap
+    case FK_F: return f12_index(i, (uint32_t)(r / 12)) + r % 12;
+    case FK_LINES: return lines_index(i) + r;
+    case FK_POOL: return soa_index(pool_cap, i, r);  // one item per distinct committee, not per update
+    case FK_RANK: return rank_index(i) + r;
+    case FK_SPACE: return r;              // one per work space (the fold's result): a single item
+    case FK_ITEM: return i * f.rows + r;  // item-major rows (the deduplication scratch, never sliced)
+  }
+  return 0;
+}
+static bool field_per_item(const Field& f) { return f.kind != FK_POOL && f.kind != FK_SPACE; }
+static size_t field_items(const Field& f, size_t cap, size_t pool_cap) {
+  return f.kind == FK_POOL ? pool_cap : f.kind == FK_SPACE ? 1 : cap;
+}
+// the arrays of `o` (null: the sizes only), each at the next 256-byte aligned offset of m and as long as its last
+// item's last element reaches; returns the bytes taken
+template <size_t N> static size_t fields_bind(void* o, const Field (&tab)[N], uint8_t* m, size_t cap, size_t pool_cap) {
+  size_t off = 0;
+  for (const Field& f : tab) {
+    if (o) slot_set(o, f.slot, m + off);
+    const size_t bytes = f.esize * (field_index(f, cap, pool_cap, field_items(f, cap, pool_cap) - 1, f.rows - 1) + 1);
+    off += (bytes + 255) & ~(size_t)255;
+  }
+  return off;
+}
+
 // the work space of `slot` (allocated or grown on demand; be_free waits for the streams) becomes ctx->W
 static int ensure_work(lcv_ctx* ctx, size_t cap, size_t pool_cap, int slot = 0) {
   if (cap <= ctx->work_cap[slot] && pool_cap <= ctx->work_pool_cap[slot] && ctx->work_mem[slot]) {
@@ -290,46 +358,18 @@ static int ensure_work(lcv_ctx* ctx, size_t cap, size_t pool_cap, int slot = 0) 
   if (pool_cap < 1) pool_cap = 1;
   if (ctx->work_mem[slot]) be_free(ctx, ctx->work_mem[slot]);
   ctx->work_mem[slot] = nullptr;
-  const size_t C = cap, Pc = pool_cap;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_msg = take(32 * C), o_pre = take(C), o_comm = take(4 * C), o_nsceq = take(C),
-               o_nroot = take(32 * Pc), o_nfl = take(Pc),
-               o_qmap = take(384 * C), o_qh = take(192 * C), o_qhinf = take(C), o_qs = take(192 * C), o_sst = take(C), o_pk = take(96 * C),
-               o_ast = take(C), o_f = take(576 * C), o_pok = take(C), o_ver = take(C),
-               o_rea = take(C), o_lines = take((size_t)4 * SOP_LINE_WORDS * C),
-               o_rank = take(rank_index(C)), o_fold = take(FOLD_RESULT_BYTES);
+  const size_t total = fields_bind(nullptr, kWorkFields, nullptr, cap, pool_cap);
   void* mem = nullptr;
-  LCV_TRY(be_alloc(ctx, &mem, off));
-  LCV_TRY(be_memset(ctx, mem, 0, off));
-  uint8_t* m = (uint8_t*)mem;
+  LCV_TRY(be_alloc(ctx, &mem, total));
+  LCV_TRY(be_memset(ctx, mem, 0, total));
   Work& W = ctx->Wslot[slot];
   W = Work{};
-  W.cap = (uint32_t)C;
-  W.pool_cap = (uint32_t)Pc;
-  W.msg = (uint32_t*)(m + o_msg);
-  W.pre_reason = m + o_pre;
-  W.comm_id = (uint32_t*)(m + o_comm);
-  W.nsc_root = (uint32_t*)(m + o_nroot);
-  W.nsc_flags = m + o_nfl;
-  W.nsc_eq = m + o_nsceq;
-  W.qmap = (uint32_t*)(m + o_qmap);
-  W.qh = (uint32_t*)(m + o_qh);
-  W.qh_inf = m + o_qhinf;
-  W.qs = (uint32_t*)(m + o_qs);
-  W.sig_status = m + o_sst;
-  W.pk = (uint32_t*)(m + o_pk);
-  W.agg_status = m + o_ast;
-  W.f = (uint32_t*)(m + o_f);
-  W.pair_ok = m + o_pok;
-  W.verdict = m + o_ver;
-  W.reason = m + o_rea;
-  W.lines = (uint32_t*)(m + o_lines);
-  W.rank = m + o_rank;
-  W.fold_out = m + o_fold;
+  W.cap = (uint32_t)cap;
+  W.pool_cap = (uint32_t)pool_cap;
+  fields_bind(&W, kWorkFields, (uint8_t*)mem, cap, pool_cap);
   ctx->work_mem[slot] = mem;
-  ctx->work_cap[slot] = C;
-  ctx->work_pool_cap[slot] = Pc;
+  ctx->work_cap[slot] = cap;
+  ctx->work_pool_cap[slot] = pool_cap;
   ctx->W = W;
   return LCV_OK;
 }
@@ -340,15 +380,14 @@ static int ensure_work(lcv_ctx* ctx, size_t cap, size_t pool_cap, int slot = 0) 
 static int ensure_dedup(lcv_ctx* ctx, size_t cap, int slot) {
   if (cap < ctx->work_cap[slot]) cap = ctx->work_cap[slot];
   if (cap <= ctx->dedup_cap[slot] && ctx->dedup_mem[slot]) return LCV_OK;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-  const size_t o_beacon = take((size_t)K_BEACON * cap), o_slot = take(8 * cap), o_bits = take(64 * cap),
-               o_sig = take(96 * cap), o_comm = take(4 * cap), o_rep = take(4 * cap), o_urow = take(4 * cap);
-  LCV_TRY(dev_alloc_grow(ctx, &ctx->dedup_mem[slot], &ctx->dedup_cap[slot], cap, off));
-  uint8_t* m = (uint8_t*)ctx->dedup_mem[slot];
-  ctx->Dslot[slot] = DedupDev{m + o_beacon, (uint64_t*)(m + o_slot), m + o_bits, m + o_sig, (uint32_t*)(m + o_comm),
-                              (uint32_t*)(m + o_rep), (uint32_t*)(m + o_urow)};
+  LCV_TRY(dev_alloc_grow(ctx, &ctx->dedup_mem[slot], &ctx->dedup_cap[slot], cap, fields_bind(nullptr, kDedupFields, nullptr, cap, 0)));
+  fields_bind(&ctx->Dslot[slot], kDedupFields, (uint8_t*)ctx->dedup_mem[slot], cap, 0);
   return LCV_OK;
+}
+// the BLS stages' view of a deduplicated chunk of m items: the compact columns where they read the batch's and W's
+static void dedup_batch_view(const DedupDev& D, uint32_t m, BatchDev& Bu, Work& Wu) {
+  Bu.att_beacon = D.att_beacon; Bu.sig_slot = D.sig_slot; Bu.bits = D.bits; Bu.sig = D.sig; Bu.n = m;
+  Wu.comm_id = D.comm_id;
 }
 
 static int ensure_committees(lcv_ctx* ctx, CommitteeBufs& cb, size_t ncomm, uint32_t raw_stride) {
@@ -415,16 +454,13 @@ static int upload_sop(lcv_ctx* ctx) {
   return be_sync(ctx);
 }
 
-// items [base, base + n) of the work space: every per-item array is [k][cap] + i, so a slice is the
-// same layout with the pointers advanced by `base` (the committee-pool arrays are not per item)
+// items [base, base + n) of the work space: the same layout with every per-item array advanced to its item
+// `base`, which is right because each kind's index function is additive in the item (lcv_debug_work_check (1));
+// the committee-pool arrays and the fold's result are not per item
 static Work work_view(const Work& W, size_t base) {
   Work v = W;
-  v.msg += base; v.pre_reason += base; v.comm_id += base; v.nsc_eq += base; v.qmap += base; v.qh += base; v.qh_inf += base;
-  v.qs += base; v.sig_status += base; v.pk += base; v.agg_status += base; v.pair_ok += base;
-  v.verdict += base; v.reason += base;
-  v.f += base * 144;  // item-major (lcv_items.hpp f12_st_coeff)
-  v.lines += base * (size_t)SOP_LINE_WORDS;
-  v.rank += rank_index(base);  // item-major (lcv_fold.hpp); fold_out is per work space, not per item
+  for (const Field& f : kWorkFields)
+    if (field_per_item(f)) slot_set(&v, f.slot, slot_get(&W, f.slot) + f.esize * field_index(f, W.cap, W.pool_cap, base, 0));
   return v;
 }
 
@@ -546,11 +582,7 @@ static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint3
   const uint32_t m = R ? R->m : n;
   BatchDev Bu = B;
   Work Wu = W;
-  if (R) {
-    Bu.att_beacon = R->D.att_beacon; Bu.sig_slot = R->D.sig_slot; Bu.bits = R->D.bits; Bu.sig = R->D.sig;
-    Bu.n = m;
-    Wu.comm_id = R->D.comm_id;
-  }
+  if (R) dedup_batch_view(R->D, m, Bu, Wu);
   LCV_TRY(be_mark(ctx, EV_START, 0));
   LCV_TRY(be_wait(ctx, 1, EV_START));  // the side stream starts after the slot's earlier main-stream work
   be_use_stream(ctx, 1);
@@ -713,24 +745,51 @@ struct BatchCols {
   size_t bytes[BATCH_COLS], off[BATCH_COLS];
   size_t total = 0, n = 0, np = 0;
 };
+// One row per BatchCol, in the enum's order: the bytes of an element; what counts the elements; the member of BatchDev
+// it is bound to, with the same member of ProdOut (the producer's writable view of the row columns); the member of
+// lcv_update_batch it is read from or written to (download); -1 where there is none.  Layout, sources, binding,
+// slicing and the copies out are derived from these rows: a new column is a new enum entry and a new row here
+// (ColCount, in batch_layout's order: n; np; n with a store_index; ng; ng + 1 and n in a segmented fold; n in a batch
+// staged with its grouping into BLS items; nd)
+enum ColCount { CN_ROWS, CN_POOL, CN_ROWS_IF_STORES, CN_SEGS, CN_SEGS_1, CN_ROWS_IF_SEGS, CN_ROWS_IF_ITEMS, CN_ITEMS };
+struct ColSpec { size_t width; ColCount count; int dev, prod, host; };
+#define LCV_COL_ROW(w, dev, host) {w, CN_ROWS, (int)offsetof(BatchDev, dev), (int)offsetof(ProdOut, dev), (int)offsetof(lcv_update_batch, host)}
+static constexpr ColSpec kBatchCols[] = {
+    LCV_COL_ROW(K_BEACON, att_beacon, attested.beacon),
+    LCV_COL_ROW(K_EXEC, att_exec, attested.execution),
+    LCV_COL_ROW(K_EXEC_BRANCH, att_branch, attested.exec_branch),
+    LCV_COL_ROW(K_BEACON, fin_beacon, finalized.beacon),
+    LCV_COL_ROW(K_EXEC, fin_exec, finalized.execution),
+    LCV_COL_ROW(K_EXEC_BRANCH, fin_branch, finalized.exec_branch),
+    {K_SC, CN_POOL, (int)offsetof(BatchDev, nsc_pool), -1, (int)offsetof(lcv_update_batch, nsc_pool)},
+    LCV_COL_ROW(sizeof(uint32_t), nsc_index, nsc_index),
+    LCV_COL_ROW(K_NSC_BRANCH, nsc_branch, nsc_branch),
+    LCV_COL_ROW(K_FIN_BRANCH, finality_branch, finality_branch),
+    LCV_COL_ROW(K_BITS, bits, sync_bits),
+    LCV_COL_ROW(K_SIG, sig, sync_signature),
+    LCV_COL_ROW(sizeof(uint64_t), sig_slot, signature_slot),
+    {sizeof(uint32_t), CN_ROWS_IF_STORES, (int)offsetof(BatchDev, store_index), -1, -1},
+    {sizeof(uint32_t), CN_SEGS, -1, -1, -1},          // COL_SEG_STORE
+    {sizeof(uint32_t), CN_SEGS_1, -1, -1, -1},        // COL_SEG_OFF
+    {sizeof(uint32_t), CN_ROWS_IF_SEGS, -1, -1, -1},  // COL_SEG_ROW
+    {sizeof(FoldState), CN_SEGS, -1, -1, -1},         // COL_SEG_IN
+    {sizeof(uint32_t), CN_ROWS_IF_ITEMS, -1, -1, -1}, // COL_DEDUP_REP
+    {sizeof(uint32_t), CN_ITEMS, -1, -1, -1},         // COL_DEDUP_UROW
+};
+static_assert(sizeof(kBatchCols) / sizeof(ColSpec) == BATCH_COLS, "one row per BatchCol");
+// the columns a slice advances (chunk_view) and a download copies row by row: the per-row members of BatchDev
+static bool col_per_row(const ColSpec& s) { return s.dev >= 0 && s.count != CN_POOL; }
 
 // the layout alone (no host sources): n rows, np pool rows, with a store_index column or not, ng fold segments,
 // nd BLS items (0: no grouping)
 static void batch_layout(BatchCols& c, size_t n, size_t np, bool stores, size_t ng, size_t nd = 0) {
-  size_t* b = c.bytes;
-  b[COL_ATT_BEACON] = b[COL_FIN_BEACON] = 112 * n; b[COL_ATT_EXEC] = b[COL_FIN_EXEC] = 832 * n;
-  b[COL_ATT_BRANCH] = b[COL_FIN_BRANCH] = 128 * n;
-  b[COL_NSC_POOL] = (size_t)K_SC * np; b[COL_NSC_INDEX] = 4 * n; b[COL_NSC_BRANCH] = 160 * n;
-  b[COL_FINALITY_BRANCH] = 192 * n; b[COL_BITS] = 64 * n; b[COL_SIG] = 96 * n; b[COL_SIG_SLOT] = 8 * n;
-  b[COL_STORE_INDEX] = stores ? 4 * n : 0;
-  b[COL_SEG_STORE] = 4 * ng; b[COL_SEG_OFF] = ng ? 4 * (ng + 1) : 0; b[COL_SEG_ROW] = ng ? 4 * n : 0;
-  b[COL_SEG_IN] = sizeof(FoldState) * ng;
-  b[COL_DEDUP_REP] = nd ? 4 * n : 0; b[COL_DEDUP_UROW] = 4 * nd;
+  const size_t count[] = {n, np, stores ? n : 0, ng, ng ? ng + 1 : 0, ng ? n : 0, nd ? n : 0, nd};  // by ColCount
   c.total = 0;
   for (int k = 0; k < BATCH_COLS; ++k) {
     c.src[k] = nullptr;
+    c.bytes[k] = kBatchCols[k].width * count[kBatchCols[k].count];
     c.off[k] = c.total;
-    c.total += (b[k] + 255) & ~(size_t)255;
+    c.total += (c.bytes[k] + 255) & ~(size_t)255;
   }
   c.n = n;
   c.np = np;
@@ -743,13 +802,8 @@ static int batch_cols(lcv_ctx* ctx, const lcv_update_batch* hb, BatchCols& c, co
   if (n == 0 || np == 0 || n > 0xffffffffull || np > 0xffffffffull)
     return fail(ctx, LCV_EINVAL, std::string(who) + ": need 0 < n, 0 < npool < 2^32");
   const void* src[BATCH_COLS] = {};
-  src[COL_ATT_BEACON] = hb->attested.beacon; src[COL_ATT_EXEC] = hb->attested.execution;
-  src[COL_ATT_BRANCH] = hb->attested.exec_branch;
-  src[COL_FIN_BEACON] = hb->finalized.beacon; src[COL_FIN_EXEC] = hb->finalized.execution;
-  src[COL_FIN_BRANCH] = hb->finalized.exec_branch;
-  src[COL_NSC_POOL] = hb->nsc_pool; src[COL_NSC_INDEX] = hb->nsc_index; src[COL_NSC_BRANCH] = hb->nsc_branch;
-  src[COL_FINALITY_BRANCH] = hb->finality_branch;
-  src[COL_BITS] = hb->sync_bits; src[COL_SIG] = hb->sync_signature; src[COL_SIG_SLOT] = hb->signature_slot;
+  for (int k = 0; k < BATCH_COLS; ++k)
+    if (kBatchCols[k].host >= 0) src[k] = slot_get(hb, kBatchCols[k].host);
   src[COL_STORE_INDEX] = store_index;
   if (ng) {
     src[COL_SEG_STORE] = segs->store.data(); src[COL_SEG_OFF] = segs->off.data();
@@ -769,12 +823,9 @@ static int batch_cols(lcv_ctx* ctx, const lcv_update_batch* hb, BatchCols& c, co
 static void bind_batch(lcv_dbatch* db, uint8_t* m, const BatchCols& c) {
   auto at = [&](BatchCol k) { return m + c.off[k]; };
   BatchDev& B = db->B;
-  B.att_beacon = at(COL_ATT_BEACON); B.att_exec = at(COL_ATT_EXEC); B.att_branch = at(COL_ATT_BRANCH);
-  B.fin_beacon = at(COL_FIN_BEACON); B.fin_exec = at(COL_FIN_EXEC); B.fin_branch = at(COL_FIN_BRANCH);
-  B.nsc_pool = at(COL_NSC_POOL); B.nsc_index = (const uint32_t*)at(COL_NSC_INDEX); B.nsc_branch = at(COL_NSC_BRANCH);
-  B.finality_branch = at(COL_FINALITY_BRANCH); B.bits = at(COL_BITS); B.sig = at(COL_SIG);
-  B.sig_slot = (const uint64_t*)at(COL_SIG_SLOT);
-  B.store_index = c.bytes[COL_STORE_INDEX] ? (const uint32_t*)at(COL_STORE_INDEX) : nullptr;
+  for (int k = 0; k < BATCH_COLS; ++k)  // an optional column that the batch does not carry is null
+    if (kBatchCols[k].dev >= 0)
+      slot_set(&B, kBatchCols[k].dev, k < BATCH_COLS_REQUIRED || c.bytes[k] ? at((BatchCol)k) : nullptr);
   B.n = (uint32_t)c.n;
   B.npool = (uint32_t)c.np;
   db->n = c.n;
@@ -924,13 +975,12 @@ void lcv_batch_free(lcv_ctx* ctx, lcv_dbatch* b) {
   delete b;
 }
 
+// rows [base, base + n) of a batch: every per-row column it carries advanced by `base` elements, the pool as it is
 static BatchDev chunk_view(const BatchDev& B, size_t base, uint32_t n) {
   BatchDev c = B;
-  c.att_beacon += 112 * base; c.att_exec += 832 * base; c.att_branch += 128 * base;
-  c.fin_beacon += 112 * base; c.fin_exec += 832 * base; c.fin_branch += 128 * base;
-  c.nsc_index += base; c.nsc_branch += 160 * base; c.finality_branch += 192 * base;
-  c.bits += 64 * base; c.sig += 96 * base; c.sig_slot += base;
-  if (c.store_index) c.store_index += base;
+  for (const ColSpec& s : kBatchCols)
+    if (col_per_row(s))
+      if (const uint8_t* p = slot_get(&B, s.dev)) slot_set(&c, s.dev, p + s.width * base);
   c.n = n;
   return c;
 }
@@ -970,7 +1020,7 @@ static int ensure_fold_seg(lcv_ctx* ctx, int slot, size_t nseg) {
 static int fold_seg_stage(lcv_ctx* ctx, const Work& W, const StoreDev& S, const FoldSegDev& G, uint32_t nseg) {
   return stage(ctx, ST_FOLD, [&] { return be_launch_team(ctx, F_fold_seg{W, S, G}, nseg); });
 }
-// the results of a segmented fold, as they arrived (128 bytes per store present), to the caller's array indexed
+// the results of a segmented fold, as they arrived (FOLD_RESULT_BYTES per store present), to the caller's array indexed
 // by store row: only the present stores' entries are written
 static void fold_seg_scatter(lcv_fold_result* out, const uint8_t* res, const uint32_t* seg_store, size_t nseg) {
   for (size_t g = 0; g < nseg; ++g) memcpy(&out[seg_store[g]], res + FOLD_RESULT_BYTES * g, sizeof(FoldResult));
@@ -1947,61 +1997,16 @@ int lcv_debug_set_chunk(lcv_ctx* ctx, uint64_t rows) {
   return LCV_OK;
 }
 
-// ---- work-space layout check (test entry; host arithmetic only, nothing is read or written on the device).
-// Every per-item field of a Work, as the kernels address it (lcv_items.hpp soa_index / f12_index,
-// lcv_functors_sop.hpp lines_index): item i of field k covers `rows` elements of `esize` bytes, element r at
-// base + index(i, r).
-// kind 0 SoA (stride cap), 1 f, 2 lines, 3 committee-pool SoA (stride pool_cap, one item per distinct committee;
-// work_view does not advance these: they are not per update), 4 the rank records (item-major, lcv_fold.hpp
-// rank_index), 5 one per work space (the fold's result: a single item, not advanced by work_view either), 6 the
-// slot's deduplication scratch (lcv_set_dedup, ensure_dedup: item-major rows, one item per row of the work space;
-// a deduplicated chunk is never sliced, so work_view does not advance these)
-struct FieldRef { const char* name; const uint8_t* base; size_t esize, rows; int kind; size_t pool_cap = 0; };
-enum { WORK_FIELDS_MAX = 32 };
-static int work_fields(const Work& W, FieldRef* f, const DedupDev* D = nullptr) {
-  int n = 0;
-  f[n++] = {"msg", (const uint8_t*)W.msg, 4, 8, 0};
-  f[n++] = {"pre_reason", W.pre_reason, 1, 1, 0};
-  f[n++] = {"comm_id", (const uint8_t*)W.comm_id, 4, 1, 0};
-  f[n++] = {"nsc_eq", W.nsc_eq, 1, 1, 0};
-  f[n++] = {"qmap", (const uint8_t*)W.qmap, 4, 96, 0};
-  f[n++] = {"qh", (const uint8_t*)W.qh, 4, 48, 0};
-  f[n++] = {"qh_inf", W.qh_inf, 1, 1, 0};
-  f[n++] = {"qs", (const uint8_t*)W.qs, 4, 48, 0};
-  f[n++] = {"sig_status", W.sig_status, 1, 1, 0};
-  f[n++] = {"pk", (const uint8_t*)W.pk, 4, 24, 0};
-  f[n++] = {"agg_status", W.agg_status, 1, 1, 0};
-  f[n++] = {"f", (const uint8_t*)W.f, 4, F12_ITEM_WORDS, 1};
-  f[n++] = {"pair_ok", W.pair_ok, 1, 1, 0};
-  f[n++] = {"verdict", W.verdict, 1, 1, 0};
-  f[n++] = {"reason", W.reason, 1, 1, 0};
-  f[n++] = {"lines", (const uint8_t*)W.lines, 4, SOP_LINE_WORDS, 2};
-  f[n++] = {"nsc_root", (const uint8_t*)W.nsc_root, 4, 8, 3, W.pool_cap};
-  f[n++] = {"nsc_flags", W.nsc_flags, 1, 1, 3, W.pool_cap};
-  f[n++] = {"rank", W.rank, 1, RANK_BYTES, 4};
-  f[n++] = {"fold_out", W.fold_out, 1, FOLD_RESULT_BYTES, 5, 1};
-  if (D) {
-    f[n++] = {"dedup_att_beacon", D->att_beacon, 1, K_BEACON, 6};
-    f[n++] = {"dedup_sig_slot", (const uint8_t*)D->sig_slot, 8, 1, 6};
-    f[n++] = {"dedup_bits", D->bits, 1, 64, 6};
-    f[n++] = {"dedup_sig", D->sig, 1, 96, 6};
-    f[n++] = {"dedup_comm_id", (const uint8_t*)D->comm_id, 4, 1, 6};
-    f[n++] = {"dedup_rep", (const uint8_t*)D->rep, 4, 1, 6};
-    f[n++] = {"dedup_urow", (const uint8_t*)D->urow, 4, 1, 6};
-  }
-  return n;
-}
-// byte address of element r of item i (cap: the stride of the SoA fields)
-static const uint8_t* field_addr(const FieldRef& f, size_t cap, size_t i, size_t r) {
-  size_t idx;
-  if (f.kind == 0) idx = soa_index(cap, i, r);
-  else if (f.kind == 1) idx = f12_index(i, (uint32_t)(r / 12)) + r % 12;
-  else if (f.kind == 3) idx = soa_index(f.pool_cap, i, r);
-  else if (f.kind == 4) idx = rank_index(i) + r;
-  else if (f.kind == 5) idx = r;
-  else if (f.kind == 6) idx = i * f.rows + r;
-  else idx = lines_index(i) + r;
-  return f.base + idx * f.esize;
+// ---- work-space layout check (test entry; host arithmetic only, nothing is read or written on the device), over
+// kWorkFields and kDedupFields: element r of item i of a field at base + field_index(i, r), the kernels' own functions.
+// (1) work_view is derived from the same rows and functions, so what this proves is that every kind's index function
+// is additive in the item — index(b + j, r) - index(j, r) depends on neither j nor r — the precondition of slicing by
+// advancing a pointer.  It does not cross-check two hand-written lists, and it cannot see a field given the wrong
+// kind in the table: the slices then overwrite each other's items on the device, where they run side by side (the
+// sliced cases of tests/stage_mark_cases.py), but not on the host simulation, which runs them one after another.
+// (2) proves the allocation: no two arrays of any slots overlap
+static const uint8_t* field_addr(const void* obj, const Field& f, size_t cap, size_t pool_cap, size_t i, size_t r) {
+  return slot_get(obj, f.slot) + f.esize * field_index(f, cap, pool_cap, i, r);
 }
 
 extern "C" int lcv_debug_work_check(lcv_ctx* ctx, uint64_t cap, uint64_t slice, int nslots) {
@@ -2012,47 +2017,43 @@ extern "C" int lcv_debug_work_check(lcv_ctx* ctx, uint64_t cap, uint64_t slice, 
     LCV_TRY(ensure_dedup(ctx, cap, s));    // and the slot's deduplication scratch (lcv_set_dedup), checked in (2)
   }
   ctx->W = ctx->Wslot[0];
-  // (1) slices: item j of work_view(W, b) is item b + j of W, element for element, in every field
+  // (1) slices: item j of work_view(W, b) is item b + j of W, element for element, in every per-item field
   for (int s = 0; s < nslots; ++s) {
     const Work& W = ctx->Wslot[s];
-    const size_t C = W.cap;
-    FieldRef full[WORK_FIELDS_MAX], part[WORK_FIELDS_MAX];
-    const int nf = work_fields(W, full);
+    const size_t C = W.cap, Pc = W.pool_cap;
     for (size_t b = 0; b < C; b += slice) {
-      work_fields(work_view(W, b), part);
+      const Work V = work_view(W, b);
       const size_t len = C - b < slice ? C - b : slice;
-      for (int k = 0; k < nf; ++k)
-        if (full[k].kind != 3 && full[k].kind != 5)
-        for (size_t j = 0; j < len; ++j)
-          for (size_t r = 0; r < full[k].rows; ++r)
-            if (field_addr(part[k], C, j, r) != field_addr(full[k], C, b + j, r))
-              return fail(ctx, LCV_EINVAL, std::string("lcv_debug_work_check: slot ") + std::to_string(s) + " field " +
-                                               full[k].name + ": item " + std::to_string(j) + " of the slice at " +
-                                               std::to_string(b) + " is not item " + std::to_string(b + j));
+      for (const Field& f : kWorkFields)
+        if (field_per_item(f))
+          for (size_t j = 0; j < len; ++j)
+            for (size_t r = 0; r < f.rows; ++r)
+              if (field_addr(&V, f, C, Pc, j, r) != field_addr(&W, f, C, Pc, b + j, r))
+                return fail(ctx, LCV_EINVAL, std::string("lcv_debug_work_check: slot ") + std::to_string(s) + " field " +
+                                                 f.name + ": item " + std::to_string(j) + " of the slice at " +
+                                                 std::to_string(b) + " is not item " + std::to_string(b + j));
     }
   }
   // (2) every field of every slot: its byte range [first element, last element] is disjoint from every
   // other field's (of this slot and of the other slots), and every item's elements lie in it (the
   // committee-pool fields over their pool_cap items)
-  struct Range { const uint8_t *lo, *hi; int slot; const char* name; };
+  struct Range { const uint8_t *lo, *hi; int slot; std::string name; };
   std::vector<Range> rg;
+  auto ranges = [&](int s, const void* obj, const Field& f, const char* prefix, size_t C, size_t Pc) {
+    const uint8_t* lo = field_addr(obj, f, C, Pc, 0, 0);
+    const uint8_t* hi = lo;
+    for (size_t i = 0; i < field_items(f, C, Pc); ++i)
+      for (size_t r = 0; r < f.rows; ++r) {
+        const uint8_t* a = field_addr(obj, f, C, Pc, i, r);
+        if (a < lo) lo = a;
+        if (a + f.esize > hi) hi = a + f.esize;
+      }
+    rg.push_back({lo, hi, s, std::string(prefix) + f.name});
+  };
   for (int s = 0; s < nslots; ++s) {
     const Work& W = ctx->Wslot[s];
-    const size_t C = W.cap;
-    FieldRef fr[WORK_FIELDS_MAX];
-    const int nf = work_fields(W, fr, &ctx->Dslot[s]);
-    for (int k = 0; k < nf; ++k) {
-      const uint8_t* lo = field_addr(fr[k], C, 0, 0);
-      const uint8_t* hi = lo;
-      const size_t items = (fr[k].kind == 3 || fr[k].kind == 5) ? fr[k].pool_cap : C;
-      for (size_t i = 0; i < items; ++i)
-        for (size_t r = 0; r < fr[k].rows; ++r) {
-          const uint8_t* a = field_addr(fr[k], C, i, r);
-          if (a < lo) lo = a;
-          if (a + fr[k].esize > hi) hi = a + fr[k].esize;
-        }
-      rg.push_back({lo, hi, s, fr[k].name});
-    }
+    for (const Field& f : kWorkFields) ranges(s, &W, f, "", W.cap, W.pool_cap);
+    for (const Field& f : kDedupFields) ranges(s, &ctx->Dslot[s], f, "dedup_", W.cap, 0);
   }
   for (size_t a = 0; a < rg.size(); ++a)
     for (size_t b = a + 1; b < rg.size(); ++b)
@@ -2171,17 +2172,17 @@ static int fav_impl(lcv_ctx* ctx, const uint8_t* committees, uint64_t ncomm, con
   }
   CommitteeDev C = committee_view(ctx->adhoc, nullptr);
   void* tmp = nullptr;
-  const size_t tb = rows * (64 + 96 + 32);
+  const size_t tb = rows * (K_BITS + K_SIG + 32);
   LCV_TRY(be_alloc(ctx, &tmp, tb));
   uint8_t* t = (uint8_t*)tmp;
-  int rc = be_h2d(ctx, t, bits, 64 * rows);
-  if (rc == LCV_OK && sig) rc = be_h2d(ctx, t + 64 * rows, sig, 96 * n);
+  int rc = be_h2d(ctx, t, bits, K_BITS * rows);
+  if (rc == LCV_OK && sig) rc = be_h2d(ctx, t + K_BITS * rows, sig, K_SIG * n);
   void* mtmp = nullptr;  // a message that is not 32 bytes (n == 1): its bytes, hashed into b0 on device
   if (rc == LCV_OK && msg && msg_len != 32) {
     rc = be_alloc(ctx, &mtmp, msg_len ? msg_len : 1);
     if (rc == LCV_OK) rc = be_h2d(ctx, mtmp, msg, msg_len);
   } else if (rc == LCV_OK && msg) {
-    rc = be_h2d(ctx, t + 160 * rows, msg, 32 * n);
+    rc = be_h2d(ctx, t + (K_BITS + K_SIG) * rows, msg, 32 * n);
   }
   if (rc == LCV_OK) rc = be_h2d(ctx, ctx->W.comm_id, cid, 4 * rows);
   if (rc == LCV_OK) rc = be_memset(ctx, ctx->W.pre_reason, 0, rows);
@@ -2195,7 +2196,7 @@ static int fav_impl(lcv_ctx* ctx, const uint8_t* committees, uint64_t ncomm, con
       rc = be_launch(ctx, F_msg_import_b0{(const uint8_t*)mtmp, msg_len, ctx->W}, 1);
       ctx->W.msg_b0 = 1;
     } else {
-      rc = be_launch(ctx, F_msg_import{t + 160 * rows, ctx->W}, (uint32_t)n);
+      rc = be_launch(ctx, F_msg_import{t + (K_BITS + K_SIG) * rows, ctx->W}, (uint32_t)n);
     }
     if (rc == LCV_OK) rc = run_bls(ctx, B, C, (uint32_t)n, (uint32_t)agg_items);
     ctx->W.msg_b0 = 0;
@@ -2307,7 +2308,7 @@ int lcv_bootstrap_check_batch(lcv_ctx* ctx, const uint8_t* beacon112, const uint
   return simple_call(ctx, n,
                      {{beacon112, (size_t)K_BEACON * n}, {exec832, (size_t)K_EXEC * n},
                       {exec_branch128, (size_t)K_EXEC_BRANCH * n}, {committees, (size_t)K_SC * n},
-                      {committee_branch160, 160 * n}, {trusted_root32, 32 * n}},
+                      {committee_branch160, (size_t)K_NSC_BRANCH * n}, {trusted_root32, 32 * n}},
                      {{reason_out, n}}, [&](std::vector<uint8_t*>& d) {
                        return be_launch(ctx, F_bootstrap{d[0], d[1], d[2], d[3], d[4], d[5], d[6], ctx->cfg}, (uint32_t)n);
                      });
@@ -2346,7 +2347,7 @@ int lcv_debug_hash_to_g2(lcv_ctx* ctx, const uint8_t* msg32, uint64_t n, uint8_t
   if (!ctx || !msg32 || !out192 || !inf) return fail(ctx, LCV_EINVAL, "debug_hash_to_g2: null argument");
   if (n > kChunk) return fail(ctx, LCV_EINVAL, "debug_hash_to_g2: n > 65536");
   LCV_TRY(ensure_work(ctx, n, 1));
-  return simple_call(ctx, n, {{msg32, 32 * n}}, {{out192, 192 * n}, {inf, n}}, [&](std::vector<uint8_t*>& d) {
+  return simple_call(ctx, n, {{msg32, 32 * n}}, {{out192, 4 * 48 * n}, {inf, n}}, [&](std::vector<uint8_t*>& d) {
     Work W = ctx->W;
     LCV_TRY(be_launch(ctx, F_msg_import{d[0], W}, (uint32_t)n));
     LCV_TRY(hash_to_g2_stage(ctx, ctx->W, (uint32_t)n));
@@ -2359,7 +2360,7 @@ int lcv_debug_g2_decompress(lcv_ctx* ctx, const uint8_t* sig96, uint64_t n, uint
   if (!ctx || !sig96 || !out192 || !status) return fail(ctx, LCV_EINVAL, "debug_g2_decompress: null argument");
   if (n > kChunk) return fail(ctx, LCV_EINVAL, "debug_g2_decompress: n > 65536");
   LCV_TRY(ensure_work(ctx, n, 1));
-  return simple_call(ctx, n, {{sig96, 96 * n}}, {{out192, 192 * n}, {status, n}}, [&](std::vector<uint8_t*>& d) {
+  return simple_call(ctx, n, {{sig96, K_SIG * n}}, {{out192, 4 * 48 * n}, {status, n}}, [&](std::vector<uint8_t*>& d) {
     Work W = ctx->W;
     BatchDev B;
     memset(&B, 0, sizeof(B));
@@ -2376,7 +2377,7 @@ int lcv_debug_pairing(lcv_ctx* ctx, const uint8_t* p96, const uint8_t* q192, uin
   if (n > kChunk) return fail(ctx, LCV_EINVAL, "debug_pairing: n > 65536");
   LCV_TRY(ensure_work(ctx, n, 1));
   be_reset_timings(ctx);
-  const int rc = simple_call(ctx, n, {{p96, 96 * n}, {q192, 192 * n}}, {{out576, 576 * n}}, [&](std::vector<uint8_t*>& d) {
+  const int rc = simple_call(ctx, n, {{p96, 96 * n}, {q192, 4 * 48 * n}}, {{out576, 576 * n}}, [&](std::vector<uint8_t*>& d) {
     Work W = ctx->W;
     LCV_TRY(be_launch(ctx, F_import_pq{d[0], d[1], W}, (uint32_t)n));
     LCV_TRY(pairing_check(ctx, ctx->W, (uint32_t)n));
@@ -2434,7 +2435,7 @@ static int prod_views(lcv_ctx* ctx, const lcv_state_views* s, uint64_t ns, const
   const void* src[NV] = {s->slot, s->latest_block_header, s->fin_epoch, s->fin_root, s->field_roots, s->cur_index,
                          s->nxt_index, b->slot, b->proposer_index, b->parent_root, b->state_root, b->bits,
                          b->signature, b->execution, b->exec_kind, b->body_roots};
-  const size_t bytes[NV] = {8 * ns, 112 * ns, 8 * ns, 32 * ns, 32 * PROD_STATE_FIELDS * ns, 4 * ns, 4 * ns, 8 * nb, 8 * nb,
+  const size_t bytes[NV] = {8 * ns, (size_t)K_BEACON * ns, 8 * ns, 32 * ns, 32 * PROD_STATE_FIELDS * ns, 4 * ns, 4 * ns, 8 * nb, 8 * nb,
                             32 * nb, 32 * nb, 64 * nb, 96 * nb, (size_t)K_EXEC * nb, nb, 32 * PROD_BODY_FIELDS * nb};
   auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
   size_t off[NV], total = 0;
@@ -2483,30 +2484,28 @@ static int prod_views(lcv_ctx* ctx, const lcv_state_views* s, uint64_t ns, const
   return stage(ctx, ST_PRODUCE_VIEWS, [&] { return be_launch(ctx, F_prod_state{R.S, R.X}, (uint32_t)ns); });
 }
 
+// the producer's writable view of a batch's row columns (kBatchCols: the rows with a ProdOut member)
 static ProdOut prod_out(const BatchDev& B) {
-  return ProdOut{(uint8_t*)B.att_beacon, (uint8_t*)B.att_exec, (uint8_t*)B.att_branch, (uint8_t*)B.fin_beacon,
-                 (uint8_t*)B.fin_exec, (uint8_t*)B.fin_branch, (uint32_t*)B.nsc_index, (uint8_t*)B.nsc_branch,
-                 (uint8_t*)B.finality_branch, (uint8_t*)B.bits, (uint8_t*)B.sig, (uint64_t*)B.sig_slot};
+  ProdOut O = {};
+  for (const ColSpec& s : kBatchCols)
+    if (s.prod >= 0) slot_set(&O, s.prod, slot_get(&B, s.dev));
+  return O;
 }
 
-// a resident batch's 12 row columns (and its pool, when asked) to the caller's arrays
+// a resident batch's row columns (and its pool, when asked, after them) to the caller's arrays
 static int prod_copy_out(lcv_ctx* ctx, const BatchDev& B, size_t n, const lcv_update_batch* out, bool with_pool,
                          size_t npool) {
-  void* dst[12] = {(void*)out->attested.beacon, (void*)out->attested.execution, (void*)out->attested.exec_branch,
-                   (void*)out->finalized.beacon, (void*)out->finalized.execution, (void*)out->finalized.exec_branch,
-                   (void*)out->nsc_index, (void*)out->nsc_branch, (void*)out->finality_branch, (void*)out->sync_bits,
-                   (void*)out->sync_signature, (void*)out->signature_slot};
-  const void* src[12] = {B.att_beacon, B.att_exec, B.att_branch, B.fin_beacon, B.fin_exec, B.fin_branch, B.nsc_index,
-                         B.nsc_branch, B.finality_branch, B.bits, B.sig, B.sig_slot};
-  const size_t width[12] = {112, 832, 128, 112, 832, 128, 4, 160, 192, 64, 96, 8};
-  for (int k = 0; k < 12; ++k) LCV_TRY(be_d2h(ctx, dst[k], src[k], width[k] * n));
-  if (with_pool) LCV_TRY(be_d2h(ctx, (void*)out->nsc_pool, B.nsc_pool, (size_t)K_SC * npool));
+  for (const ColSpec& s : kBatchCols)
+    if (col_per_row(s) && s.host >= 0) LCV_TRY(be_d2h(ctx, slot_get(out, s.host), slot_get(&B, s.dev), s.width * n));
+  const ColSpec& p = kBatchCols[COL_NSC_POOL];
+  if (with_pool) LCV_TRY(be_d2h(ctx, slot_get(out, p.host), B.nsc_pool, p.width * npool));
   return LCV_OK;
 }
 static bool batch_out_null(const lcv_update_batch* o) {
-  return !o || !o->attested.beacon || !o->attested.execution || !o->attested.exec_branch || !o->finalized.beacon ||
-         !o->finalized.execution || !o->finalized.exec_branch || !o->nsc_pool || !o->nsc_index || !o->nsc_branch ||
-         !o->finality_branch || !o->sync_bits || !o->sync_signature || !o->signature_slot;
+  if (!o) return true;
+  for (const ColSpec& s : kBatchCols)
+    if (s.host >= 0 && !slot_get(o, s.host)) return true;
+  return false;
 }
 
 extern "C" {

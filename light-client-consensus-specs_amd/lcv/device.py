@@ -2,12 +2,13 @@
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, fields
+from dataclasses import dataclass
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
 from . import config as _config
+from . import layout as L
 from ._native import (Lib, LcvError, UpdateBatch, HeaderCols, StoreTable, FoldStateC, FoldResultC, StateViews,
                       BlockViews, UpdateCases, STORE_NEXT_UNKNOWN, as_u8, load, ptr)
 
@@ -78,66 +79,50 @@ class PackedUpdates:
     sync_signature: np.ndarray   # (n, 96) u8
     signature_slot: np.ndarray   # (n,) u64
 
+    # column -> (dtype, trailing shape, counted by the pool instead of n), in field order = lcv_update_batch's pointers
+    _SPEC = dict(att_beacon=(np.uint8, (L.BEACON_BYTES,), False), att_exec=(np.uint8, (L.EXEC_BYTES,), False),
+                 att_branch=(np.uint8, (L.EXEC_BRANCH_BYTES,), False), fin_beacon=(np.uint8, (L.BEACON_BYTES,), False),
+                 fin_exec=(np.uint8, (L.EXEC_BYTES,), False), fin_branch=(np.uint8, (L.EXEC_BRANCH_BYTES,), False),
+                 nsc_pool=(np.uint8, (L.SYNC_COMMITTEE_BYTES,), True), nsc_index=(np.uint32, (), False),
+                 nsc_branch=(np.uint8, (L.NSC_BRANCH_BYTES,), False),
+                 finality_branch=(np.uint8, (L.FINALITY_BRANCH_BYTES,), False),
+                 sync_bits=(np.uint8, (L.BITS_BYTES,), False), sync_signature=(np.uint8, (L.SIGNATURE_BYTES,), False),
+                 signature_slot=(np.uint64, (), False))
+    _CTYPE = {np.uint8: C.c_uint8, np.uint32: C.c_uint32, np.uint64: C.c_uint64}
+
     @property
     def n(self) -> int:
         return int(self.att_beacon.shape[0])
 
     def check(self) -> None:
         n = self.n
-        shapes = dict(att_beacon=112, att_exec=832, att_branch=128, fin_beacon=112, fin_exec=832, fin_branch=128,
-                      nsc_branch=160, finality_branch=192, sync_bits=64, sync_signature=96)
-        for name, w in shapes.items():
+        for name, (dt, tail, pool) in self._SPEC.items():
             a = getattr(self, name)
-            if a.dtype != np.uint8 or a.shape != (n, w) or not a.flags.c_contiguous:
-                raise ValueError(f"{name}: need C-contiguous uint8 ({n}, {w}), got {a.dtype} {a.shape}")
-        if self.nsc_pool.dtype != np.uint8 or self.nsc_pool.ndim != 2 or self.nsc_pool.shape[1] != SYNC_COMMITTEE_BYTES:
-            raise ValueError("nsc_pool: need uint8 (npool, 24624)")
-        if self.nsc_index.dtype != np.uint32 or self.nsc_index.shape != (n,):
-            raise ValueError("nsc_index: need uint32 (n,)")
-        if self.signature_slot.dtype != np.uint64 or self.signature_slot.shape != (n,):
-            raise ValueError("signature_slot: need uint64 (n,)")
+            rows = a.shape[0] if pool and a.ndim else n
+            if a.dtype != dt or a.shape != (rows,) + tail or not a.flags.c_contiguous:
+                want = ("npool" if pool else n,) + tail
+                raise ValueError(f"{name}: need C-contiguous {np.dtype(dt).name} ({', '.join(map(str, want))}"
+                                 f"{',' if len(want) == 1 else ''}), got {a.dtype} {a.shape}")
         if n and int(self.nsc_index.max()) >= self.nsc_pool.shape[0]:
             raise ValueError("nsc_index out of range")
 
     def slice(self, lo: int, hi: int) -> "PackedUpdates":
-        kw = {}
-        for f in fields(self):
-            a = getattr(self, f.name)
-            kw[f.name] = a if f.name == "nsc_pool" else np.ascontiguousarray(a[lo:hi])
-        return PackedUpdates(**kw)
+        return PackedUpdates(**{name: getattr(self, name) if pool else np.ascontiguousarray(getattr(self, name)[lo:hi])
+                                for name, (_, _, pool) in self._SPEC.items()})
 
     def to_c(self) -> Tuple[UpdateBatch, list]:
+        """The lcv_update_batch naming this batch's own arrays (check() has required them C-contiguous, so the
+        entries that write a batch write through the same pointers), and the arrays to keep alive."""
         self.check()
-        keep = []
-
-        def P(a, t=C.c_uint8):
-            a = np.ascontiguousarray(a)
-            keep.append(a)
-            return ptr(a, t)
-
-        b = UpdateBatch()
-        b.attested = HeaderCols(P(self.att_beacon), P(self.att_exec), P(self.att_branch))
-        b.finalized = HeaderCols(P(self.fin_beacon), P(self.fin_exec), P(self.fin_branch))
-        b.nsc_pool = P(self.nsc_pool)
-        b.nsc_index = P(self.nsc_index, C.c_uint32)
-        b.nsc_branch = P(self.nsc_branch)
-        b.finality_branch = P(self.finality_branch)
-        b.sync_bits = P(self.sync_bits)
-        b.sync_signature = P(self.sync_signature)
-        b.signature_slot = P(self.signature_slot, C.c_uint64)
-        b.n = self.n
-        b.npool = int(self.nsc_pool.shape[0])
-        return b, keep
-
+        keep = [getattr(self, name) for name in self._SPEC]
+        p = [ptr(a, self._CTYPE[dt]) for a, (dt, _, _) in zip(keep, self._SPEC.values())]
+        return UpdateBatch(HeaderCols(*p[0:3]), HeaderCols(*p[3:6]), *p[6:], self.n, int(self.nsc_pool.shape[0])), keep
 
     @staticmethod
     def empty(n: int, npool: int) -> "PackedUpdates":
         """An all-zero batch of n rows and npool pool rows (the arrays the download entries write into)."""
-        z = lambda *shape: np.zeros(shape, np.uint8)  # noqa: E731
-        return PackedUpdates(att_beacon=z(n, 112), att_exec=z(n, 832), att_branch=z(n, 128), fin_beacon=z(n, 112),
-                             fin_exec=z(n, 832), fin_branch=z(n, 128), nsc_pool=z(npool, SYNC_COMMITTEE_BYTES),
-                             nsc_index=np.zeros(n, np.uint32), nsc_branch=z(n, 160), finality_branch=z(n, 192),
-                             sync_bits=z(n, 64), sync_signature=z(n, 96), signature_slot=np.zeros(n, np.uint64))
+        return PackedUpdates(**{name: np.zeros((npool if pool else n,) + tail, dt)
+                                for name, (dt, tail, pool) in PackedUpdates._SPEC.items()})
 
 
 UPDATE_KINDS = {"update": 0, "finality": 1, "optimistic": 2}
@@ -209,11 +194,6 @@ def _cases_to_c(cases):
     cols = [np.ascontiguousarray(a[:, k], np.uint32) for k in range(4)] + [np.ascontiguousarray(a[:, 4], np.int32)]
     uc = UpdateCases(*[ptr(c, C.c_uint32) for c in cols[:4]], ptr(cols[4], C.c_int32))
     return uc, cols, int(a.shape[0])
-
-
-def _writable_c(p: "PackedUpdates"):
-    b, keep = p.to_c()  # (C-contiguous arrays are passed as they are: the entries write through the pointers)
-    return b, keep
 
 
 class ResidentBatch:
@@ -439,7 +419,7 @@ class Verifier:
         uc, cols, n = _cases_to_c(cases)
         r = reason if reason is not None else np.zeros(n, np.uint8)
         out = PackedUpdates.empty(n, views.ncomm + 1)
-        b, keep_out = _writable_c(out)
+        b, keep_out = out.to_c()
         self._check(self.lib.lcv_create_updates(self.ctx, C.byref(sv), views.ns, C.byref(bv), views.nb, com,
                                                 views.ncomm, C.byref(uc), n, self._kind(kind), C.byref(b), ptr(r)),
                     "lcv_create_updates")
@@ -455,7 +435,7 @@ class Verifier:
         out = PackedUpdates.empty(rb.n if ix is None else ix.shape[0], rb.npool)
         if not rb.handle:
             return out
-        b, keep = _writable_c(out)
+        b, keep = out.to_c()
         self._check(self.lib.lcv_batch_download(self.ctx, rb.handle, None if ix is None else ptr(ix, C.c_uint32),
                                                 0 if ix is None else ix.shape[0], C.byref(b)), "lcv_batch_download")
         return out
