@@ -374,6 +374,47 @@ int lcv_debug_engine_log(lcv_ctx* ctx, uint64_t* out8, int reset);
 int lcv_set_dedup(lcv_ctx* ctx, int on);
 int lcv_last_dedup(lcv_ctx* ctx, int slot, uint64_t* rows, uint64_t* items);
 int lcv_debug_dedup_hash_bits(lcv_ctx* ctx, int bits);
+
+/* ---- Batch verification: one final exponentiation per group of rows (randomised linear combination, as blst's
+ * verify_multiple_aggregate_signatures).  For a group of G consecutive items of a chunk (the rows; under
+ * lcv_set_dedup the distinct items; the last group may be short) and secret 64-bit coefficients r_i,
+ *     prod_i  e(r_i PK_i, H(m_i)) e(r_i (-G1), S_i)  ==  1
+ * holds when every item of the group is valid, and fails when one is not except with probability about 2^-64.  So a
+ * group pays ONE final exponentiation; the items of a failing group then pay one each, over their own scaled Miller
+ * value (e(PK_i, H_i) e(-G1, S_i))^r_i, which is 1 exactly when the unscaled one is (0 < r_i < the group order, all
+ * points in the prime-order subgroups): the fallback is exact.  Worst case, every group failing: (1 + 1/G) final
+ * exponentiations per item, plus the scaling.
+ * lcv_set_rlc(ctx, group, seed32): group 0 turns the mode off (the default: every call then launches exactly what it
+ * launches without this entry); group in {2, 4, 8, 16, 32, 64} turns it on.  Any other value, or a missing or all-zero
+ * seed with group != 0, is LCV_EINVAL; so is the mode together with a multi-stream pipeline (lcv_set_pipeline
+ * streams > 1), from whichever call comes second (the sliced chains are not taught the mode).
+ * Coefficients: r_i = the first 8 bytes, read little-endian, of SHA-256(seed32 || counter || i), 0 replaced by 1;
+ * counter is a u64 (little-endian) per context that every chunk running the mode takes and increments, i the item's
+ * index in its chunk as a u32 (little-endian).  They are derived on the device.
+ * Security conditions.  The seed must be unpredictable to whoever supplies updates (draw it from the system's
+ * random source; one who knows the coefficients can build invalid rows whose group product is 1).  Coefficients never
+ * repeat across batches of a context (the counter); use a fresh seed per context.  The mode accepts a group
+ * wrongly with probability at most about 2^-64 per group; every other accept / reject, and every reason byte, is that
+ * of the mode off.  The product relies on: participant keys KeyValidated (lcv_set_store*); the signature's G2
+ * membership, checked by its line walk before the product reads the flag; H(m) cofactor-cleared.  An item failing one
+ * of these — no aggregate key, an undecodable signature or one outside G2 — or, where the items are the rows, a
+ * pre-check is excluded from its group, never multiplied in, and never retried.
+ * Scope: chunks on the batch engine; a chunk the fan engine takes (lcv_set_latency_mode) runs as with the mode off and
+ * counts no groups, as does every chunk in the CPU-baseline build.  Every validate entry is covered (staged, resident,
+ * asynchronous, store tables, the folds, sharded); lcv_fast_aggregate_verify* is not.  Scratch: one allocation per
+ * work-space slot, made by the slot's first call with the mode on (1.35 KB per row of the slot's capacity).
+ * lcv_last_rlc: the groups and the rows retried after a failing group, totals over the chunks of the last batch
+ * enqueued on `slot` (synchronous calls: slot 0); valid once that batch has been waited for; it does a small
+ * blocking device-to-host read of its own.  groups == 0: the mode did not act.
+ * Test hooks: lcv_debug_rlc_coeffs writes the n coefficients the device derives for batch counter `counter` under the
+ * seed of the last lcv_set_rlc; lcv_debug_rlc_scale writes r_i P_i (affine x || y, 48 big-endian bytes each, as p96)
+ * through the scaling kernel's ladder and shared inversion.
+ * Out of scope: one signature Miller loop per group (aggregating the signatures in G2); bisecting a failing group;
+ * groups across chunks or batches; the sliced pipeline. */
+int lcv_set_rlc(lcv_ctx* ctx, uint32_t group, const uint8_t seed32[32]);
+int lcv_last_rlc(lcv_ctx* ctx, int slot, uint64_t* groups, uint64_t* retried_rows);
+int lcv_debug_rlc_coeffs(lcv_ctx* ctx, uint64_t counter, uint64_t n, uint64_t* out_u64);
+int lcv_debug_rlc_scale(lcv_ctx* ctx, const uint8_t* p96, const uint64_t* r_u64, uint64_t n, uint8_t* out96);
 /* kernel time of the last validate call: total and per stage (ms); names via lcv_stage_name
  * (stage times are recorded by the serial shape only: zero under a multi-stream pipeline) */
 int lcv_last_timings(lcv_ctx* ctx, float* ms_out, int max_stages, int* nstages);
@@ -538,7 +579,7 @@ int lcv_sign_batch(lcv_ctx* ctx, const uint8_t* sk32, const uint8_t* msg32, uint
 
 /* ---- parity-test entry points (intermediate values, canonical big-endian bytes) */
 /* field ops on (a, b) < p: out per item = a*b, a+b, a-b, a^-1, sqrt_fp2(a + b u) (2 x 48); ok = sqrt exists */
-/* test hook: rows per validate chunk (multiple of 64, <= 65536; default 65536) */
+/* test hook: rows per validate chunk (1 .. 65536; default 65536) */
 int lcv_debug_set_chunk(lcv_ctx* ctx, uint64_t rows);
 /* test hook (host arithmetic only): allocates work-space slots 0 .. nslots-1 for `cap` rows and checks
  * (1) for slices of `slice` rows, that item j of each slice's work view is item base + j of the slot's

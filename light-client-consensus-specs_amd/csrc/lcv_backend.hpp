@@ -27,6 +27,9 @@ template <class F> static int be_launch(lcv_ctx* ctx, const F& f, uint32_t n);
 template <class F> static int be_launch_team(lcv_ctx* ctx, const F& f, uint32_t n);
 template <class F> static int be_launch_sop(lcv_ctx* ctx, const F& f, uint32_t n, uint32_t g);
 template <class F> static int be_launch_sop_fan(lcv_ctx* ctx, const F& f, uint32_t n);
+// a SOP program on the batch engine over *n_dev <= n_max items: the count is device memory the stream's earlier
+// kernels wrote, which the host does not wait for
+template <class F> static int be_launch_sop_counted(lcv_ctx* ctx, const F& f, const uint32_t* n_dev, uint32_t n_max, uint32_t g);
 // streams: work-space slot s owns a main stream (0) and a side stream (1), plus the forked streams of a sliced
 // pipeline.  be_set_slot makes a slot's main stream current; be_use_stream picks stream k of the active slot
 static void be_set_slot(lcv_ctx* ctx, int slot);

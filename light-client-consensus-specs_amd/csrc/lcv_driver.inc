@@ -17,6 +17,7 @@
 #include "lcv_dedup.hpp"
 #include "lcv_dedup_plan.hpp"
 #include "lcv_sop.hpp"
+#include "lcv_rlc.hpp"
 #include "lcv_build_id.h"  // LCV_BUILD_ID (Makefile: tools/build_id.py over the sources)
 
 using namespace lcv;
@@ -24,12 +25,13 @@ using namespace lcv;
 // One mark per kernel launch (marks never nest, so the host simulation's op counter attributes every
 // operation to exactly one stage, and a HIP event pair brackets exactly one kernel on its stream).
 enum { ST_NSC = 0, ST_PRE, ST_H2C_MAP, ST_H2C, ST_SIG, ST_AGG, ST_MILLER, ST_FEXP, ST_VERDICT, ST_SETUP,
-       ST_LINES, ST_LINES_SIG, ST_SIGROOT, ST_RANK, ST_FOLD, ST_PRODUCE_VIEWS, ST_PRODUCE_ROWS, ST_DEDUP, ST_COUNT };
+       ST_LINES, ST_LINES_SIG, ST_SIGROOT, ST_RANK, ST_FOLD, ST_PRODUCE_VIEWS, ST_PRODUCE_ROWS, ST_DEDUP,
+       ST_RLC_SCALE, ST_RLC_PROD, ST_RLC_SPREAD, ST_RLC_RETRY, ST_COUNT };
 static const char* kStageNames[ST_COUNT] = {"nsc_htr", "pre_checks", "h2c_sswu", "hash_to_g2", "sig_decode",
                                             "g1_aggregate", "miller_loop", "final_exp", "verdict",
                                             "setup", "miller_lines", "miller_lines_sig", "signing_root",
                                             "store_rank", "store_fold", "produce_views", "produce_rows",
-                                            "dedup_gather"};
+                                            "dedup_gather", "rlc_scale", "rlc_product", "rlc_spread", "rlc_retry"};
 
 struct CommitteeBufs {
   uint8_t* raw = nullptr;
@@ -122,7 +124,7 @@ struct lcv_ctx {
   FoldSegs segs;  // the grouping of the call in progress (staged before the call returns)
   float stage_ms[ST_COUNT];
   void* sop_mem = nullptr;   // device copies of the SOP pairing programs (tools/gen_sop.py)
-  SopView sop_lines, sop_acc, sop_fexp, sop_h2c, sop_miller;
+  SopView sop_lines, sop_acc, sop_fexp, sop_h2c, sop_miller, sop_f12mul;
   // chunk pipeline of validate (lcv_set_pipeline; default 1 x 1 = serial stages): a batch is cut into `pipe_chunks` slices whose
   // stage chains run on `pipe_streams` streams, so the stages of different slices overlap
   int pipe_streams = 1, pipe_chunks = 1;
@@ -178,6 +180,20 @@ struct lcv_ctx {
   std::vector<uint32_t> dd_cls, dd_comm, dd_rep, dd_urow;
   std::vector<uint64_t> tab_fin;
   std::vector<uint32_t> tab_cur, tab_next;
+  // randomised batch verification (lcv_set_rlc, off by default; include/lcv.h "Batch verification"): the group size
+  // (0: off) and the seed; the batch counter the next chunk's coefficients are derived from (never reused: +1 per
+  // chunk that runs the mode); per work-space slot the scratch (ensure_rlc: an allocation of its own, made by the
+  // slot's first call with the mode on, laid out for the slot's work-space capacity) and, for lcv_last_rlc, the groups
+  // of the slot's last batch and the slots whose scratch counted that batch's retried rows (bit s: slot s)
+  uint32_t rlc_group = 0;
+  bool rlc_seeded = false;
+  uint32_t rlc_seed[8] = {};
+  uint64_t rlc_counter = 0;
+  void* rlc_mem[LCV_SLOTS] = {};
+  size_t rlc_cap[LCV_SLOTS] = {};
+  RlcDev Rslot[LCV_SLOTS] = {};
+  uint64_t rl_groups[LCV_SLOTS] = {};
+  uint32_t rl_used[LCV_SLOTS] = {};
 };
 
 static uint32_t host_be32(const uint8_t* p) {
@@ -305,6 +321,14 @@ static constexpr Field kDedupFields[] = {
     LCV_FIELD(DedupDev, comm_id, 1, FK_ITEM),           LCV_FIELD(DedupDev, rep, 1, FK_ITEM),
     LCV_FIELD(DedupDev, urow, 1, FK_ITEM),
 };
+// the batch-verification scratch (lcv_rlc.hpp RlcDev), laid out for the slot's work-space capacity
+static constexpr Field kRlcFields[] = {
+    LCV_FIELD(RlcDev, pk_s, 24, FK_SOA),              LCV_FIELD(RlcDev, g1_s, 24, FK_SOA),
+    LCV_FIELD(RlcDev, prod_a, F12_ITEM_WORDS, FK_F),  LCV_FIELD(RlcDev, prod_b, F12_ITEM_WORDS, FK_F),
+    LCV_FIELD(RlcDev, g_ok, 1, FK_SOA),               LCV_FIELD(RlcDev, retry, 1, FK_SOA),
+    LCV_FIELD(RlcDev, cnt, 4, FK_SPACE),
+};
+static_assert(sizeof(RlcDev) == sizeof(kRlcFields) / sizeof(Field) * sizeof(void*), "an RlcDev array without a row in kRlcFields");
 // every pointer member has its row (a Work also holds cap and pool_cap in one pointer-sized word, msg_b0 in another)
 static_assert(sizeof(Work) == (2 + sizeof(kWorkFields) / sizeof(Field)) * sizeof(void*), "a Work array without a row in kWorkFields");
 static_assert(sizeof(DedupDev) == sizeof(kDedupFields) / sizeof(Field) * sizeof(void*), "a DedupDev array without a row in kDedupFields");
@@ -384,6 +408,22 @@ static int ensure_dedup(lcv_ctx* ctx, size_t cap, int slot) {
   fields_bind(&ctx->Dslot[slot], kDedupFields, (uint8_t*)ctx->dedup_mem[slot], cap, 0);
   return LCV_OK;
 }
+// the batch-verification scratch of `slot` (lcv_set_rlc), laid out for the slot's work-space capacity of this moment
+// (pk_s stands in for W.pk, with W's stride), so it follows the work space when that grows; allocated by the slot's
+// first call with the mode on (be_free waits for the streams)
+static int ensure_rlc(lcv_ctx* ctx, int slot) {
+  const size_t cap = ctx->work_cap[slot];
+  if (cap == ctx->rlc_cap[slot] && ctx->rlc_mem[slot]) return LCV_OK;
+  if (ctx->rlc_mem[slot]) be_free(ctx, ctx->rlc_mem[slot]);
+  ctx->rlc_mem[slot] = nullptr;
+  ctx->rlc_cap[slot] = 0;
+  const size_t total = fields_bind(nullptr, kRlcFields, nullptr, cap, 0);
+  LCV_TRY(be_alloc(ctx, &ctx->rlc_mem[slot], total));
+  LCV_TRY(be_memset(ctx, ctx->rlc_mem[slot], 0, total));
+  fields_bind(&ctx->Rslot[slot], kRlcFields, (uint8_t*)ctx->rlc_mem[slot], cap, 0);
+  ctx->rlc_cap[slot] = cap;
+  return LCV_OK;
+}
 // the BLS stages' view of a deduplicated chunk of m items: the compact columns where they read the batch's and W's
 static void dedup_batch_view(const DedupDev& D, uint32_t m, BatchDev& Bu, Work& Wu) {
   Bu.att_beacon = D.att_beacon; Bu.sig_slot = D.sig_slot; Bu.bits = D.bits; Bu.sig = D.sig; Bu.n = m;
@@ -435,13 +475,14 @@ static int build_committees(lcv_ctx* ctx, CommitteeBufs& cb) {
     {kSop_##name##_rec, sizeof(kSop_##name##_rec)}, {kSop_##name##_consts, sizeof(kSop_##name##_consts)}
 static int upload_sop(lcv_ctx* ctx) {
   struct Src { const void* p; size_t bytes; };
-  const Src src[15] = {LCV_SOP_SRC(lines), LCV_SOP_SRC(miller_acc), LCV_SOP_SRC(fexp), LCV_SOP_SRC(h2c),
-                       LCV_SOP_SRC(miller)};
-  size_t off[15], total = 0;
-  for (int k = 0; k < 15; ++k) { off[k] = total; total += (src[k].bytes + 255) & ~(size_t)255; }
+  enum { NSRC = 18 };
+  const Src src[NSRC] = {LCV_SOP_SRC(lines), LCV_SOP_SRC(miller_acc), LCV_SOP_SRC(fexp), LCV_SOP_SRC(h2c),
+                         LCV_SOP_SRC(miller), LCV_SOP_SRC(f12mul)};
+  size_t off[NSRC], total = 0;
+  for (int k = 0; k < NSRC; ++k) { off[k] = total; total += (src[k].bytes + 255) & ~(size_t)255; }
   LCV_TRY(be_alloc(ctx, &ctx->sop_mem, total));
   uint8_t* m = (uint8_t*)ctx->sop_mem;
-  for (int k = 0; k < 15; ++k) LCV_TRY(be_h2d(ctx, m + off[k], src[k].p, src[k].bytes));
+  for (int k = 0; k < NSRC; ++k) LCV_TRY(be_h2d(ctx, m + off[k], src[k].p, src[k].bytes));
   auto view = [&](int k, uint32_t rounds, uint32_t slots, uint32_t nconst) {
     return SopView{(const uint32_t*)(m + off[3 * k]), (const uint32_t*)(m + off[3 * k + 1]),
                    (const uint32_t*)(m + off[3 * k + 2]), rounds, slots, nconst};
@@ -451,6 +492,7 @@ static int upload_sop(lcv_ctx* ctx) {
   ctx->sop_fexp = view(2, LCV_SOP_FEXP_ROUNDS, LCV_SOP_FEXP_SLOTS, LCV_SOP_FEXP_NCONST);
   ctx->sop_h2c = view(3, LCV_SOP_H2C_ROUNDS, LCV_SOP_H2C_SLOTS, LCV_SOP_H2C_NCONST);
   ctx->sop_miller = view(4, LCV_SOP_MILLER_ROUNDS, LCV_SOP_MILLER_SLOTS, LCV_SOP_MILLER_NCONST);
+  ctx->sop_f12mul = view(5, LCV_SOP_F12MUL_ROUNDS, LCV_SOP_F12MUL_SLOTS, LCV_SOP_F12MUL_NCONST);
   return be_sync(ctx);
 }
 
@@ -551,6 +593,54 @@ static int run_bls_direct(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C
 // pointers) is known, D is the slot's scratch for the items' compact columns
 struct DedupRun { DedupDev D; const uint32_t* rep; const uint32_t* urow; uint32_t m; };
 
+// A chunk of validate under randomised batch verification (lcv_set_rlc): groups of `group` = 1 << shift consecutive
+// items, the coefficients' key (seed, this chunk's batch counter), D the slot's scratch
+struct RlcRun { RlcDev D; RlcKey key; uint32_t shift; };
+
+// a batch-engine launch of the mode's own SOP functors (never on the fan engine: the mode acts on batch-engine chunks
+// only), counted in the engine log like launch_sop's; `prog`: the program's index in ctx->sop_items, or -1
+template <class F> static int launch_sop_rlc(lcv_ctx* ctx, const F& f, uint32_t n, int prog) {
+  constexpr uint32_t G = 64 / F::TEAM;
+  uint32_t g = prog >= 0 ? ctx->sop_items[prog] : 0;
+  if (g == 0 || g > G) g = G;
+  ctx->eng_count[1] += 1;
+  if (prog >= 0) ctx->eng_items[prog] = g;
+  return be_launch_sop(ctx, f, n, g);
+}
+
+// The end of the pairing check of a batch-verified chunk, after the Miller accumulation (W.f: the items' scaled Miller
+// values), on the main stream: the product tree over each group (shift launches with halving item counts, ping-pong
+// between the scratch's two arrays), the unchanged final exponentiation over the groups (a Work view: f -> the
+// products, pair_ok -> g_ok), the spread of the groups' results, and the unchanged final exponentiation again over the
+// items of failing groups, whose number stays on the device (worst-case grid)
+static int rlc_finish(lcv_ctx* ctx, const Work& W, uint32_t m, uint32_t flags, const RlcRun& L) {
+  const RlcDev& D = L.D;
+  const uint32_t* src = W.f;
+  uint32_t src_n = m;
+  LCV_TRY(stage(ctx, ST_RLC_PROD, [&]() -> int {
+    for (uint32_t level = 0; level < L.shift; ++level) {
+      uint32_t* dst = (level & 1u) ? D.prod_b : D.prod_a;
+      const uint32_t n = (src_n + 1) / 2;
+      LCV_TRY(launch_sop_rlc(ctx, F_sop_f12mul{W, ctx->sop_f12mul, src, dst, src_n, level, flags}, n, -1));
+      src = dst;
+      src_n = n;
+    }
+    return LCV_OK;
+  }));
+  Work Wg = W;
+  Wg.f = const_cast<uint32_t*>(src);
+  Wg.pair_ok = D.g_ok;
+  LCV_TRY(stage(ctx, ST_FEXP, [&] { return launch_sop(ctx, F_sop_fexp{Wg, ctx->sop_fexp}, src_n, m); }));
+  LCV_TRY(stage(ctx, ST_RLC_SPREAD, [&] { return be_launch(ctx, F_rlc_spread{W, D, L.shift, flags}, m); }));
+  return stage(ctx, ST_RLC_RETRY, [&] {
+    constexpr uint32_t G = 64 / F_sop_fexp_rows::TEAM;
+    uint32_t g = ctx->sop_items[2];
+    if (g == 0 || g > G) g = G;
+    ctx->eng_count[1] += 1;
+    return be_launch_sop_counted(ctx, F_sop_fexp_rows{W, ctx->sop_fexp, D.retry}, D.cnt, m, g);
+  });
+}
+
 // The BLS half of the pipeline for rows [0, n) on two streams of the active slot (a main stream and a
 // side stream), ordered by events:
 //   side: [HTR(next_sync_committee)] [item_pre: reasons, committee ids] [rank records], signature decode, [masked
@@ -574,7 +664,7 @@ struct DedupRun { DedupDev D; const uint32_t* rep; const uint32_t* urow; uint32_
 // wrote; F_verdict_dedup then gives each of the n rows its item's verdict.  Without R the items are the rows.
 static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint32_t n, uint32_t agg_items = 0,
                    const Params* P = nullptr, const BatchDev* nsc = nullptr, const StoreDev* S = nullptr,
-                   bool rank = false, const DedupRun* R = nullptr) {
+                   bool rank = false, const DedupRun* R = nullptr, const RlcRun* L = nullptr) {
   const Work& W = ctx->W;
 #if defined(LCV_CPU_FAST)
   if (!W.msg_b0) return run_bls_direct(ctx, B, C, n, agg_items, P, nsc, S, rank);
@@ -583,6 +673,11 @@ static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint3
   BatchDev Bu = B;
   Work Wu = W;
   if (R) dedup_batch_view(R->D, m, Bu, Wu);
+  if (L && fan_on(ctx, m)) L = nullptr;  // the mode acts on batch-engine chunks only
+  // the message pairing's walk reads the scaled aggregate key where it reads W.pk
+  Work Ws = Wu;
+  if (L) Ws.pk = L->D.pk_s;
+  auto scale = [&] { return stage(ctx, ST_RLC_SCALE, [&] { return be_launch(ctx, F_rlc_scale{Wu, L->key, L->D}, m); }); };
   LCV_TRY(be_mark(ctx, EV_START, 0));
   LCV_TRY(be_wait(ctx, 1, EV_START));  // the side stream starts after the slot's earlier main-stream work
   be_use_stream(ctx, 1);
@@ -602,6 +697,7 @@ static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint3
   // update), which makes this stream the longer one: then it stays on the main stream, after EV_PRE
   const bool agg_side = nsc == nullptr || nsc->npool < 64;
   if (agg_side) LCV_TRY(agg_stage(ctx, Bu, C, Wu, m, agg_items));
+  if (agg_side && L) LCV_TRY(scale());
   LCV_TRY(be_mark(ctx, EV_PRE, 1));
   be_use_stream(ctx, 0);
   if (R) LCV_TRY(be_wait(ctx, 0, EV_GATHER));
@@ -614,18 +710,29 @@ static int run_bls(lcv_ctx* ctx, const BatchDev& B, const CommitteeDev& C, uint3
   // accumulation after them measured 1.75 -> 1.9-2.3 ms per 10^4 batch (profiles/r05_v3/serial_ab.txt)
   LCV_TRY(be_wait(ctx, 0, EV_PRE));
   if (!agg_side) LCV_TRY(agg_stage(ctx, Bu, C, Wu, m, agg_items));
+  if (!agg_side && L) LCV_TRY(scale());  // before EV_H2C, which the signature's walk waits for
   const bool fused = fused_miller(ctx, m);  // latency mode: EV_PRE (after the side stream's last kernel) joins it
   if (!fused) {
     LCV_TRY(be_mark(ctx, EV_H2C, 0));
     be_use_stream(ctx, 1);
     LCV_TRY(be_wait(ctx, 1, EV_H2C));
-    LCV_TRY(stage(ctx, ST_LINES_SIG, [&] { return launch_sop(ctx, F_sop_lines{Wu, ctx->sop_lines, 1u}, m, m); }));
+    LCV_TRY(stage(ctx, ST_LINES_SIG, [&] {
+      if (L) return launch_sop_rlc(ctx, F_sop_lines_g1{Wu, ctx->sop_lines, L->D.g1_s}, m, 0);
+      return launch_sop(ctx, F_sop_lines{Wu, ctx->sop_lines, 1u}, m, m);
+    }));
     LCV_TRY(be_mark(ctx, EV_SIDE, 1));
     be_use_stream(ctx, 0);
-    LCV_TRY(stage(ctx, ST_LINES, [&] { return launch_sop(ctx, F_sop_lines{Wu, ctx->sop_lines, 2u}, m, m); }));
+    LCV_TRY(stage(ctx, ST_LINES, [&] { return launch_sop(ctx, F_sop_lines{Ws, ctx->sop_lines, 2u}, m, m); }));
     LCV_TRY(be_wait(ctx, 0, EV_SIDE));
   }
-  LCV_TRY(miller_fexp(ctx, Wu, m, fused));
+  if (L) {
+    // excluded from its group: an item whose verdict does not read pair_ok; the rows' pre-checks count where the
+    // items are the rows
+    LCV_TRY(stage(ctx, ST_MILLER, [&] { return launch_sop(ctx, F_sop_acc{Wu, ctx->sop_acc}, m, m); }));
+    LCV_TRY(rlc_finish(ctx, Wu, m, (P && !R) ? RLC_PRE : 0u, *L));
+  } else {
+    LCV_TRY(miller_fexp(ctx, Wu, m, fused));
+  }
   return stage(ctx, ST_VERDICT, [&] {
     return R ? be_launch(ctx, F_verdict_dedup{W, R->rep}, n) : be_launch(ctx, F_verdict{W}, n);
   });
@@ -692,6 +799,7 @@ void lcv_destroy(lcv_ctx* ctx) {
     if (ctx->work_mem[k]) be_free(ctx, ctx->work_mem[k]);
     if (ctx->seg_mem[k]) be_free(ctx, ctx->seg_mem[k]);
     if (ctx->dedup_mem[k]) be_free(ctx, ctx->dedup_mem[k]);
+    if (ctx->rlc_mem[k]) be_free(ctx, ctx->rlc_mem[k]);
     if (ctx->plan_pin[k]) be_host_free(ctx, ctx->plan_pin[k]);
   }
   if (ctx->sop_mem) be_free(ctx, ctx->sop_mem);
@@ -1050,6 +1158,7 @@ struct ValidateRun {
   FoldSegDev seg_dev;
   size_t fold_bytes;
   bool dedup;       // lcv_set_dedup: the chunks run the BLS half once per distinct item
+  bool rlc;         // lcv_set_rlc: the batch-engine chunks pay one final exponentiation per group of items
   bool pinned_out = false;  // the results wait in ctx->hsync.out for validate_finish
 };
 
@@ -1116,16 +1225,45 @@ static void count_items(ValidateRun& v, uint64_t rows, uint64_t items) {
   v.ctx->dd_rows[v.slot] += rows;
   v.ctx->dd_items[v.slot] += items;
 }
+// rlc_chunk: a chunk of `items` items on the batch engine under lcv_set_rlc gets the slot's scratch, the next batch
+// counter and its groups counted for lcv_last_rlc (the batch's first chunk on a slot zeroes that slot's count of retried
+// rows, every chunk the length of retry[]); else L stays null and the chunk runs as with the mode off
+#if defined(LCV_CPU_FAST)
+static bool rlc_on(const lcv_ctx*) { return false; }  // run_bls's direct branch runs every row: 0 groups
+#else
+static bool rlc_on(const lcv_ctx* ctx) { return ctx->rlc_group != 0; }
+#endif
+static int rlc_chunk(ValidateRun& v, int sl, uint32_t items, RlcRun& run, const RlcRun** L) {
+  lcv_ctx* ctx = v.ctx;
+  *L = nullptr;
+  if (!v.rlc || items == 0 || fan_on(ctx, items)) return LCV_OK;
+  LCV_TRY(ensure_rlc(ctx, sl));
+  run.D = ctx->Rslot[sl];
+  for (int k = 0; k < 8; ++k) run.key.seed[k] = ctx->rlc_seed[k];
+  run.key.counter = ctx->rlc_counter++;
+  run.shift = 0;
+  while ((1u << run.shift) < ctx->rlc_group) ++run.shift;
+  const bool first = !(ctx->rl_used[v.slot] & (1u << sl));
+  LCV_TRY(be_memset(ctx, run.D.cnt, 0, first ? 2 * sizeof(uint32_t) : sizeof(uint32_t)));
+  ctx->rl_used[v.slot] |= 1u << sl;
+  ctx->rl_groups[v.slot] += (items + ctx->rlc_group - 1) / ctx->rlc_group;
+  *L = &run;
+  return LCV_OK;
+}
 static int bls_chunk(ValidateRun& v, int sl, const BatchDev& Bc, size_t base, uint32_t m, const BatchDev* nsc, bool rank) {
+  RlcRun run;
+  const RlcRun* L = nullptr;
   if (!v.dedup) {
     count_items(v, m, m);
-    return run_bls(v.ctx, Bc, v.C, m, 0, &v.P, nsc, v.S, rank);
+    LCV_TRY(rlc_chunk(v, sl, m, run, &L));
+    return run_bls(v.ctx, Bc, v.C, m, 0, &v.P, nsc, v.S, rank, nullptr, L);
   }
   DedupRun R;
   count_items(v, m, 0);  // (the rows count even where the grouping fails)
   LCV_TRY(dedup_chunk(v.ctx, v.db, sl, base, m, R));
   count_items(v, 0, R.m);
-  return run_bls(v.ctx, Bc, v.C, m, 0, &v.P, nsc, v.S, rank, &R);
+  LCV_TRY(rlc_chunk(v, sl, R.m, run, &L));
+  return run_bls(v.ctx, Bc, v.C, m, 0, &v.P, nsc, v.S, rank, &R, L);
 }
 
 // what follows the verdicts of rows [base, base + m) in the active work space, on the main stream: the fold
@@ -1253,6 +1391,9 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
   const bool piped = !v.async && ns > 1 && ctx->pipe_chunks > 1;
   v.dedup = dedup_on(ctx) && !piped && (db->plan_m > 0 || !db->cls.empty());
   ctx->dd_rows[v.slot] = ctx->dd_items[v.slot] = 0;
+  v.rlc = rlc_on(ctx) && !piped;
+  ctx->rl_groups[v.slot] = 0;
+  ctx->rl_used[v.slot] = 0;
   const bool marks_were_off = ctx->marks_off;
   if (v.async) {
     ctx->marks_off = true;  // nothing collects an asynchronous batch's stage marks
@@ -1989,10 +2130,12 @@ int lcv_debug_event_pool(lcv_ctx* ctx, uint64_t* events_out) {
   return LCV_OK;
 }
 
-// test hook: validate cuts batches into chunks of `rows` (a multiple of 64; default 65536), so the
-// chunk rotation over the work-space slots runs at host-simulation sizes
+// test hook: validate cuts batches into chunks of `rows` (default 65536), so the chunk rotation over the work-space
+// slots runs at host-simulation sizes.  Any size works: every chunk starts at item 0 of its slot's work space (the
+// sliced pipeline rounds its slices to whole waves itself); sizes that are no multiple of a group give the batch
+// verification's groups (lcv_set_rlc) a short tail in every chunk
 int lcv_debug_set_chunk(lcv_ctx* ctx, uint64_t rows) {
-  if (!ctx || rows < 64 || rows > 65536 || rows % 64) return fail(ctx, LCV_EINVAL, "lcv_debug_set_chunk: 64 <= rows <= 65536, rows % 64 == 0");
+  if (!ctx || rows < 1 || rows > 65536) return fail(ctx, LCV_EINVAL, "lcv_debug_set_chunk: 1 <= rows <= 65536");
   ctx->chunk = (size_t)rows;
   return LCV_OK;
 }
@@ -2015,6 +2158,7 @@ extern "C" int lcv_debug_work_check(lcv_ctx* ctx, uint64_t cap, uint64_t slice, 
   for (int s = 0; s < nslots; ++s) {
     LCV_TRY(ensure_work(ctx, cap, 5, s));  // a committee pool of 5
     LCV_TRY(ensure_dedup(ctx, cap, s));    // and the slot's deduplication scratch (lcv_set_dedup), checked in (2)
+    LCV_TRY(ensure_rlc(ctx, s));           // and its batch-verification scratch (lcv_set_rlc), likewise
   }
   ctx->W = ctx->Wslot[0];
   // (1) slices: item j of work_view(W, b) is item b + j of W, element for element, in every per-item field
@@ -2054,6 +2198,7 @@ extern "C" int lcv_debug_work_check(lcv_ctx* ctx, uint64_t cap, uint64_t slice, 
     const Work& W = ctx->Wslot[s];
     for (const Field& f : kWorkFields) ranges(s, &W, f, "", W.cap, W.pool_cap);
     for (const Field& f : kDedupFields) ranges(s, &ctx->Dslot[s], f, "dedup_", W.cap, 0);
+    for (const Field& f : kRlcFields) ranges(s, &ctx->Rslot[s], f, "rlc_", W.cap, 0);
   }
   for (size_t a = 0; a < rg.size(); ++a)
     for (size_t b = a + 1; b < rg.size(); ++b)
@@ -2091,9 +2236,52 @@ int lcv_set_pipeline(lcv_ctx* ctx, int streams, int chunks) {
   if (!ctx || streams < 1 || chunks < 1 || chunks > 4096) return fail(ctx, LCV_EINVAL, "lcv_set_pipeline: streams >= 1, 1 <= chunks <= 4096");
   if (streams > 1 && ctx->dedup)
     return fail(ctx, LCV_EINVAL, "lcv_set_pipeline: no multi-stream pipeline while lcv_set_dedup is on (sliced chains would need a grouping per slice)");
+  if (streams > 1 && ctx->rlc_group)
+    return fail(ctx, LCV_EINVAL, "lcv_set_pipeline: no multi-stream pipeline while lcv_set_rlc is on (the sliced chains run every row)");
   ctx->pipe_streams = streams < 4 ? streams : 4;
   ctx->pipe_chunks = chunks;
   return LCV_OK;
+}
+
+// ---- randomised batch verification (include/lcv.h "Batch verification")
+int lcv_set_rlc(lcv_ctx* ctx, uint32_t group, const uint8_t* seed32) {
+  if (!ctx) return LCV_EINVAL;
+  if (group == 0) {
+    ctx->rlc_group = 0;
+    return LCV_OK;
+  }
+  if (group < 2 || group > 64 || (group & (group - 1)))
+    return fail(ctx, LCV_EINVAL, "lcv_set_rlc: group must be 0 (off), 2, 4, 8, 16, 32 or 64");
+  uint32_t any = 0;
+  for (int k = 0; seed32 && k < 32; ++k) any |= seed32[k];
+  if (!any) return fail(ctx, LCV_EINVAL, "lcv_set_rlc: the seed must be 32 bytes that are not all zero");
+  if (ctx->pipe_streams > 1)
+    return fail(ctx, LCV_EINVAL, "lcv_set_rlc: not with a multi-stream pipeline (lcv_set_pipeline streams > 1): the sliced chains run every row");
+  for (int k = 0; k < 8; ++k) ctx->rlc_seed[k] = host_be32(seed32 + 4 * k);
+  ctx->rlc_seeded = true;
+  ctx->rlc_group = group;
+  return LCV_OK;
+}
+
+// the retried rows are counted on the device, in the scratch of every slot the batch's chunks ran on: one small
+// blocking read each, here and not on the asynchronous path
+int lcv_last_rlc(lcv_ctx* ctx, int slot, uint64_t* groups, uint64_t* retried_rows) {
+  if (!ctx || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_last_rlc: slot must be 0..7");
+  if (groups) *groups = ctx->rl_groups[slot];
+  if (!retried_rows) return LCV_OK;
+  uint64_t total = 0;
+  int rc = LCV_OK;
+  for (int s = 0; s < LCV_SLOTS && rc == LCV_OK; ++s) {
+    if (!(ctx->rl_used[slot] & (1u << s)) || !ctx->rlc_mem[s]) continue;
+    uint32_t c = 0;
+    be_set_slot(ctx, s);
+    rc = be_d2h(ctx, &c, ctx->Rslot[s].cnt + 1, sizeof(c));
+    if (rc == LCV_OK) rc = be_sync_slot(ctx);
+    total += c;
+  }
+  be_set_slot(ctx, 0);
+  *retried_rows = total;
+  return rc;
 }
 
 // ---- deduplicated BLS half (include/lcv.h "Deduplicated signatures")
@@ -2385,6 +2573,25 @@ int lcv_debug_pairing(lcv_ctx* ctx, const uint8_t* p96, const uint8_t* q192, uin
   });
   be_collect_timings(ctx);  // miller / final_exp kernel times (lcv_last_timings)
   return rc;
+}
+
+// ---- test hooks of randomised batch verification (lcv_rlc.hpp)
+int lcv_debug_rlc_coeffs(lcv_ctx* ctx, uint64_t counter, uint64_t n, uint64_t* out_u64) {
+  if (!ctx || !out_u64) return fail(ctx, LCV_EINVAL, "lcv_debug_rlc_coeffs: null argument");
+  if (!ctx->rlc_seeded) return fail(ctx, LCV_ESTATE, "lcv_debug_rlc_coeffs: lcv_set_rlc has set no seed");
+  RlcKey key;
+  for (int k = 0; k < 8; ++k) key.seed[k] = ctx->rlc_seed[k];
+  key.counter = counter;
+  return simple_call(ctx, n, {}, {{out_u64, 8 * n}}, [&](std::vector<uint8_t*>& d) {
+    return be_launch(ctx, F_dbg_rlc_coeffs{key, (uint64_t*)d[0]}, (uint32_t)n);
+  });
+}
+
+int lcv_debug_rlc_scale(lcv_ctx* ctx, const uint8_t* p96, const uint64_t* r_u64, uint64_t n, uint8_t* out96) {
+  if (!ctx || !p96 || !r_u64 || !out96) return fail(ctx, LCV_EINVAL, "lcv_debug_rlc_scale: null argument");
+  return simple_call(ctx, n, {{p96, 96 * n}, {r_u64, 8 * n}}, {{out96, 96 * n}}, [&](std::vector<uint8_t*>& d) {
+    return be_launch(ctx, F_dbg_rlc_scale{d[0], (const uint64_t*)d[1], d[2]}, (uint32_t)n);
+  });
 }
 
 }  // extern "C"

@@ -204,6 +204,13 @@ template <class F> static int be_launch_sop(lcv_ctx* ctx, const F& f, uint32_t n
   return LCV_OK;
 }
 
+template <class F> static int be_launch_sop_counted(lcv_ctx* ctx, const F& f, const uint32_t* n_dev, uint32_t n_max, uint32_t g) {
+  if (n_max == 0) return LCV_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->be.device));
+  HIPCHK(ctx, lcv_hip_launch_sop_counted<F>(f, n_dev, n_max, cur_stream(ctx), g));  // lcv_k_rlc.hip
+  return LCV_OK;
+}
+
 template <class F> static int be_launch_sop_fan(lcv_ctx* ctx, const F& f, uint32_t n) {
   if (n == 0) return LCV_OK;
   HIPCHK(ctx, hipSetDevice(ctx->be.device));

@@ -109,6 +109,11 @@ template <class F> static int be_launch_sop(lcv_ctx*, const F& f, uint32_t n, ui
   return LCV_OK;
 }
 
+// every launch runs in program order, so the count is there to read
+template <class F> static int be_launch_sop_counted(lcv_ctx* ctx, const F& f, const uint32_t* n_dev, uint32_t n_max, uint32_t g) {
+  return be_launch_sop(ctx, f, *n_dev < n_max ? *n_dev : n_max, g);
+}
+
 static void be_stage_begin(lcv_ctx* ctx, int stage) {
   if (ctx->marks_off) return;
   Backend& b = ctx->be;

@@ -11,6 +11,7 @@ template <class F> hipError_t lcv_hip_launch(const F& f, uint32_t n, hipStream_t
 template <class F> hipError_t lcv_hip_launch_team(const F& f, uint32_t n, hipStream_t s);
 template <class F> hipError_t lcv_hip_launch_sop(const F& f, uint32_t n, hipStream_t s, uint32_t g = 0);
 template <class F> hipError_t lcv_hip_launch_sop_fan(const F& f, uint32_t n, hipStream_t s);
+template <class F> hipError_t lcv_hip_launch_sop_counted(const F& f, const uint32_t* n_dev, uint32_t n_max, hipStream_t s, uint32_t g = 0);
 
 #ifdef LCV_KERNEL_UNIT
 template <class F>
@@ -70,6 +71,17 @@ template <class F> hipError_t lcv_hip_launch_sop(const F& f, uint32_t n, hipStre
   hipLaunchKernelGGL(k_sop<F>, dim3(blocks), dim3(64), lds_bytes, s, f, n, g);
   return hipGetLastError();
 }
+// the same round loop over *n_dev <= n_max items, a count that stays on the device (lcv_rlc.hpp k_sop_counted): the
+// grid is n_max's, the blocks past the count return at once
+template <class F> __global__ void k_sop_counted(F f, const uint32_t* n_dev, uint32_t g);
+template <class F> hipError_t lcv_hip_launch_sop_counted(const F& f, const uint32_t* n_dev, uint32_t n_max, hipStream_t s, uint32_t g) {
+  constexpr uint32_t G = 64 / F::TEAM;
+  if (g == 0 || g > G) g = G;
+  const uint32_t blocks = (n_max + g - 1) / g;
+  const size_t lds_bytes = 4 * (size_t)(F::SHARED_WORDS + LCV_SOP_QP_WORDS + g * F::LDS_WORDS);
+  hipLaunchKernelGGL(k_sop_counted<F>, dim3(blocks), dim3(64), lds_bytes, s, f, n_dev, g);
+  return hipGetLastError();
+}
 // the fan engine (latency mode, lcv_sop_fan.hpp): one item per block of TEAM x MAXK x F::FAN_PARTS lanes
 // (whole waves), and at least 16 lanes per op when the ops' reductions run on rows of 16 lanes (lcv_sop_row.hpp).
 // Row tails for programs of at most LCV_FAN_ROW_MAX_TEAM ops a round (lines 10, acc 12, fexp 12, h2c 8); the fused Miller program
@@ -90,6 +102,7 @@ template <class F> hipError_t lcv_hip_launch_sop_fan(const F& f, uint32_t n, hip
   return hipGetLastError();
 }
 #define LCV_INSTANTIATE_SOP(F) template hipError_t lcv_hip_launch_sop<F>(const F&, uint32_t, hipStream_t, uint32_t);
+#define LCV_INSTANTIATE_SOP_COUNTED(F) template hipError_t lcv_hip_launch_sop_counted<F>(const F&, const uint32_t*, uint32_t, hipStream_t, uint32_t);
 #define LCV_INSTANTIATE_SOP_FAN(F) template hipError_t lcv_hip_launch_sop_fan<F>(const F&, uint32_t, hipStream_t);
 #define LCV_INSTANTIATE(F) template hipError_t lcv_hip_launch<F>(const F&, uint32_t, hipStream_t);
 #define LCV_INSTANTIATE_TEAM(F) template hipError_t lcv_hip_launch_team<F>(const F&, uint32_t, hipStream_t);

@@ -157,6 +157,10 @@ SIGNATURES = {
     "lcv_set_dedup": (C.c_int, [C.c_void_p, C.c_int]),
     "lcv_last_dedup": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p]),
     "lcv_debug_dedup_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
+    "lcv_set_rlc": (C.c_int, [C.c_void_p, C.c_uint32, u8p]),
+    "lcv_last_rlc": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p]),
+    "lcv_debug_rlc_coeffs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u64p]),
+    "lcv_debug_rlc_scale": (C.c_int, [C.c_void_p, u8p, u64p, C.c_uint64, u8p]),
     "lcv_set_config": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lcv_stage_name": (C.c_char_p, [C.c_int]),
     "lcv_comm_unique_id": (C.c_int, [u8p]),

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
 from dataclasses import dataclass
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -235,6 +236,8 @@ class Verifier:
         self.pipeline = (1, 1)  # lcv_set_pipeline's (streams, chunks)
         self.chunk_rows = 65536  # rows per validate chunk, and the most one asynchronous call takes (debug_set_chunk)
         self.dedup = False  # lcv_set_dedup's value
+        self.rlc_group = 0  # lcv_set_rlc's group (0: off) and the seed of the last call that gave one
+        self.rlc_seed: Optional[bytes] = None
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc: int, what: str):
@@ -300,8 +303,54 @@ class Verifier:
         every row collides, so only the full compare of the rows' bytes separates them)."""
         self._check(self.lib.lcv_debug_dedup_hash_bits(self.ctx, int(bits)), "lcv_debug_dedup_hash_bits")
 
+    def set_rlc(self, group: int, seed: Optional[bytes] = None) -> None:
+        """Randomised batch verification (lcv_set_rlc; off by default): groups of `group` (2, 4, ... 64) consecutive
+        items of a batch-engine chunk pay one final exponentiation, and only the items of a failing group one of their
+        own; 0 turns the mode off.  `seed`: 32 bytes that whoever supplies updates cannot predict — by default drawn
+        from os.urandom by this call.  A wrong group is accepted with probability about 2^-64; every other verdict and
+        every reason is that of the mode off.  LcvError (status -1) for any other group, an all-zero seed, or together
+        with a multi-stream pipeline (set_pipeline streams > 1), from whichever call comes second."""
+        group = int(group)
+        if group and seed is None:
+            seed = os.urandom(32)
+        if seed is not None and len(bytes(seed)) != 32:
+            raise ValueError("the seed must be 32 bytes")
+        s = as_u8(bytes(seed)) if seed is not None else None
+        self._check(self.lib.lcv_set_rlc(self.ctx, group, ptr(s) if s is not None else None), "lcv_set_rlc")
+        self.rlc_group = group
+        if seed is not None:
+            self.rlc_seed = bytes(seed)
+
+    def last_rlc(self, slot: int = 0) -> Tuple[int, int]:
+        """(groups, rows retried after a failing group) of the last batch enqueued on work-space slot `slot`
+        (lcv_last_rlc), summed over its chunks; valid once that batch has been waited for.  groups == 0: the mode did
+        not act (off, the fan engine, the CPU-baseline build)."""
+        groups, retried = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.lcv_last_rlc(self.ctx, int(slot), C.byref(groups), C.byref(retried)), "lcv_last_rlc")
+        return int(groups.value), int(retried.value)
+
+    def debug_rlc_coeffs(self, counter: int, n: int) -> np.ndarray:
+        """Test hook (lcv_debug_rlc_coeffs): the n coefficients the device derives for batch counter `counter` under
+        the seed of the last set_rlc."""
+        out = np.zeros(int(n), np.uint64)
+        self._check(self.lib.lcv_debug_rlc_coeffs(self.ctx, int(counter), int(n), ptr(out, C.c_uint64)),
+                    "lcv_debug_rlc_coeffs")
+        return out
+
+    def debug_rlc_scale(self, p96: np.ndarray, r: np.ndarray) -> np.ndarray:
+        """Test hook (lcv_debug_rlc_scale): r[i] * P[i] for affine G1 points (rows of x || y, 48 big-endian bytes
+        each), through the scaling kernel's ladder and shared inversion."""
+        p = np.ascontiguousarray(p96, np.uint8).reshape(-1, 96)
+        rr = np.ascontiguousarray(r, np.uint64).reshape(-1)
+        if rr.shape[0] != p.shape[0]:
+            raise ValueError("one coefficient per point")
+        out = np.zeros_like(p)
+        self._check(self.lib.lcv_debug_rlc_scale(self.ctx, ptr(p), ptr(rr, C.c_uint64), p.shape[0], ptr(out)),
+                    "lcv_debug_rlc_scale")
+        return out
+
     def debug_set_chunk(self, rows: int) -> None:
-        """Test hook (lcv_debug_set_chunk): rows per validate chunk, a multiple of 64 up to the default 65536."""
+        """Test hook (lcv_debug_set_chunk): rows per validate chunk, 1 up to the default 65536."""
         self._check(self.lib.lcv_debug_set_chunk(self.ctx, int(rows)), "lcv_debug_set_chunk")
         self.chunk_rows = int(rows)
 

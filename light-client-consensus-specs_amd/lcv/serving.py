@@ -22,7 +22,8 @@ Item = Union[PackedUpdates, Tuple[PackedUpdates, np.ndarray]]
 
 
 def validate_stream(verifier: Verifier, items: Iterable[Item], current_slot: int, genesis_validators_root: bytes,
-                    in_flight: int = SLOTS, dedup: Optional[bool] = None) -> Iterator[Tuple[np.ndarray, np.ndarray]]:
+                    in_flight: int = SLOTS, dedup: Optional[bool] = None,
+                    rlc_group: int = 0) -> Iterator[Tuple[np.ndarray, np.ndarray]]:
     """Validate every item of `items` and yield its (verdicts: bool array, reason codes: uint8 array), in input
     order.  An item is a PackedUpdates — validated against the store of Verifier.set_store, as
     Verifier.validate does — or (PackedUpdates, store_index) — update i against row store_index[i] of the table
@@ -38,7 +39,11 @@ def validate_stream(verifier: Verifier, items: Iterable[Item], current_slot: int
 
     `dedup`: None leaves the verifier's setting (Verifier.set_dedup) alone; a bool sets it for the stream — every
     distinct signature of a piece checked once, for streams that relay one update to many stores — and restores
-    the previous setting when the generator ends."""
+    the previous setting when the generator ends.
+
+    `rlc_group`: 0 leaves the verifier's batch-verification setting (Verifier.set_rlc) alone; 2, 4, ... 64 turns the
+    mode on for the stream with that group size and a seed drawn from os.urandom, and restores the previous setting
+    (group and seed) when the generator ends."""
     in_flight = int(in_flight)
     if not 1 <= in_flight <= SLOTS:
         raise ValueError(f"in_flight must be 1..{SLOTS}")
@@ -50,6 +55,15 @@ def validate_stream(verifier: Verifier, items: Iterable[Item], current_slot: int
     dedup_before = bool(getattr(verifier, "dedup", False))
     if dedup is not None:
         verifier.set_dedup(bool(dedup))
+    rlc_group = int(rlc_group)
+    rlc_before = (int(getattr(verifier, "rlc_group", 0)), getattr(verifier, "rlc_seed", None))
+    if rlc_group:
+        try:
+            verifier.set_rlc(rlc_group)
+        except Exception:
+            if dedup is not None:
+                verifier.set_dedup(dedup_before)
+            raise
 
     def finish_oldest():
         slot, rows, last = pending.popleft()
@@ -101,3 +115,5 @@ def validate_stream(verifier: Verifier, items: Iterable[Item], current_slot: int
                     pass
         if dedup is not None:
             verifier.set_dedup(dedup_before)
+        if rlc_group:
+            verifier.set_rlc(rlc_before[0], rlc_before[1])

@@ -1319,6 +1319,17 @@ def check_h2c(hp):
     print("  SOP hash_to_G2 tail checked against the oracle")
 
 
+# ============================================================================ batch verification's group product
+def f12mul_program(team=12):
+    """r = a * b, one dense Fp12 product in place over a (lcv_set_rlc: the product tree over a group's Miller values,
+    F_sop_f12mul): a in slots 0..11 and b in slots 12..23, both in W.f's coefficient order (slot 2 g + c)."""
+    p = Program("f12mul", team)
+    a = fp12_slots(p, "a")
+    b = fp12_slots(p, "b")
+    p.round(fp12_mul_ops(a, b, a))
+    return p
+
+
 # ============================================================================ checks against the oracle
 def _f12_from_mem(p, mem, name):
     g = [(unmont(mem[p.named[f"{name}{i}_0"]]), unmont(mem[p.named[f"{name}{i}_1"]])) for i in range(6)]
@@ -1443,6 +1454,21 @@ def check_fexp(fp):
     print("  SOP final exponentiation checked against the oracle (e^3)")
 
 
+def check_f12mul(mp):
+    from oracle import bls12_381 as B
+    rnd = random.Random(31)
+    for _ in range(3):
+        fa, fb = (tuple(tuple((rnd.randrange(P), rnd.randrange(P)) for _ in range(3)) for _ in range(2)) for _ in range(2))
+        mem = {s: 0 for s in range(mp.nslots)}
+        for nm, f in (("a", fa), ("b", fb)):
+            g = B.f12_coeffs(f)
+            for i in range(6):
+                mem[mp.named[f"{nm}{i}_0"]], mem[mp.named[f"{nm}{i}_1"]] = mont(g[i][0]), mont(g[i][1])
+        mp.emulate(mem)
+        assert B.f12_from_coeffs(_f12_from_mem(mp, mem, "a")) == B.f12_mul(fa, fb), "SOP f12mul mismatch"
+    print("  SOP Fp12 product checked against the oracle's f12_mul")
+
+
 # ============================================================================ emit
 def emit(progs, path):
     lines = ["// GENERATED by tools/gen_sop.py — do not edit.  SOP team programs (see lcv_sop.hpp).",
@@ -1490,7 +1516,7 @@ def build():
     fp = fexp_program()
     hp = h2c_program()
     mp = miller_program()
-    progs = (lp, ap, fp, hp, mp)
+    progs = (lp, ap, fp, hp, mp, f12mul_program())
     return progs
 
 
@@ -1509,6 +1535,7 @@ def main():
         check_miller_fused(progs[0], progs[1], progs[4])
         check_fexp(progs[2])
         check_h2c(progs[3])
+        check_f12mul(progs[5])
     emit(progs, args.out)
 
 
