@@ -551,6 +551,46 @@ int lcv_create_bootstraps(lcv_ctx* ctx, const lcv_state_views* states, uint64_t 
                           uint8_t* exec_branch128, uint32_t* committee_index, uint8_t* committee_branch160,
                           uint8_t* reason_out);
 
+/* ---- SSZ wire bytes of a resident batch, encoded on the device (csrc/lcv_wire_enc.hpp): what a full node serves —
+ * LightClientUpdatesByRange chunks, the finality / optimistic gossip topics and their Req/Resp forms
+ * (p2p-interface.md:74-115, 177-200, 222-262).  kind: 0 LightClientUpdate, 1 LightClientFinalityUpdate,
+ * 2 LightClientOptimisticUpdate of the row.  The bytes are those of lcv.wire.encode_updates (the inverse of
+ * lcv_ssz_decode_updates for rows that came from such messages).
+ * lcv_encode_pitch: the bytes between consecutive messages of the output, a multiple of 16: the longest message of
+ * `kind` over the three forks, rounded up.  kind 0 update: 26880, 1 finality: 2096, 2 optimistic: 1040; 0 for any
+ * other kind.
+ * lcv_batch_encode.  rows == NULL: every row of b in order (nrows ignored); else rows[0 .. nrows), each < b's n,
+ * repeats allowed, gathered on the device as lcv_batch_download does.  fork: 0 Deneb, 1 Capella, 2 Altair for every
+ * row, or LCV_FORK_AUTO: per row from compute_epoch_at_slot(attested beacon slot) under lcv_set_config's fork epochs
+ * (>= DENEB 0, >= CAPELLA 1, else 2), so one by-range response may straddle a fork boundary (p2p-interface.md:189).
+ * With m the number of messages and pitch = lcv_encode_pitch of the kind:
+ *   out         m x pitch bytes, message i at out + i * pitch, EVERY byte of the m x pitch written (zero past len)
+ *   len_out     m x u32: the message's length
+ *   fork_out    m x u8: the fork code used
+ *   version_out m x 4 B: compute_fork_version(the attested slot's epoch) — the chunk's ForkDigest context version,
+ *               whatever `fork` forces
+ *   status_out  m x u8: 0 ok; 1 an Altair-format row with execution data (a non-zero byte in the execution record or
+ *               execution branch of a header that is encoded: the finalized header is not, for kind 2); 2 an encoded
+ *               header's extra_data length > 32.  Such a row has len 0 and an all-zero area.
+ * Refused with LCV_EINVAL before any launch, naming the first offender, the outputs untouched: a null argument, kind
+ * or fork out of range, rows[i] >= n.  No message (b's n == 0, or rows with nrows == 0): LCV_OK, nothing written.
+ * Device scratch for the areas is bounded by LCV_ENCODE_SCRATCH_BYTES, not by m: the rows are encoded in chunks of
+ * LCV_ENCODE_SCRATCH_BYTES / pitch messages (2496 updates), each chunk copied out before the scratch is reused; the
+ * scratch is kept by the context.  Kernel time: lcv_last_timings' wire_encode stage.  Synchronous, on work-space
+ * slot 0's stream: wait for pending slots first.
+ * lcv_encode_updates is upload + encode + free for rows that live on the host.
+ * lcv_debug_set_encode_chunk (test hook): rows per encode chunk, where fewer than fit the scratch bound (0: the
+ * default).
+ * Out of scope: bootstraps, snappy framing and the Req/Resp result byte, compact (unpitched) output. */
+#define LCV_FORK_AUTO (-1)
+#define LCV_ENCODE_SCRATCH_BYTES (64u << 20)
+uint64_t lcv_encode_pitch(int kind);
+int lcv_batch_encode(lcv_ctx* ctx, lcv_dbatch* b, const uint32_t* rows, uint64_t nrows, int kind, int fork,
+                     uint8_t* out, uint32_t* len_out, uint8_t* fork_out, uint8_t* version_out, uint8_t* status_out);
+int lcv_encode_updates(lcv_ctx* ctx, const lcv_update_batch* batch, int kind, int fork, uint8_t* out,
+                       uint32_t* len_out, uint8_t* fork_out, uint8_t* version_out, uint8_t* status_out);
+int lcv_debug_set_encode_chunk(lcv_ctx* ctx, uint64_t rows);
+
 /* ---- SSZ wire decode (host only, no device work; csrc/lcv_wire.cpp).  Replaces the upstream SSZ
  * deserialisation of the reference's containers (sync-protocol.md:109-115 LightClientBootstrap,
  * :120-133 LightClientUpdate, :138-148 LightClientFinalityUpdate, :153-160 LightClientOptimisticUpdate)

@@ -14,6 +14,7 @@
 #include "lcv_items.hpp"
 #include "lcv_fold.hpp"
 #include "lcv_producer.hpp"
+#include "lcv_wire_enc.hpp"
 #include "lcv_dedup.hpp"
 #include "lcv_dedup_plan.hpp"
 #include "lcv_sop.hpp"
@@ -26,12 +27,13 @@ using namespace lcv;
 // operation to exactly one stage, and a HIP event pair brackets exactly one kernel on its stream).
 enum { ST_NSC = 0, ST_PRE, ST_H2C_MAP, ST_H2C, ST_SIG, ST_AGG, ST_MILLER, ST_FEXP, ST_VERDICT, ST_SETUP,
        ST_LINES, ST_LINES_SIG, ST_SIGROOT, ST_RANK, ST_FOLD, ST_PRODUCE_VIEWS, ST_PRODUCE_ROWS, ST_DEDUP,
-       ST_RLC_SCALE, ST_RLC_PROD, ST_RLC_SPREAD, ST_RLC_RETRY, ST_COUNT };
+       ST_RLC_SCALE, ST_RLC_PROD, ST_RLC_SPREAD, ST_RLC_RETRY, ST_WIRE_ENCODE, ST_COUNT };
 static const char* kStageNames[ST_COUNT] = {"nsc_htr", "pre_checks", "h2c_sswu", "hash_to_g2", "sig_decode",
                                             "g1_aggregate", "miller_loop", "final_exp", "verdict",
                                             "setup", "miller_lines", "miller_lines_sig", "signing_root",
                                             "store_rank", "store_fold", "produce_views", "produce_rows",
-                                            "dedup_gather", "rlc_scale", "rlc_product", "rlc_spread", "rlc_retry"};
+                                            "dedup_gather", "rlc_scale", "rlc_product", "rlc_spread", "rlc_retry",
+                                            "wire_encode"};
 
 struct CommitteeBufs {
   uint8_t* raw = nullptr;
@@ -194,6 +196,11 @@ struct lcv_ctx {
   RlcDev Rslot[LCV_SLOTS] = {};
   uint64_t rl_groups[LCV_SLOTS] = {};
   uint32_t rl_used[LCV_SLOTS] = {};
+  // lcv_batch_encode's scratch (one chunk of message areas, their result records, the chunk's row list): grown on
+  // demand up to LCV_ENCODE_SCRATCH_BYTES of areas, kept for the next call; enc_chunk: lcv_debug_set_encode_chunk
+  void* enc_mem = nullptr;
+  size_t enc_cap = 0;
+  uint64_t enc_chunk = 0;
 };
 
 static uint32_t host_be32(const uint8_t* p) {
@@ -803,6 +810,7 @@ void lcv_destroy(lcv_ctx* ctx) {
     if (ctx->plan_pin[k]) be_host_free(ctx, ctx->plan_pin[k]);
   }
   if (ctx->sop_mem) be_free(ctx, ctx->sop_mem);
+  if (ctx->enc_mem) be_free(ctx, ctx->enc_mem);
   if (ctx->comm_buf) be_free(ctx, ctx->comm_buf);
   for (void* p : ctx->comm_retired) be_free(ctx, p);
   auto free_host_slot = [ctx](HostSlot& h) {
@@ -2875,6 +2883,93 @@ int lcv_create_bootstraps(lcv_ctx* ctx, const lcv_state_views* states, uint64_t 
   };
   const int rc = body();
   if (R.mem) be_free(ctx, R.mem);
+  return rc;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ SSZ wire bytes of a resident batch (lcv_wire_enc.hpp)
+// The message areas are written into device scratch one chunk at a time and copied out before the scratch is reused:
+// at most LCV_ENCODE_SCRATCH_BYTES of areas, whatever the number of rows.  Copies and launches share one stream, so
+// a chunk's kernel starts after the previous chunk's areas have left.
+static const uint64_t kEncPitch[3] = {26880, 2096, 1040};
+static_assert(LCV_ENCODE_SCRATCH_BYTES >= 26880, "the scratch holds one message");
+
+extern "C" {
+
+uint64_t lcv_encode_pitch(int kind) { return (kind >= 0 && kind <= 2) ? kEncPitch[kind] : 0; }
+
+int lcv_debug_set_encode_chunk(lcv_ctx* ctx, uint64_t rows) {
+  if (!ctx) return LCV_EINVAL;
+  ctx->enc_chunk = rows;  // 0: as many as fit the scratch bound
+  return LCV_OK;
+}
+
+int lcv_batch_encode(lcv_ctx* ctx, lcv_dbatch* b, const uint32_t* rows, uint64_t nrows, int kind, int fork,
+                     uint8_t* out, uint32_t* len_out, uint8_t* fork_out, uint8_t* version_out, uint8_t* status_out) {
+  const char* who = "lcv_batch_encode";
+  if (!ctx || !b || !out || !len_out || !fork_out || !version_out || !status_out)
+    return fail(ctx, LCV_EINVAL, std::string(who) + ": null argument");
+  if (kind < 0 || kind > 2) return fail(ctx, LCV_EINVAL, std::string(who) + ": kind is 0 (update), 1 (finality) or 2 (optimistic)");
+  if (fork < LCV_FORK_AUTO || fork > 2)
+    return fail(ctx, LCV_EINVAL, std::string(who) + ": fork is 0 (Deneb), 1 (Capella), 2 (Altair) or LCV_FORK_AUTO");
+  if (rows) {
+    if (nrows >= 0xffffffffull) return fail(ctx, LCV_EINVAL, std::string(who) + ": need nrows < 2^32 - 1");
+    LCV_TRY(prod_check_index(ctx, who, "rows", rows, nrows, b->n));
+  }
+  const uint64_t m = rows ? nrows : b->n;
+  if (m == 0) return LCV_OK;
+  const uint64_t pitch = kEncPitch[kind];
+  uint64_t chunk = LCV_ENCODE_SCRATCH_BYTES / pitch;
+  if (ctx->enc_chunk && ctx->enc_chunk < chunk) chunk = ctx->enc_chunk;
+  if (m < chunk) chunk = m;
+  auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_meta = pad(chunk * pitch), o_rows = o_meta + pad(chunk * ENC_META_BYTES);
+  const size_t total = o_rows + pad(4 * chunk);
+  std::vector<uint8_t> meta;
+  try {
+    meta.resize(m * ENC_META_BYTES);
+  } catch (...) {  // an extern "C" entry point must not let an exception out
+    return fail(ctx, LCV_ENOMEM, std::string(who) + ": out of host memory");
+  }
+  be_set_slot(ctx, 0);
+  LCV_TRY(dev_alloc_grow(ctx, &ctx->enc_mem, &ctx->enc_cap, total, total));
+  uint8_t* d = (uint8_t*)ctx->enc_mem;
+  be_reset_timings(ctx);
+  for (uint64_t c0 = 0; c0 < m; c0 += chunk) {
+    const uint64_t mc = std::min(chunk, m - c0);
+    if (rows) LCV_TRY(be_h2d(ctx, d + o_rows, rows + c0, 4 * mc));
+    const EncArgs A = {b->B, rows ? (const uint32_t*)(d + o_rows) : nullptr, (uint32_t)c0, d, d + o_meta, ctx->cfg,
+                       (uint32_t)kind, (int32_t)fork, (uint32_t)pitch};
+    LCV_TRY(stage(ctx, ST_WIRE_ENCODE, [&] { return be_launch_team(ctx, F_wire_enc{A}, (uint32_t)mc); }));
+    LCV_TRY(be_d2h(ctx, out + c0 * pitch, d, mc * pitch));
+    LCV_TRY(be_d2h(ctx, meta.data() + c0 * ENC_META_BYTES, d + o_meta, mc * ENC_META_BYTES));
+  }
+  LCV_TRY(be_sync(ctx));
+  be_collect_timings(ctx);
+  for (uint64_t i = 0; i < m; ++i) {
+    const uint8_t* r = meta.data() + i * ENC_META_BYTES;
+    memcpy(&len_out[i], r, 4);
+    fork_out[i] = r[4];
+    status_out[i] = r[5];
+    memcpy(version_out + 4 * i, r + 8, 4);
+  }
+  return LCV_OK;
+}
+
+int lcv_encode_updates(lcv_ctx* ctx, const lcv_update_batch* batch, int kind, int fork, uint8_t* out, uint32_t* len_out,
+                       uint8_t* fork_out, uint8_t* version_out, uint8_t* status_out) {
+  const char* who = "lcv_encode_updates";
+  if (!ctx || !batch || !out || !len_out || !fork_out || !version_out || !status_out)
+    return fail(ctx, LCV_EINVAL, std::string(who) + ": null argument");
+  if (kind < 0 || kind > 2) return fail(ctx, LCV_EINVAL, std::string(who) + ": kind is 0 (update), 1 (finality) or 2 (optimistic)");
+  if (fork < LCV_FORK_AUTO || fork > 2)
+    return fail(ctx, LCV_EINVAL, std::string(who) + ": fork is 0 (Deneb), 1 (Capella), 2 (Altair) or LCV_FORK_AUTO");
+  if (batch->n == 0) return LCV_OK;
+  lcv_dbatch* db = nullptr;
+  LCV_TRY(batch_upload(ctx, batch, nullptr, &db));
+  const int rc = lcv_batch_encode(ctx, db, nullptr, 0, kind, fork, out, len_out, fork_out, version_out, status_out);
+  lcv_batch_free(ctx, db);
   return rc;
 }
 

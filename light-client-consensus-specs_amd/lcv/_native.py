@@ -186,6 +186,10 @@ SIGNATURES = {
     "lcv_rank_resident": (C.c_int, [C.c_void_p, C.c_void_p, u8p]),
     "lcv_create_bootstraps": (C.c_int, [C.c_void_p, C.POINTER(StateViews), C.c_uint64, C.POINTER(BlockViews), C.c_uint64,
                                         u8p, C.c_uint64, u32p, u32p, C.c_uint64, u8p, u8p, u8p, u32p, u8p, u8p]),
+    "lcv_encode_pitch": (C.c_uint64, [C.c_int]),
+    "lcv_batch_encode": (C.c_int, [C.c_void_p, C.c_void_p, u32p, C.c_uint64, C.c_int, C.c_int, u8p, u32p, u8p, u8p, u8p]),
+    "lcv_encode_updates": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), C.c_int, C.c_int, u8p, u32p, u8p, u8p, u8p]),
+    "lcv_debug_set_encode_chunk": (C.c_int, [C.c_void_p, C.c_uint64]),
     "lcv_ssz_decode_updates": (C.c_int, [u8p, u64p, u64p, C.c_uint64, C.c_int, C.c_int, C.POINTER(UpdateBatch),
                                          u64p, u64p, u8p]),
     "lcv_ssz_decode_updates_mixed": (C.c_int, [u8p, u64p, u64p, C.c_uint64, C.c_int, u8p, C.POINTER(UpdateBatch),

@@ -127,6 +127,30 @@ class PackedUpdates:
 
 
 UPDATE_KINDS = {"update": 0, "finality": 1, "optimistic": 2}
+WIRE_FORKS = {"deneb": 0, "capella": 1, "altair": 2, "auto": -1}  # lcv_batch_encode's fork codes; -1: LCV_FORK_AUTO
+
+
+@dataclass
+class EncodedMessages:
+    """SSZ wire messages as the device wrote them (lcv_batch_encode): message i is buf[i, :length[i]]; the rest of
+    its area is zero.  A row with a non-zero status has length 0."""
+    buf: np.ndarray      # (m, pitch) u8
+    length: np.ndarray   # (m,) u32
+    fork: np.ndarray     # (m,) u8  the fork code used: 0 Deneb, 1 Capella, 2 Altair
+    version: np.ndarray  # (m, 4) u8  the fork version of the attested slot's epoch (the chunk's ForkDigest context)
+    status: np.ndarray   # (m,) u8  0 ok, 1 Altair-format row with execution data, 2 extra_data longer than 32 bytes
+
+    @property
+    def n(self) -> int:
+        return int(self.buf.shape[0])
+
+    def messages(self) -> list:
+        return [self.buf[i, :int(self.length[i])].tobytes() for i in range(self.n)]
+
+    @staticmethod
+    def empty(m: int, pitch: int, fill: int = 0) -> "EncodedMessages":
+        return EncodedMessages(np.full((m, pitch), fill, np.uint8), np.zeros(m, np.uint32), np.zeros(m, np.uint8),
+                               np.zeros((m, 4), np.uint8), np.zeros(m, np.uint8))
 
 
 @dataclass
@@ -495,6 +519,55 @@ class Verifier:
         if rb.n:
             self._check(self.lib.lcv_rank_resident(self.ctx, rb.handle, ptr(out.view(np.uint8))), "lcv_rank_resident")
         return out
+
+    # ------------------------------------------------------------------ SSZ wire bytes on the device (include/lcv.h)
+    @staticmethod
+    def _wire_fork(fork) -> int:
+        f = WIRE_FORKS.get(fork, fork) if isinstance(fork, str) else fork
+        return int(f)
+
+    def encode_pitch(self, kind=0) -> int:
+        """Bytes between consecutive messages of an encode call's output (lcv_encode_pitch)."""
+        return int(self.lib.lcv_encode_pitch(self._kind(kind)))
+
+    def _encoded_out(self, m: int, kind: int, out: Optional[EncodedMessages]) -> EncodedMessages:
+        pitch = int(self.lib.lcv_encode_pitch(kind))
+        if out is None:
+            return EncodedMessages.empty(m, max(pitch, 16))
+        if out.buf.shape != (m, pitch) or out.buf.dtype != np.uint8 or not out.buf.flags.c_contiguous:
+            raise ValueError(f"out.buf: need C-contiguous uint8 ({m}, {pitch})")
+        return out
+
+    def encode_resident(self, rb: ResidentBatch, kind=0, fork="auto", rows=None,
+                        out: Optional[EncodedMessages] = None) -> EncodedMessages:
+        """The SSZ wire messages of a resident batch's rows, encoded on the device (lcv_batch_encode): every row, or
+        `rows` in that order.  kind 0 / "update", 1 / "finality", 2 / "optimistic"; fork "deneb", "capella", "altair"
+        for every row, or "auto": per row from the attested slot under the context's fork epochs.  `out`: arrays to
+        write into (EncodedMessages.empty(m, encode_pitch(kind)))."""
+        k, f = self._kind(kind), self._wire_fork(fork)
+        ix = None if rows is None else np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        m = rb.n if ix is None else ix.shape[0]
+        if not rb.handle and m == 0 and 0 <= k <= 2 and -1 <= f <= 2:
+            return self._encoded_out(0, k, out)  # (an empty resident batch has no handle)
+        e = self._encoded_out(m, k, out)
+        self._check(self.lib.lcv_batch_encode(self.ctx, rb.handle, None if ix is None else ptr(ix, C.c_uint32),
+                                              0 if ix is None else ix.shape[0], k, f, ptr(e.buf),
+                                              ptr(e.length, C.c_uint32), ptr(e.fork), ptr(e.version), ptr(e.status)),
+                    "lcv_batch_encode")
+        return e
+
+    def encode(self, batch: PackedUpdates, kind=0, fork="auto", out: Optional[EncodedMessages] = None) -> EncodedMessages:
+        """encode_resident for rows that live on the host (lcv_encode_updates: upload, encode, free)."""
+        k, f = self._kind(kind), self._wire_fork(fork)
+        b, keep = batch.to_c()
+        e = self._encoded_out(batch.n, k, out)
+        self._check(self.lib.lcv_encode_updates(self.ctx, C.byref(b), k, f, ptr(e.buf), ptr(e.length, C.c_uint32),
+                                                ptr(e.fork), ptr(e.version), ptr(e.status)), "lcv_encode_updates")
+        return e
+
+    def debug_set_encode_chunk(self, rows: int) -> None:
+        """Test hook (lcv_debug_set_encode_chunk): rows per encode chunk; 0: as many as fit the scratch bound."""
+        self._check(self.lib.lcv_debug_set_encode_chunk(self.ctx, int(rows)), "lcv_debug_set_encode_chunk")
 
     def create_bootstraps(self, views: PackedViews, state_idx, block_idx, reason: Optional[np.ndarray] = None):
         """create_light_client_bootstrap per (state_idx[i], block_idx[i]) (lcv_create_bootstraps) -> (beacon (n, 112),

@@ -521,3 +521,42 @@ def create_light_client_updates(states: Sequence[BeaconStateView], blocks: Seque
     from . import runtime
     v = verifier if verifier is not None else runtime.default_verifier()
     return v.create_updates(pack_views(states, blocks), cases, kind)
+
+
+MAX_REQUEST_LIGHT_CLIENT_UPDATES = 128
+
+
+def updates_by_range(rb, start_period: int, count: int, genesis_validators_root: bytes, verifier=None) -> list:
+    """The response chunks of LightClientUpdatesByRange (p2p-interface.md:177-200) from a resident batch of
+    candidate updates -> [(fork digest, SSZ LightClientUpdate)], at most min(128, count) of them (:187): the best
+    update (is_better_update; lcv.store.best_update_per_period) of each sync-committee period in [start_period,
+    start_period + count) that has one, in consecutive order by period.  The batch is ranked where it lies, and the
+    winners are encoded by one lcv_batch_encode call, the container of each chunk chosen from its attested slot
+    (:189); the chunk's digest is compute_fork_digest of the fork version at that slot.  Rows without a sync
+    committee participant (the all-zero rows of cases the producer refused) are never served."""
+    from . import runtime
+    from .device import RANK_N_MASK
+    from .store import best_update_per_period
+    from .wire import fork_digest
+    v = verifier if verifier is not None else runtime.default_verifier()
+    limit = min(MAX_REQUEST_LIGHT_CLIENT_UPDATES, int(count))
+    if limit <= 0 or rb.n == 0:
+        return []
+    rank = v.rank_resident(rb)
+    best = best_update_per_period(rb, v, rank=rank)
+    rows = [best[p] for p in sorted(best)
+            if start_period <= p < start_period + int(count) and int(rank["key0"][best[p]]) & RANK_N_MASK][:limit]
+    if not rows:
+        return []
+    enc = v.encode_resident(rb, "update", "auto", rows=rows)
+    bad = np.flatnonzero(enc.status)
+    if bad.size:
+        raise ValueError(f"updates_by_range: row {rows[int(bad[0])]} cannot be encoded (status {int(enc.status[bad[0]])})")
+    digests = {}
+    out = []
+    for i, msg in enumerate(enc.messages()):
+        ver = enc.version[i].tobytes()
+        if ver not in digests:  # at most five distinct versions
+            digests[ver] = fork_digest(ver, genesis_validators_root)
+        out.append((digests[ver], msg))
+    return out

@@ -495,14 +495,15 @@ def rank_updates(updates, verifier: Optional[Verifier] = None) -> np.ndarray:
     return v.rank(updates if isinstance(updates, PackedUpdates) else pack_updates(updates))
 
 
-def best_update_per_period(updates, verifier: Optional[Verifier] = None) -> dict:
+def best_update_per_period(updates, verifier: Optional[Verifier] = None, rank: Optional[np.ndarray] = None) -> dict:
     """full-node.md:184-187: the best LightClientUpdate (according to is_better_update) for each sync committee
     period -> {period: row}.  A row belongs to the period of its attested header; rows whose signature_slot lies
     in another period are left out.  Per period the first arg-max of the device's rank records (one lexsort).
     `updates` may be a ResidentBatch (Verifier.create_updates_resident, upload): it is ranked on the device
-    without a copy, and the rows are its rows (Verifier.download(rb, rows) fetches the winners)."""
+    without a copy, and the rows are its rows (Verifier.download(rb, rows) fetches the winners).  `rank`: the
+    batch's rank records where the caller already has them (rank_updates)."""
     v = verifier if verifier is not None else runtime.default_verifier()
-    rec = rank_updates(updates, v)
+    rec = rank if rank is not None else rank_updates(updates, v)
     spp = v.config.SLOTS_PER_PERIOD
     period = rec["attested_slot"] // np.uint64(spp)
     rows = np.nonzero(period == rec["signature_slot"] // np.uint64(spp))[0]

@@ -15,6 +15,9 @@ device verifier consumes; no per-update Python objects are built.
     decode_updates_status(messages, kind, fork)             -> (PackedUpdates, ok: np.ndarray[bool])
     decode_bootstrap(data, fork="deneb")                    -> Bootstrap (header rows, committee, branch)
     encode_updates(batch, kind="update", fork="deneb")      -> [bytes]  (serving side; inverse of decode)
+    encode_updates_device(batch_or_resident, kind, fork="auto", verifier) -> [bytes]  (the same bytes from the
+        device encoder, lcv_batch_encode; the fork per row from the attested slot)
+    fork_digest(version, genesis_validators_root)            -> 4 bytes (a chunk's ForkDigest context)
 
 `kind` "finality" / "optimistic" rows are the LightClientUpdate the reference builds from those
 messages (sync-protocol.md:563-571 / :582-590).  `messages` is a sequence of `bytes`, or a tuple
@@ -229,6 +232,33 @@ def encode_updates(batch: PackedUpdates, kind: str = "update", fork: str = "dene
         fixed = 4 + len(sc) + 4 + len(mid)
         out.append(fixed.to_bytes(4, "little") + sc + (fixed + len(att)).to_bytes(4, "little") + mid + att + fin)
     return out
+
+
+def encode_updates_device(batch, kind: str = "update", fork: str = "auto", verifier=None) -> list:
+    """encode_updates on the device (lcv_batch_encode: one kernel over the rows, no per-row Python): `batch` is a
+    PackedUpdates or a ResidentBatch; fork "auto" chooses the container per row from the attested slot under the
+    verifier's configuration (p2p-interface.md:189).  ValueError, as encode_updates raises, for an Altair-format row
+    that carries execution data, and for an extra_data length above 32."""
+    from .device import ResidentBatch, Verifier
+    if kind not in KINDS or (fork not in FORKS and fork != "auto"):
+        raise ValueError(f"kind must be one of {list(KINDS)}, fork one of {list(FORKS)} or 'auto'")
+    v = verifier if verifier is not None else (batch.v if isinstance(batch, ResidentBatch) else Verifier(0))
+    enc = v.encode_resident(batch, kind, fork) if isinstance(batch, ResidentBatch) else v.encode(batch, kind, fork)
+    bad = np.flatnonzero(enc.status)
+    if bad.size:
+        why = {1: "an Altair-format header carries no execution data", 2: "extra_data longer than 32 bytes"}
+        raise ValueError(f"{why.get(int(enc.status[bad[0]]), 'not encodable')}: row(s) {bad[:8].tolist()}")
+    return enc.messages()
+
+
+def fork_digest(version: bytes, genesis_validators_root: bytes) -> bytes:
+    """compute_fork_digest: the first 4 bytes of hash_tree_root(ForkData(current_version, genesis_validators_root)),
+    the context of a Req/Resp chunk and of the gossip topics (p2p-interface.md:82-85)."""
+    import hashlib
+    v, g = bytes(version), bytes(genesis_validators_root)
+    if len(v) != 4 or len(g) != 32:
+        raise ValueError("version is 4 bytes, genesis_validators_root 32")
+    return hashlib.sha256(v + bytes(28) + g).digest()[:4]
 
 
 def encode_bootstrap(beacon: bytes, execution: bytes, execution_branch: bytes, committee: bytes,
