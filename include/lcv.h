@@ -274,6 +274,9 @@ int lcv_batch_upload(lcv_ctx* ctx, const lcv_update_batch* batch, lcv_dbatch** o
 /* the same with the batch's store_index column (n entries): a table batch, see the store table above */
 int lcv_batch_upload_stores(lcv_ctx* ctx, const lcv_update_batch* batch, const uint32_t* store_index, lcv_dbatch** out);
 void lcv_batch_free(lcv_ctx* ctx, lcv_dbatch* b);
+/* a resident batch's rows and pool rows (what lcv_batch_download's arrays hold): a batch the device made, as
+ * lcv_batch_decode's, has a pool size only the batch knows */
+int lcv_batch_shape(lcv_ctx* ctx, const lcv_dbatch* b, uint64_t* n_out, uint64_t* npool_out);
 int lcv_validate_resident(lcv_ctx* ctx, lcv_dbatch* b, uint64_t current_slot, const uint8_t* genesis_validators_root,
                           uint8_t* verdict_out, uint8_t* reason_out);
 /* same, verdicts written to a DEVICE buffer of n bytes (for an RCCL all-gather); no host copy */
@@ -367,8 +370,8 @@ int lcv_debug_engine_log(lcv_ctx* ctx, uint64_t* out8, int reset);
  * column (and in the CPU-baseline build, whose direct path runs every row).
  * lcv_debug_dedup_hash_bits is a test hook: the host hash is truncated to `bits` bits (default 64; 0 makes every
  * row collide, so that only the full compare separates classes).
- * Out of scope: resident batches made on the device (lcv_create_updates_resident: no host bytes to class; they run
- * without deduplication); merging across chunks or across batches in flight; lcv_fast_aggregate_verify_batch;
+ * Out of scope: resident batches made on the device (lcv_create_updates_resident, lcv_batch_decode: no host bytes to
+ * class; they run without deduplication); merging across chunks or across batches in flight; lcv_fast_aggregate_verify_batch;
  * merging committee-table rows of equal content; skipping the BLS work of items all of whose rows failed a
  * pre-check. */
 int lcv_set_dedup(lcv_ctx* ctx, int on);
@@ -590,6 +593,46 @@ int lcv_batch_encode(lcv_ctx* ctx, lcv_dbatch* b, const uint32_t* rows, uint64_t
 int lcv_encode_updates(lcv_ctx* ctx, const lcv_update_batch* batch, int kind, int fork, uint8_t* out,
                        uint32_t* len_out, uint8_t* fork_out, uint8_t* version_out, uint8_t* status_out);
 int lcv_debug_set_encode_chunk(lcv_ctx* ctx, uint64_t rows);
+
+/* ---- SSZ wire messages decoded into a resident batch on the device (csrc/lcv_wire_dec.hpp): the ingress side of
+ * the wire, so that a relay goes bytes -> resident batch -> lcv_validate_resident* -> lcv_batch_encode of the accepted
+ * rows and the host never holds a row.  Message i = buf[offsets[i] .. + lengths[i]]; kind and fork codes as for
+ * lcv_ssz_decode_updates below; forks == NULL: `fork` for every message; else one code per message and `fork` is
+ * ignored.
+ * Contract: *out is a resident batch in lcv_batch_upload's layout, taken by every resident entry and freed by
+ * lcv_batch_free.  Its rows and status_out (0 ok, 1 malformed) are exactly what lcv_ssz_decode_updates (forks == NULL)
+ * or lcv_ssz_decode_updates_mixed produce for the same messages: the same strict rules in the same order; status 1
+ * and an all-zero row for a malformed message or a fork code outside 0..2; finality and optimistic messages become
+ * the update the reference builds from them; Altair-format messages become their Capella upgrade.
+ * Pool order: the pool holds the distinct next_sync_committee values by content in order of first occurrence, and
+ * SyncCommittee() (all zero; also the committee of a malformed row and of kinds 1 and 2) takes a row at its first
+ * use.  This is the host decoder's order whenever its sampled key does not collide; where the numbering differs,
+ * pool[nsc_index] still agrees row for row.  Rows merge only on a full compare on the device; a 64-bit hash of the
+ * committee, computed by the decode kernel, only picks which rows are compared.
+ * Refused with LCV_EINVAL before any launch, lcv_last_error naming the first offender, *out = NULL and status_out
+ * untouched: a null argument; kind or fork out of range; n > LCV_DECODE_MAX_ROWS; offsets[i] + lengths[i] > buf_len
+ * (computed without wrapping); more than LCV_DECODE_MAX_BYTES of staged bytes (every length rounded up to 16, plus
+ * 16).  n == 0: LCV_OK and *out = NULL.
+ * The host copies the messages into a pinned buffer of the context (16-byte aligned each; messages that overlap or
+ * repeat in buf are staged twice) and one DMA moves it into a device scratch; both grow on demand and are kept.
+ * Synchronous, on work-space slot 0's stream: wait for pending slots first.
+ * No deduplication: a batch made this way has no host bytes to class and is validated without deduplication under
+ * lcv_set_dedup, as lcv_create_updates_resident's batches are.
+ * lcv_last_decode_timings: kernel time of the last decode, [0] the decode kernel's passes, [1] the committee
+ * compares and the pool gather (0 for kinds 1 and 2).  These launches are not stages of lcv_last_timings, which
+ * reads all zero after a decode.
+ * lcv_debug_decode_hash_bits (test hook): the committee hash truncated to `bits` bits for the grouping (default 64;
+ * 0 makes every committee collide, so that only the full compares separate them), as lcv_debug_dedup_hash_bits.
+ * Out of scope: an asynchronous wire-in entry on the eight slots, decoding inside the streaming validation,
+ * bootstraps, snappy framing and the Req/Resp result byte, merging pools across calls. */
+#define LCV_DECODE_MAX_ROWS 65536u
+#define LCV_DECODE_MAX_BYTES (2ull << 30)
+int lcv_batch_decode(lcv_ctx* ctx, const uint8_t* buf, uint64_t buf_len, const uint64_t* offsets,
+                     const uint64_t* lengths, uint64_t n, int kind, int fork,
+                     const uint8_t* forks /* NULL, or one code per message */, uint8_t* status_out /* n */,
+                     lcv_dbatch** out);
+int lcv_last_decode_timings(lcv_ctx* ctx, float ms_out[2]);
+int lcv_debug_decode_hash_bits(lcv_ctx* ctx, uint32_t bits);
 
 /* ---- SSZ wire decode (host only, no device work; csrc/lcv_wire.cpp).  Replaces the upstream SSZ
  * deserialisation of the reference's containers (sync-protocol.md:109-115 LightClientBootstrap,

@@ -15,6 +15,7 @@
 #include "lcv_fold.hpp"
 #include "lcv_producer.hpp"
 #include "lcv_wire_enc.hpp"
+#include "lcv_wire_dec.hpp"
 #include "lcv_dedup.hpp"
 #include "lcv_dedup_plan.hpp"
 #include "lcv_sop.hpp"
@@ -34,6 +35,9 @@ static const char* kStageNames[ST_COUNT] = {"nsc_htr", "pre_checks", "h2c_sswu",
                                             "store_rank", "store_fold", "produce_views", "produce_rows",
                                             "dedup_gather", "rlc_scale", "rlc_product", "rlc_spread", "rlc_retry",
                                             "wire_encode"};
+// lcv_batch_decode's launches: timed like the others, but past the public list (lcv_stage_name, lcv_last_timings);
+// lcv_last_decode_timings reports them
+enum { ST_WIRE_DECODE = ST_COUNT, ST_DECODE_POOL, ST_TOTAL };
 
 struct CommitteeBufs {
   uint8_t* raw = nullptr;
@@ -124,7 +128,7 @@ struct lcv_ctx {
   void* seg_mem[LCV_SLOTS] = {};
   size_t seg_cap[LCV_SLOTS] = {};
   FoldSegs segs;  // the grouping of the call in progress (staged before the call returns)
-  float stage_ms[ST_COUNT];
+  float stage_ms[ST_TOTAL];
   void* sop_mem = nullptr;   // device copies of the SOP pairing programs (tools/gen_sop.py)
   SopView sop_lines, sop_acc, sop_fexp, sop_h2c, sop_miller, sop_f12mul;
   // chunk pipeline of validate (lcv_set_pipeline; default 1 x 1 = serial stages): a batch is cut into `pipe_chunks` slices whose
@@ -201,6 +205,15 @@ struct lcv_ctx {
   void* enc_mem = nullptr;
   size_t enc_cap = 0;
   uint64_t enc_chunk = 0;
+  // lcv_batch_decode's staging: the pinned buffer the messages are copied into and the device scratch one DMA moves
+  // them to (followed there by the rows' records and the pool resolution's lists), both grown on demand and kept;
+  // dec_hash_bits: lcv_debug_decode_hash_bits; dec_table: the grouping's scratch
+  uint8_t* dec_pin = nullptr;
+  size_t dec_pin_cap = 0;
+  void* dec_mem = nullptr;
+  size_t dec_cap = 0;
+  uint32_t dec_hash_bits = 64;
+  DedupTable dec_table;
 };
 
 static uint32_t host_be32(const uint8_t* p) {
@@ -781,7 +794,7 @@ int lcv_init(int device, lcv_ctx** out) {
     delete ctx;
     return rc;
   }
-  for (int s = 0; s < ST_COUNT; ++s) ctx->stage_ms[s] = 0.f;
+  for (int s = 0; s < ST_TOTAL; ++s) ctx->stage_ms[s] = 0.f;
   {
     const char* names[4] = {"LCV_SOP_ITEMS_LINES", "LCV_SOP_ITEMS_ACC", "LCV_SOP_ITEMS_FEXP", "LCV_SOP_ITEMS_H2C"};
     for (int k = 0; k < 4; ++k)
@@ -811,6 +824,8 @@ void lcv_destroy(lcv_ctx* ctx) {
   }
   if (ctx->sop_mem) be_free(ctx, ctx->sop_mem);
   if (ctx->enc_mem) be_free(ctx, ctx->enc_mem);
+  if (ctx->dec_mem) be_free(ctx, ctx->dec_mem);
+  if (ctx->dec_pin) be_host_free(ctx, ctx->dec_pin);
   if (ctx->comm_buf) be_free(ctx, ctx->comm_buf);
   for (void* p : ctx->comm_retired) be_free(ctx, p);
   auto free_host_slot = [ctx](HostSlot& h) {
@@ -1089,6 +1104,13 @@ void lcv_batch_free(lcv_ctx* ctx, lcv_dbatch* b) {
   if (!ctx || !b) return;
   if (b->mem) be_free(ctx, b->mem);
   delete b;
+}
+
+int lcv_batch_shape(lcv_ctx* ctx, const lcv_dbatch* b, uint64_t* n_out, uint64_t* npool_out) {
+  if (!ctx || !b || !n_out || !npool_out) return fail(ctx, LCV_EINVAL, "lcv_batch_shape: null argument");
+  *n_out = b->n;
+  *npool_out = b->npool;
+  return LCV_OK;
 }
 
 // rows [base, base + n) of a batch: every per-row column it carries advanced by `base` elements, the pool as it is
@@ -1448,15 +1470,10 @@ int lcv_validate_resident_async(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_s
 // them to the slot's device copy on the slot's main stream — overlapping the kernels of the other slots'
 // batches — then the whole pipeline is enqueued, and the verdicts and reasons are copied back into pinned
 // host memory at the end of the slot's stream; lcv_slot_wait waits and hands them out.
-// the columns of c into dst (laid out as c), on up to 4 host threads for large batches
-static void stage_columns(uint8_t* dst, const BatchCols& c) {
-  struct Piece { uint8_t* d; const uint8_t* s; size_t b; };
-  std::vector<Piece> pieces;
-  const size_t kPiece = (size_t)1 << 20;
-  for (int k = 0; k < BATCH_COLS; ++k)
-    for (size_t o = 0; o < c.bytes[k]; o += kPiece)
-      pieces.push_back({dst + c.off[k] + o, (const uint8_t*)c.src[k] + o, c.bytes[k] - o < kPiece ? c.bytes[k] - o : kPiece});
-  const size_t nt = c.total >= ((size_t)8 << 20) ? 4 : 1;
+// host copies of a staging step, on up to 4 host threads above 8 MB in all
+struct CopyPiece { uint8_t* d; const uint8_t* s; size_t b; };
+static void copy_pieces(const std::vector<CopyPiece>& pieces, size_t total) {
+  const size_t nt = total >= ((size_t)8 << 20) ? 4 : 1;
   auto work = [&](size_t t) {
     for (size_t i = t; i < pieces.size(); i += nt) memcpy(pieces[i].d, pieces[i].s, pieces[i].b);
   };
@@ -1475,6 +1492,15 @@ static void stage_columns(uint8_t* dst, const BatchCols& c) {
   work(0);
   for (size_t t = started; t < nt; ++t) work(t);
   for (auto& x : th) x.join();
+}
+// the columns of c into dst (laid out as c)
+static void stage_columns(uint8_t* dst, const BatchCols& c) {
+  std::vector<CopyPiece> pieces;
+  const size_t kPiece = (size_t)1 << 20;
+  for (int k = 0; k < BATCH_COLS; ++k)
+    for (size_t o = 0; o < c.bytes[k]; o += kPiece)
+      pieces.push_back({dst + c.off[k] + o, (const uint8_t*)c.src[k] + o, c.bytes[k] - o < kPiece ? c.bytes[k] - o : kPiece});
+  copy_pieces(pieces, c.total);
 }
 
 // A one-chunk host batch into the HostSlot h: its columns (with a segmented fold's grouping `segs` and, under
@@ -2971,6 +2997,223 @@ int lcv_encode_updates(lcv_ctx* ctx, const lcv_update_batch* batch, int kind, in
   const int rc = lcv_batch_encode(ctx, db, nullptr, 0, kind, fork, out, len_out, fork_out, version_out, status_out);
   lcv_batch_free(ctx, db);
   return rc;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ SSZ wire messages into a resident batch (lcv_wire_dec.hpp)
+// The messages go through the context's pinned buffer — message i at a 16-byte aligned offset, 16 zero bytes behind
+// the last, then the (offset, length, fork) of every message — and ONE DMA into the context's device scratch, which
+// also holds the rows' records and the lists of the pool resolution.  Updates (kind 0) take two passes of F_wire_dec:
+// the plan and the committee hashes first, because the batch's layout depends on the number of pool rows; then, with
+// the batch allocated, the rows.  The other kinds have one pool row, SyncCommittee(), and take the second pass only.
+struct DecScratch { size_t meta, stage_bytes, rec, pairs, differ, pool_src, total; };
+static DecScratch dec_scratch(size_t msg_bytes, size_t n) {
+  auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  DecScratch s;
+  s.meta = pad(msg_bytes);
+  s.stage_bytes = s.meta + n * DEC_META_BYTES;
+  s.rec = pad(s.stage_bytes);
+  s.pairs = s.rec + pad(n * DEC_REC_BYTES);
+  s.differ = s.pairs + pad(n * DEC_PAIR_BYTES);
+  s.pool_src = s.differ + pad(4 * n);
+  s.total = s.pool_src + pad(8 * (n + 1));
+  return s;
+}
+
+// The distinct committees of the rows `cand` (ascending; valid updates whose committee is not all zero): rep[i] = the
+// first row whose committee equals row i's.  The rows are grouped by their (truncated) hash alone; then every row but
+// a group's first is compared in full with its tentative representative on the device (F_sc_confirm), the rows that
+// differ form the next candidate group under their lowest row, and the compare repeats: one launch per extra distinct
+// content under one hash value, none at 64 bits in practice.  coff[i]: the scratch offset of row i's committee
+static int dec_resolve_pool(lcv_ctx* ctx, uint8_t* d, const DecScratch& S, const std::vector<uint32_t>& cand,
+                            const uint8_t* rec, const std::vector<uint64_t>& coff, std::vector<uint32_t>& rep) {
+  const uint32_t none = 0xffffffffu;
+  auto hash_of = [&](uint32_t row) {
+    uint64_t h;
+    memcpy(&h, rec + (size_t)DEC_REC_BYTES * row + 8, 8);
+    return h;
+  };
+  dedup_group(
+      (uint32_t)cand.size(), ctx->dec_hash_bits, ctx->dec_table, [&](uint32_t j) { return hash_of(cand[j]); },
+      [](uint32_t, uint32_t) { return true; }, [&](uint32_t j) { rep[cand[j]] = cand[j]; },
+      [&](uint32_t a, uint32_t j) { rep[cand[j]] = cand[a]; });
+  std::vector<uint32_t> pending, next, differ, touched, newrep(rep.size(), none);
+  std::vector<uint64_t> pairs;
+  for (uint32_t r : cand)
+    if (rep[r] != r) pending.push_back(r);
+  while (!pending.empty()) {
+    const size_t m = pending.size();
+    pairs.resize(2 * m);
+    differ.resize(m);
+    for (size_t k = 0; k < m; ++k) {
+      pairs[2 * k] = coff[pending[k]];
+      pairs[2 * k + 1] = coff[rep[pending[k]]];
+    }
+    LCV_TRY(be_h2d(ctx, d + S.pairs, pairs.data(), DEC_PAIR_BYTES * m));
+    const ScConfirmArgs A = {d, d + S.pairs, (uint32_t*)(d + S.differ)};
+    LCV_TRY(stage(ctx, ST_DECODE_POOL, [&] { return be_launch_team(ctx, F_sc_confirm{A}, (uint32_t)m); }));
+    LCV_TRY(be_d2h(ctx, differ.data(), d + S.differ, 4 * m));
+    LCV_TRY(be_sync(ctx));
+    next.clear();
+    touched.clear();
+    for (size_t k = 0; k < m; ++k) {
+      if (!differ[k]) continue;
+      const uint32_t r = pending[k], old = rep[r];
+      if (newrep[old] == none) {  // the lowest differing row of its group: a representative of its own
+        newrep[old] = r;
+        touched.push_back(old);
+        rep[r] = r;
+      } else {
+        rep[r] = newrep[old];
+        next.push_back(r);
+      }
+    }
+    for (uint32_t old : touched) newrep[old] = none;
+    pending.swap(next);
+  }
+  return LCV_OK;
+}
+
+extern "C" {
+
+int lcv_debug_decode_hash_bits(lcv_ctx* ctx, uint32_t bits) {
+  if (!ctx || bits > 64) return fail(ctx, LCV_EINVAL, "lcv_debug_decode_hash_bits: bits <= 64");
+  ctx->dec_hash_bits = bits;
+  return LCV_OK;
+}
+
+int lcv_last_decode_timings(lcv_ctx* ctx, float ms_out[2]) {
+  if (!ctx || !ms_out) return fail(ctx, LCV_EINVAL, "lcv_last_decode_timings: null argument");
+  ms_out[0] = ctx->stage_ms[ST_WIRE_DECODE];
+  ms_out[1] = ctx->stage_ms[ST_DECODE_POOL];
+  return LCV_OK;
+}
+
+int lcv_batch_decode(lcv_ctx* ctx, const uint8_t* buf, uint64_t buf_len, const uint64_t* offsets, const uint64_t* lengths,
+                     uint64_t n, int kind, int fork, const uint8_t* forks, uint8_t* status_out, lcv_dbatch** out) {
+  const std::string who = "lcv_batch_decode";
+  if (out) *out = nullptr;
+  if (!ctx || !buf || !offsets || !lengths || !status_out || !out) return fail(ctx, LCV_EINVAL, who + ": null argument");
+  if (kind < 0 || kind > 2) return fail(ctx, LCV_EINVAL, who + ": kind is 0 (update), 1 (finality) or 2 (optimistic)");
+  if (!forks && (fork < 0 || fork > 2)) return fail(ctx, LCV_EINVAL, who + ": fork is 0 (Deneb), 1 (Capella) or 2 (Altair)");
+  if (n > LCV_DECODE_MAX_ROWS)
+    return fail(ctx, LCV_EINVAL, who + ": n = " + std::to_string(n) + " above LCV_DECODE_MAX_ROWS");
+  uint64_t msg_bytes = 16;  // the zero padding behind the last message
+  for (uint64_t i = 0; i < n; ++i) {
+    if (lengths[i] > buf_len || offsets[i] > buf_len - lengths[i])
+      return fail(ctx, LCV_EINVAL, who + ": message " + std::to_string(i) + ": offsets + lengths = " + std::to_string(offsets[i]) +
+                                       " + " + std::to_string(lengths[i]) + " is past buf_len " + std::to_string(buf_len));
+    if (lengths[i] <= LCV_DECODE_MAX_BYTES) msg_bytes += (lengths[i] + 15) & ~(uint64_t)15;
+    if (lengths[i] > LCV_DECODE_MAX_BYTES || msg_bytes > LCV_DECODE_MAX_BYTES)
+      return fail(ctx, LCV_EINVAL, who + ": staged bytes above LCV_DECODE_MAX_BYTES at message " + std::to_string(i));
+  }
+  if (n == 0) return LCV_OK;
+  const DecScratch S = dec_scratch((size_t)msg_bytes, (size_t)n);
+  std::vector<uint8_t> rec;
+  std::vector<uint32_t> nsc_index, rep, cand;
+  std::vector<uint64_t> coff, pool_src;
+  std::vector<CopyPiece> pieces;
+  try {
+    rec.resize(n * DEC_REC_BYTES);
+    nsc_index.assign(n, 0u);
+    pieces.reserve(n);
+  } catch (...) {  // an extern "C" entry point must not let an exception out
+    return fail(ctx, LCV_ENOMEM, who + ": out of host memory");
+  }
+  be_set_slot(ctx, 0);
+  LCV_TRY(host_alloc_grow(ctx, &ctx->dec_pin, &ctx->dec_pin_cap, S.stage_bytes));
+  LCV_TRY(dev_alloc_grow(ctx, &ctx->dec_mem, &ctx->dec_cap, S.total, S.total));
+  uint8_t* pin = ctx->dec_pin;
+  uint8_t* d = (uint8_t*)ctx->dec_mem;
+  {  // staging: the messages (host threads above 8 MB), the padding, the meta records
+    uint64_t o = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+      const uint32_t f = forks ? (uint32_t)forks[i] : (uint32_t)fork;
+      const uint32_t len = (uint32_t)lengths[i];  // (<= LCV_DECODE_MAX_BYTES < 2^32)
+      memcpy(pin + S.meta + DEC_META_BYTES * i, &o, 8);
+      memcpy(pin + S.meta + DEC_META_BYTES * i + 8, &len, 4);
+      memcpy(pin + S.meta + DEC_META_BYTES * i + 12, &f, 4);
+      if (lengths[i]) pieces.push_back({pin + o, buf + offsets[i], (size_t)lengths[i]});
+      o += (lengths[i] + 15) & ~(uint64_t)15;
+    }
+    memset(pin + o, 0, 16);
+    copy_pieces(pieces, (size_t)msg_bytes);
+  }
+  be_reset_timings(ctx);
+  LCV_TRY(be_h2d(ctx, d, pin, S.stage_bytes));
+  DecArgs A = {d, d + S.meta, d + S.rec, ProdOut{}, (uint32_t)kind, (uint32_t)DEC_PLAN};
+  uint64_t npool = 1;
+  try {
+    pool_src.assign(1, DEC_NO_COMMITTEE);
+    if (kind == 0) {
+      LCV_TRY(stage(ctx, ST_WIRE_DECODE, [&] { return be_launch_team(ctx, F_wire_dec{A}, (uint32_t)n); }));
+      LCV_TRY(be_d2h(ctx, rec.data(), d + S.rec, n * DEC_REC_BYTES));
+      LCV_TRY(be_sync(ctx));
+      const uint32_t none = 0xffffffffu;
+      rep.assign(n, none);
+      coff.assign(n, 0);
+      for (uint64_t i = 0; i < n; ++i) {
+        uint32_t st, zero;
+        memcpy(&st, rec.data() + DEC_REC_BYTES * i, 4);
+        memcpy(&zero, rec.data() + DEC_REC_BYTES * i + 4, 4);
+        if (st || zero) continue;
+        uint64_t o;
+        memcpy(&o, pin + S.meta + DEC_META_BYTES * i, 8);
+        coff[i] = o + ((forks ? forks[i] : fork) == ENC_ALTAIR ? (uint64_t)K_BEACON : 4u);
+        cand.push_back((uint32_t)i);
+      }
+      LCV_TRY(dec_resolve_pool(ctx, d, S, cand, rec.data(), coff, rep));
+      // pool rows in order of first occurrence; SyncCommittee() takes a row at its first use
+      std::vector<uint32_t> ix(n, none);
+      uint32_t zero_ix = none;
+      pool_src.clear();
+      for (uint64_t i = 0; i < n; ++i) {
+        if (rep[i] == none) {
+          if (zero_ix == none) { zero_ix = (uint32_t)pool_src.size(); pool_src.push_back(DEC_NO_COMMITTEE); }
+          nsc_index[i] = zero_ix;
+        } else {
+          if (rep[i] == i) { ix[i] = (uint32_t)pool_src.size(); pool_src.push_back(coff[i]); }
+          nsc_index[i] = ix[rep[i]];
+        }
+      }
+      npool = pool_src.size();
+    }
+  } catch (...) {
+    return fail(ctx, LCV_ENOMEM, who + ": out of host memory");
+  }
+  // the batch: lcv_batch_upload's layout
+  BatchCols c;
+  batch_layout(c, n, npool, false, 0);
+  lcv_dbatch* db = new (std::nothrow) lcv_dbatch();
+  if (!db) return LCV_ENOMEM;
+  int rc = be_alloc(ctx, &db->mem, c.total);
+  if (rc != LCV_OK) { delete db; return rc; }
+  uint8_t* m = (uint8_t*)db->mem;
+  bind_batch(db, m, c);
+  auto body = [&]() -> int {
+    LCV_TRY(be_h2d(ctx, m + c.off[COL_NSC_INDEX], nsc_index.data(), 4 * n));
+    A.O = prod_out(db->B);
+    A.phase = DEC_ROWS;
+    if (kind == 0) A.rec = nullptr;  // (the first pass left the records)
+    LCV_TRY(stage(ctx, ST_WIRE_DECODE, [&] { return be_launch_team(ctx, F_wire_dec{A}, (uint32_t)n); }));
+    if (kind == 0) {
+      LCV_TRY(be_h2d(ctx, d + S.pool_src, pool_src.data(), 8 * npool));
+      const ScGatherArgs G = {d, (const uint64_t*)(d + S.pool_src), m + c.off[COL_NSC_POOL]};
+      LCV_TRY(stage(ctx, ST_DECODE_POOL, [&] { return be_launch_team(ctx, F_sc_gather{G}, (uint32_t)npool); }));
+    } else {
+      LCV_TRY(be_memset(ctx, m + c.off[COL_NSC_POOL], 0, K_SC));
+      LCV_TRY(be_d2h(ctx, rec.data(), d + S.rec, n * DEC_REC_BYTES));
+    }
+    LCV_TRY(be_sync(ctx));
+    be_collect_timings(ctx);
+    return LCV_OK;
+  };
+  rc = body();
+  if (rc != LCV_OK) { be_free(ctx, db->mem); delete db; return rc; }
+  for (uint64_t i = 0; i < n; ++i) status_out[i] = rec[DEC_REC_BYTES * i] ? 1 : 0;
+  *out = db;
+  return LCV_OK;
 }
 
 }  // extern "C"

@@ -253,7 +253,7 @@ static void be_reset_timings(lcv_ctx* ctx) {
   ctx->be.marks.clear();
   ctx->be.used = 0;
   for (int k = 0; k < BE_STREAMS; ++k) ctx->be.open_stage[k] = -1;
-  for (int s = 0; s < ST_COUNT; ++s) ctx->stage_ms[s] = 0.f;
+  for (int s = 0; s < ST_TOTAL; ++s) ctx->stage_ms[s] = 0.f;
 }
 static void be_collect_timings(lcv_ctx* ctx) {
   for (auto& m : ctx->be.marks) {

@@ -136,7 +136,7 @@ static void be_stage_end(lcv_ctx* ctx, int stage) {
 }
 static void be_reset_timings(lcv_ctx* ctx) {
   for (int k = 0; k < 4; ++k) ctx->be.open_stage[k] = -1;
-  for (int s = 0; s < ST_COUNT; ++s) ctx->stage_ms[s] = 0.f;
+  for (int s = 0; s < ST_TOTAL; ++s) ctx->stage_ms[s] = 0.f;
   for (int s = 0; s < 32; ++s) for (int k = 0; k < 4; ++k) ctx->be.ops[s][k] = 0;
 }
 static void be_collect_timings(lcv_ctx*) {}

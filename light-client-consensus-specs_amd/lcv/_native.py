@@ -190,6 +190,11 @@ SIGNATURES = {
     "lcv_batch_encode": (C.c_int, [C.c_void_p, C.c_void_p, u32p, C.c_uint64, C.c_int, C.c_int, u8p, u32p, u8p, u8p, u8p]),
     "lcv_encode_updates": (C.c_int, [C.c_void_p, C.POINTER(UpdateBatch), C.c_int, C.c_int, u8p, u32p, u8p, u8p, u8p]),
     "lcv_debug_set_encode_chunk": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "lcv_batch_decode": (C.c_int, [C.c_void_p, u8p, C.c_uint64, u64p, u64p, C.c_uint64, C.c_int, C.c_int, u8p, u8p,
+                                   C.POINTER(C.c_void_p)]),
+    "lcv_last_decode_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "lcv_debug_decode_hash_bits": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "lcv_batch_shape": (C.c_int, [C.c_void_p, C.c_void_p, u64p, u64p]),
     "lcv_ssz_decode_updates": (C.c_int, [u8p, u64p, u64p, C.c_uint64, C.c_int, C.c_int, C.POINTER(UpdateBatch),
                                          u64p, u64p, u8p]),
     "lcv_ssz_decode_updates_mixed": (C.c_int, [u8p, u64p, u64p, C.c_uint64, C.c_int, u8p, C.POINTER(UpdateBatch),

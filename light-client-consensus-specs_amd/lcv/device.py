@@ -310,7 +310,8 @@ class Verifier:
         attested beacon header, signature_slot, sync bits, signature and signing committee are bytewise equal — one
         update relayed to many stores — share one run of the BLS half, and every row keeps its own pre-checks.
         Verdicts and reasons are those of the mode off.  Batches taken (validate*, upload) while the mode is on are
-        grouped; a ResidentBatch uploaded with it off is validated without deduplication.  LcvError (status -1)
+        grouped; a ResidentBatch uploaded with it off, or made on the device (create_updates_resident,
+        decode_resident: no host bytes to class), is validated without deduplication.  LcvError (status -1)
         together with a multi-stream pipeline (set_pipeline streams > 1), from whichever call comes second."""
         self._check(self.lib.lcv_set_dedup(self.ctx, 1 if on else 0), "lcv_set_dedup")
         self.dedup = bool(on)
@@ -568,6 +569,44 @@ class Verifier:
     def debug_set_encode_chunk(self, rows: int) -> None:
         """Test hook (lcv_debug_set_encode_chunk): rows per encode chunk; 0: as many as fit the scratch bound."""
         self._check(self.lib.lcv_debug_set_encode_chunk(self.ctx, int(rows)), "lcv_debug_set_encode_chunk")
+
+    def decode_resident(self, messages, kind="update", fork="deneb") -> Tuple[ResidentBatch, np.ndarray]:
+        """SSZ wire messages decoded on the device into a resident batch (lcv_batch_decode) -> (ResidentBatch, ok).
+        `messages`, `kind` and `fork` (one name, or one per message) as lcv.wire.decode_updates takes them; the rows
+        and ok are lcv.wire.decode_updates_status's (a malformed message: an all-zero row, ok False).  The relay
+        path: decode_resident -> validate_resident -> encode_resident(rows=accepted), no row on the host."""
+        from . import wire
+        if kind not in wire.KINDS:
+            raise ValueError(f"kind must be one of {list(wire.KINDS)}")
+        buf, offs, lens = wire._flatten(messages)
+        n = int(offs.size)
+        fcode, forks = wire._fork_codes(fork, n)
+        status = np.zeros(max(n, 1), np.uint8)
+        src = buf if buf.size else np.zeros(1, np.uint8)
+        o = offs if n else np.zeros(1, np.uint64)
+        ln = lens if n else np.zeros(1, np.uint64)
+        h = C.c_void_p()
+        self._check(self.lib.lcv_batch_decode(self.ctx, ptr(src), int(buf.size), ptr(o, C.c_uint64), ptr(ln, C.c_uint64),
+                                              n, wire.KINDS[kind], 0 if fcode is None else fcode,
+                                              None if forks is None or not n else ptr(forks), ptr(status), C.byref(h)),
+                    "lcv_batch_decode")
+        if not h:
+            return ResidentBatch(self, None, 0, npool=1), status[:0] == 0
+        rows, npool = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.lcv_batch_shape(self.ctx, h, C.byref(rows), C.byref(npool)), "lcv_batch_shape")
+        return ResidentBatch(self, h, n, npool=int(npool.value)), status[:n] == 0
+
+    def last_decode_timings(self) -> Tuple[float, float]:
+        """Kernel milliseconds of the last decode_resident (lcv_last_decode_timings): (the decode kernel's passes,
+        the committee compares and the pool gather; 0.0 for finality and optimistic messages)."""
+        ms = (C.c_float * 2)()
+        self._check(self.lib.lcv_last_decode_timings(self.ctx, ms), "lcv_last_decode_timings")
+        return float(ms[0]), float(ms[1])
+
+    def debug_decode_hash_bits(self, bits: int) -> None:
+        """Test hook (lcv_debug_decode_hash_bits): the committee hash of decode_resident's pool grouping truncated to
+        `bits` bits (64: whole; 0: every committee collides, so only the full compares separate them)."""
+        self._check(self.lib.lcv_debug_decode_hash_bits(self.ctx, int(bits)), "lcv_debug_decode_hash_bits")
 
     def create_bootstraps(self, views: PackedViews, state_idx, block_idx, reason: Optional[np.ndarray] = None):
         """create_light_client_bootstrap per (state_idx[i], block_idx[i]) (lcv_create_bootstraps) -> (beacon (n, 112),

@@ -13,6 +13,8 @@ device verifier consumes; no per-update Python objects are built.
         response's chunks each carry a ForkDigest context: p2p-interface.md:189-200; `fork_of_digest_version`
         maps a chunk's fork version to its name under the network configuration)
     decode_updates_status(messages, kind, fork)             -> (PackedUpdates, ok: np.ndarray[bool])
+    decode_updates_device(messages, kind, fork, verifier, strict=True) -> (ResidentBatch, ok)  (the same rows
+        decoded on the device into a resident batch, lcv_batch_decode: what a relay validates and serves on)
     decode_bootstrap(data, fork="deneb")                    -> Bootstrap (header rows, committee, branch)
     encode_updates(batch, kind="update", fork="deneb")      -> [bytes]  (serving side; inverse of decode)
     encode_updates_device(batch_or_resident, kind, fork="auto", verifier) -> [bytes]  (the same bytes from the
@@ -151,6 +153,20 @@ def decode_updates(messages: Messages, kind: str = "update", fork="deneb",
         bad = np.flatnonzero(~ok)
         raise ValueError(f"malformed SSZ {kind} message(s) at index {bad[:8].tolist()}")
     return batch
+
+
+def decode_updates_device(messages: Messages, kind: str = "update", fork="deneb", verifier=None, strict: bool = True):
+    """decode_updates on the device (lcv_batch_decode: the rows are written where validation reads them, the host
+    never holds one) -> (ResidentBatch, ok).  `messages` and `fork` as decode_updates takes them.  With `strict`,
+    ValueError naming the first malformed indices, as decode_updates raises; the batch is freed first."""
+    from .device import Verifier
+    v = verifier if verifier is not None else Verifier(0)
+    rb, ok = v.decode_resident(messages, kind, fork)
+    if strict and not ok.all():
+        rb.free()
+        bad = np.flatnonzero(~ok)
+        raise ValueError(f"malformed SSZ {kind} message(s) at index {bad[:8].tolist()}")
+    return rb, ok
 
 
 @dataclass
