@@ -6,6 +6,9 @@
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
+#include <new>
+#include <stdexcept>
 #include <string>
 #include <thread>
 #include <vector>
@@ -39,19 +42,89 @@ static const char* kStageNames[ST_COUNT] = {"nsc_htr", "pre_checks", "h2c_sswu",
 // lcv_last_decode_timings reports them
 enum { ST_WIRE_DECODE = ST_COUNT, ST_DECODE_POOL, ST_TOTAL };
 
+#define LCV_TRY(x)                    \
+  do {                                \
+    int _rc = (x);                    \
+    if (_rc != LCV_OK) return _rc;    \
+  } while (0)
+
+// ---- memory.  Every allocation of the driver has one owner, and a new feature allocates through these types only:
+//   DevBuf / PinBuf  a device / pinned host buffer that lives in the context (or in a resident batch): pointer and
+//                    capacity, grown on demand under the caller's policy, released by lcv_destroy (lcv_batch_free).
+//                    No destructor: a release goes through the backend, which lcv_destroy tears down before the
+//                    context's members go
+//   Scratch          device memory of one call, freed when the call returns, on every path
+//   Layout           consecutive 256-byte aligned offsets into one allocation
+// be_free waits for every stream, so where a buffer is regrown or a scratch freed is part of a call's schedule
+template <bool PINNED> struct Buf {
+  uint8_t* p = nullptr;
+  size_t cap = 0;  // in the caller's unit
+  void release(lcv_ctx* ctx) {
+    if (p) PINNED ? be_host_free(ctx, p) : be_free(ctx, p);
+    p = nullptr;
+    cap = 0;
+  }
+  // a new buffer of `bytes` for a capacity of new_cap, in place of the old one; empty after a failure
+  int renew(lcv_ctx* ctx, size_t new_cap, size_t bytes, bool zero = false) {
+    release(ctx);
+    void* q = nullptr;
+    LCV_TRY(PINNED ? be_host_alloc(ctx, &q, bytes) : be_alloc(ctx, &q, bytes));
+    p = (uint8_t*)q;
+    cap = new_cap;
+    const int rc = zero ? be_memset(ctx, p, 0, bytes) : LCV_OK;
+    if (rc != LCV_OK) release(ctx);
+    return rc;
+  }
+  // only grows: the growth policy (new_cap) is the caller's
+  int grow(lcv_ctx* ctx, size_t new_cap, size_t bytes) { return (p && new_cap <= cap) ? LCV_OK : renew(ctx, new_cap, bytes); }
+  int grow(lcv_ctx* ctx, size_t bytes) { return grow(ctx, bytes, bytes); }
+};
+typedef Buf<false> DevBuf;
+typedef Buf<true> PinBuf;
+
+struct Scratch {
+  lcv_ctx* ctx;
+  uint8_t* p = nullptr;
+  explicit Scratch(lcv_ctx* c) : ctx(c) {}
+  Scratch(const Scratch&) = delete;
+  Scratch& operator=(const Scratch&) = delete;
+  ~Scratch() { release(); }
+  int alloc(size_t bytes) {
+    void* q = nullptr;
+    LCV_TRY(be_alloc(ctx, &q, bytes));
+    p = (uint8_t*)q;
+    return LCV_OK;
+  }
+  void release() {  // (ahead of the return, where the call still has backend work to do behind the free)
+    if (p) be_free(ctx, p);
+    p = nullptr;
+  }
+};
+
+struct Layout {
+  size_t end = 0;
+  size_t take(size_t bytes) {
+    const size_t off = end;
+    end += (bytes + 255) & ~(size_t)255;
+    return off;
+  }
+  size_t total() const { return end; }
+};
+
 struct CommitteeBufs {
-  uint8_t* raw = nullptr;
-  uint32_t* pts = nullptr;
-  uint32_t* sum_all = nullptr;
-  uint32_t* badmask = nullptr;
-  uint8_t* key_status = nullptr;
+  DevBuf raw, pts, sum_all, badmask, key_status;
   size_t ncomm_cap = 0;
   uint32_t ncomm = 0;
   uint32_t raw_stride = 0;
+  void release(lcv_ctx* ctx) {
+    for (DevBuf* b : {&raw, &pts, &sum_all, &badmask, &key_status}) b->release(ctx);
+    ncomm_cap = 0;
+    ncomm = raw_stride = 0;
+  }
 };
 
 struct lcv_dbatch {
-  void* mem = nullptr;
+  DevBuf mem;
   BatchDev B;
   uint64_t n = 0, npool = 0;
   // a batch that carries its store_index column (B.store_index) is validated against the store table; the
@@ -74,19 +147,21 @@ struct lcv_dbatch {
 // packed batch (so the host->device copy is a DMA that overlaps the other slots' kernels), the batch's
 // device copy, and pinned verdict / reason bytes copied back at the end of the slot's pipeline
 struct HostSlot {
-  uint8_t* pinned = nullptr;
-  size_t pinned_cap = 0;
-  void* dev = nullptr;
-  size_t dev_cap = 0;
-  uint8_t* out = nullptr;  // pinned: [cap] verdicts, then [cap] reasons
-  size_t out_cap = 0;
+  PinBuf pinned;
+  DevBuf dev;
+  PinBuf out;  // [cap] verdicts, then [cap] reasons
   uint64_t out_n = 0;
   bool staged = false;     // out holds the slot's last batch (lcv_slot_wait reads it)
   bool folded = false;     // ... and, after its 2 out_n bytes, that batch's fold result (lcv_slot_wait_fold)
   // ... or (lcv_validate_stores_async_fold) one result (FOLD_RESULT_BYTES) per store present, for the store rows seg_store
   bool seg_folded = false;
   std::vector<uint32_t> seg_store;
-  lcv_dbatch db;
+  lcv_dbatch db;  // (a view of `dev`: owns nothing)
+  void release(lcv_ctx* ctx) {
+    dev.release(ctx);
+    pinned.release(ctx);
+    out.release(ctx);
+  }
 };
 
 // the rows of a store-table batch grouped by store (fold_segments): the distinct stores present, ascending; each
@@ -98,6 +173,39 @@ struct FoldSegs {
   uint32_t nseg = 0;
 };
 
+// What a work-space slot owns, beside its streams and events (Backend).  The work space and the scratch buffers are
+// allocated by the slot's first call that needs them and only grow (ensure_work, ensure_fold_seg, ensure_dedup,
+// ensure_rlc: each states its own policy)
+struct Slot {
+  DevBuf work;  // (capacity: items; pool_cap: the committee-pool items beside it)
+  size_t pool_cap = 0;
+  Work W;
+  // the per-store results of a segmented fold (lcv_validate_stores_fold), FOLD_RESULT_BYTES per store present
+  DevBuf seg;
+  // lcv_set_dedup: the items' compact columns and a resident chunk's grouping, the pinned buffer that grouping is
+  // copied from, and the rows / items of the slot's last batch (lcv_last_dedup)
+  DevBuf dedup;
+  DedupDev D = {};
+  PinBuf plan_pin;
+  uint64_t dd_rows = 0, dd_items = 0;
+  // lcv_set_rlc: the scratch, laid out for the slot's work-space capacity, and, for lcv_last_rlc, the groups of the
+  // slot's last batch and the slots whose scratch counted that batch's retried rows (bit s: slot s)
+  DevBuf rlc;
+  RlcDev R = {};
+  uint64_t rl_groups = 0;
+  uint32_t rl_used = 0;
+  HostSlot host;  // lcv_validate_async and its kin
+  void release(lcv_ctx* ctx) {  // (all but `host`, which lcv_destroy releases after the context's own buffers)
+    for (DevBuf* b : {&work, &seg, &dedup, &rlc}) b->release(ctx);
+    plan_pin.release(ctx);
+  }
+};
+
+// The context.  Its memory: every buffer is a DevBuf or PinBuf member, here or in a Slot (what a work-space slot
+// owns, the HostSlot of the host-input entries among it); a call's temporary device memory is a Scratch, offsets into
+// one allocation come from a Layout, a resident batch from batch_new, and an entry that may allocate host memory runs
+// its body in `guarded`.  A new feature allocates through these only; lcv_destroy releases every owner by name or by
+// loop, so a new member is released there or leaks in tools/driver_alloc_check.cpp
 struct lcv_ctx {
   Backend be;
   std::string err;
@@ -112,24 +220,16 @@ struct lcv_ctx {
   // columns (finalized slot, current row, next row or STORE_NEXT_UNKNOWN), one device allocation
   bool table_set = false;
   CommitteeBufs table;
-  void* table_mem = nullptr;
-  size_t table_store_cap = 0;
+  DevBuf table_mem;  // (capacity: store rows)
   StoreDev table_dev = {nullptr, nullptr, nullptr, 0};
   std::vector<uint8_t> adhoc_src;  // the bytes `adhoc` was built from (reused while calls repeat them)
-  // work space
-  // work spaces: slot 0 serves every synchronous call; slots 0 and 1 alternate under
+  // work-space slots: slot 0 serves every synchronous call; slots 0 and 1 alternate under
   // lcv_validate_resident_async (up to LCV_SLOTS batches in flight, each on its own pair of streams)
-  void* work_mem[LCV_SLOTS] = {};
-  size_t work_cap[LCV_SLOTS] = {}, work_pool_cap[LCV_SLOTS] = {};
-  Work Wslot[LCV_SLOTS];
+  Slot slot[LCV_SLOTS];
   Work W;  // the active slot's work space
-  // the per-store results of a segmented fold (lcv_validate_stores_fold), FOLD_RESULT_BYTES per store present: an
-  // allocation of its own per work-space slot, made by the slot's first segmented fold and grown on demand
-  void* seg_mem[LCV_SLOTS] = {};
-  size_t seg_cap[LCV_SLOTS] = {};
   FoldSegs segs;  // the grouping of the call in progress (staged before the call returns)
   float stage_ms[ST_TOTAL];
-  void* sop_mem = nullptr;   // device copies of the SOP pairing programs (tools/gen_sop.py)
+  DevBuf sop_mem;  // device copies of the SOP pairing programs (tools/gen_sop.py)
   SopView sop_lines, sop_acc, sop_fexp, sop_h2c, sop_miller, sop_f12mul;
   // chunk pipeline of validate (lcv_set_pipeline; default 1 x 1 = serial stages): a batch is cut into `pipe_chunks` slices whose
   // stage chains run on `pipe_streams` streams, so the stages of different slices overlap
@@ -142,12 +242,10 @@ struct lcv_ctx {
   bool comm_failed = false;
   double comm_timeout_s = 60.0;
   int comm_nranks = 1, comm_rank = 0;
-  uint8_t* comm_buf = nullptr;  // device: [per_rank] send slice, then [nranks * per_rank] gathered
-  size_t comm_buf_cap = 0;
-  // communication buffers outgrown while a collective may be pending: freed only by lcv_destroy, because a
+  DevBuf comm_buf;  // [per_rank] send slice, then [nranks * per_rank] gathered
+  // communication buffers outgrown while a collective may be pending: released only by lcv_destroy, because a
   // free waits for every stream without bound (be_free) and a collective call must never block unbounded
-  std::vector<void*> comm_retired;
-  HostSlot hslot[LCV_SLOTS];
+  std::vector<DevBuf> comm_retired;
   HostSlot hsync;  // lcv_validate_updates' staging (one pinned buffer, one device copy, reused)
   // no per-stage timing marks (HIP event pairs) while set: the asynchronous entries never collect them,
   // so a serving loop would otherwise grow the event pool without bound
@@ -169,49 +267,31 @@ struct lcv_ctx {
   // knobs, set from the environment at lcv_init (LCV_SOP_ITEMS_LINES / _ACC / _FEXP / _H2C): fewer items
   // per wave = more waves per SIMD for the same batch (DESIGN §7)
   uint32_t sop_items[4] = {0, 0, 0, 0};
-  // deduplicated BLS half (lcv_set_dedup, off by default; include/lcv.h "Deduplicated signatures"): per work-space
-  // slot the items' compact columns and a resident chunk's grouping (ensure_dedup: an allocation of its own, made by
-  // the slot's first deduplicated call), the pinned buffer that grouping is copied from, and the rows / items of
-  // the slot's last batch (lcv_last_dedup).  dd_*: the host's scratch of the call in progress.  tab_*: the store
-  // table's columns as the device holds them, for the host's committee choice (dedup_comm_rows)
+  // deduplicated BLS half (lcv_set_dedup, off by default; include/lcv.h "Deduplicated signatures"; per slot: Slot).
+  // dd_*: the host's scratch of the call in progress.  tab_*: the store table's columns as the device holds them, for
+  // the host's committee choice (dedup_comm_rows)
   bool dedup = false;
   uint32_t dedup_hash_bits = 64;  // lcv_debug_dedup_hash_bits
-  void* dedup_mem[LCV_SLOTS] = {};
-  size_t dedup_cap[LCV_SLOTS] = {};
-  DedupDev Dslot[LCV_SLOTS] = {};
-  uint8_t* plan_pin[LCV_SLOTS] = {};
-  size_t plan_pin_cap[LCV_SLOTS] = {};
-  uint64_t dd_rows[LCV_SLOTS] = {}, dd_items[LCV_SLOTS] = {};
   DedupTable dd_table;
   std::vector<uint32_t> dd_cls, dd_comm, dd_rep, dd_urow;
   std::vector<uint64_t> tab_fin;
   std::vector<uint32_t> tab_cur, tab_next;
   // randomised batch verification (lcv_set_rlc, off by default; include/lcv.h "Batch verification"): the group size
   // (0: off) and the seed; the batch counter the next chunk's coefficients are derived from (never reused: +1 per
-  // chunk that runs the mode); per work-space slot the scratch (ensure_rlc: an allocation of its own, made by the
-  // slot's first call with the mode on, laid out for the slot's work-space capacity) and, for lcv_last_rlc, the groups
-  // of the slot's last batch and the slots whose scratch counted that batch's retried rows (bit s: slot s)
+  // chunk that runs the mode); per slot: Slot
   uint32_t rlc_group = 0;
   bool rlc_seeded = false;
   uint32_t rlc_seed[8] = {};
   uint64_t rlc_counter = 0;
-  void* rlc_mem[LCV_SLOTS] = {};
-  size_t rlc_cap[LCV_SLOTS] = {};
-  RlcDev Rslot[LCV_SLOTS] = {};
-  uint64_t rl_groups[LCV_SLOTS] = {};
-  uint32_t rl_used[LCV_SLOTS] = {};
   // lcv_batch_encode's scratch (one chunk of message areas, their result records, the chunk's row list): grown on
   // demand up to LCV_ENCODE_SCRATCH_BYTES of areas, kept for the next call; enc_chunk: lcv_debug_set_encode_chunk
-  void* enc_mem = nullptr;
-  size_t enc_cap = 0;
+  DevBuf enc_mem;
   uint64_t enc_chunk = 0;
   // lcv_batch_decode's staging: the pinned buffer the messages are copied into and the device scratch one DMA moves
   // them to (followed there by the rows' records and the pool resolution's lists), both grown on demand and kept;
   // dec_hash_bits: lcv_debug_decode_hash_bits; dec_table: the grouping's scratch
-  uint8_t* dec_pin = nullptr;
-  size_t dec_pin_cap = 0;
-  void* dec_mem = nullptr;
-  size_t dec_cap = 0;
+  PinBuf dec_pin;
+  DevBuf dec_mem;
   uint32_t dec_hash_bits = 64;
   DedupTable dec_table;
 };
@@ -225,12 +305,6 @@ static int fail(lcv_ctx* ctx, int code, const std::string& msg) {
   return code;
 }
 
-#define LCV_TRY(x)                    \
-  do {                                \
-    int _rc = (x);                    \
-    if (_rc != LCV_OK) return _rc;    \
-  } while (0)
-
 static const size_t kChunk = 65536;  // the largest chunk of validate, and of every entry that takes one chunk per call
 
 // A stage: one mark around its launches (marks never nest, see ST_*).  A launch that fails returns its code with
@@ -243,27 +317,26 @@ template <class L> static int stage(lcv_ctx* ctx, int st, L&& launch) {
   return LCV_OK;
 }
 
-// buffers that only grow.  Pinned host memory: at least `bytes`.  Device memory: `bytes` for a capacity of
-// `new_cap` in the caller's unit — the growth policy is the caller's (be_free waits for the streams)
-static int host_alloc_grow(lcv_ctx* ctx, uint8_t** p, size_t* cap, size_t bytes) {
-  if (bytes <= *cap && *p) return LCV_OK;
-  if (*p) be_host_free(ctx, *p);
-  *p = nullptr;
-  *cap = 0;
-  void* q = nullptr;
-  LCV_TRY(be_host_alloc(ctx, &q, bytes));
-  *p = (uint8_t*)q;
-  *cap = bytes;
-  return LCV_OK;
+// The boundary: the body of an extern "C" entry that may allocate host memory (std::vector, std::string) runs in here,
+// so that no exception leaves the library; slot 0 is the active one again after one
+static int fail_nothrow(lcv_ctx* ctx, int code, const char* who, const char* what) noexcept {
+  try {
+    if (ctx) be_set_slot(ctx, 0);
+    return fail(ctx, code, std::string(who) + ": " + what);
+  } catch (...) {
+    return code;
+  }
 }
-static int dev_alloc_grow(lcv_ctx* ctx, void** p, size_t* cap, size_t new_cap, size_t bytes) {
-  if (new_cap <= *cap && *p) return LCV_OK;
-  if (*p) be_free(ctx, *p);
-  *p = nullptr;
-  *cap = 0;
-  LCV_TRY(be_alloc(ctx, p, bytes));
-  *cap = new_cap;
-  return LCV_OK;
+template <class Body> static int guarded(lcv_ctx* ctx, const char* who, Body&& body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc&) {
+    return fail_nothrow(ctx, LCV_ENOMEM, who, "out of host memory");
+  } catch (const std::exception& e) {
+    return fail_nothrow(ctx, LCV_EINVAL, who, e.what());
+  } catch (...) {
+    return fail_nothrow(ctx, LCV_EINVAL, who, "unknown exception");
+  }
 }
 
 #include "lcv_functors_sop.hpp"
@@ -381,40 +454,29 @@ static size_t field_items(const Field& f, size_t cap, size_t pool_cap) {
 // the arrays of `o` (null: the sizes only), each at the next 256-byte aligned offset of m and as long as its last
 // item's last element reaches; returns the bytes taken
 template <size_t N> static size_t fields_bind(void* o, const Field (&tab)[N], uint8_t* m, size_t cap, size_t pool_cap) {
-  size_t off = 0;
+  Layout l;
   for (const Field& f : tab) {
+    const size_t off = l.take(f.esize * (field_index(f, cap, pool_cap, field_items(f, cap, pool_cap) - 1, f.rows - 1) + 1));
     if (o) slot_set(o, f.slot, m + off);
-    const size_t bytes = f.esize * (field_index(f, cap, pool_cap, field_items(f, cap, pool_cap) - 1, f.rows - 1) + 1);
-    off += (bytes + 255) & ~(size_t)255;
   }
-  return off;
+  return l.total();
 }
 
-// the work space of `slot` (allocated or grown on demand; be_free waits for the streams) becomes ctx->W
+// the work space of `slot` (allocated or grown on demand; be_free waits for the streams) becomes ctx->W.  Neither
+// capacity ever shrinks; at least 64 items and a pool of 1; zero-filled
 static int ensure_work(lcv_ctx* ctx, size_t cap, size_t pool_cap, int slot = 0) {
-  if (cap <= ctx->work_cap[slot] && pool_cap <= ctx->work_pool_cap[slot] && ctx->work_mem[slot]) {
-    ctx->W = ctx->Wslot[slot];
-    return LCV_OK;
+  Slot& s = ctx->slot[slot];
+  if (!s.work.p || cap > s.work.cap || pool_cap > s.pool_cap) {
+    cap = std::max({cap, s.work.cap, (size_t)64});
+    pool_cap = std::max({pool_cap, s.pool_cap, (size_t)1});
+    LCV_TRY(s.work.renew(ctx, cap, fields_bind(nullptr, kWorkFields, nullptr, cap, pool_cap), true));
+    s.pool_cap = pool_cap;
+    s.W = Work{};
+    s.W.cap = (uint32_t)cap;
+    s.W.pool_cap = (uint32_t)pool_cap;
+    fields_bind(&s.W, kWorkFields, s.work.p, cap, pool_cap);
   }
-  if (cap < ctx->work_cap[slot]) cap = ctx->work_cap[slot];
-  if (pool_cap < ctx->work_pool_cap[slot]) pool_cap = ctx->work_pool_cap[slot];
-  if (cap < 64) cap = 64;
-  if (pool_cap < 1) pool_cap = 1;
-  if (ctx->work_mem[slot]) be_free(ctx, ctx->work_mem[slot]);
-  ctx->work_mem[slot] = nullptr;
-  const size_t total = fields_bind(nullptr, kWorkFields, nullptr, cap, pool_cap);
-  void* mem = nullptr;
-  LCV_TRY(be_alloc(ctx, &mem, total));
-  LCV_TRY(be_memset(ctx, mem, 0, total));
-  Work& W = ctx->Wslot[slot];
-  W = Work{};
-  W.cap = (uint32_t)cap;
-  W.pool_cap = (uint32_t)pool_cap;
-  fields_bind(&W, kWorkFields, (uint8_t*)mem, cap, pool_cap);
-  ctx->work_mem[slot] = mem;
-  ctx->work_cap[slot] = cap;
-  ctx->work_pool_cap[slot] = pool_cap;
-  ctx->W = W;
+  ctx->W = s.W;
   return LCV_OK;
 }
 
@@ -422,26 +484,22 @@ static int ensure_work(lcv_ctx* ctx, size_t cap, size_t pool_cap, int slot = 0) 
 // compact batch columns and the compact committee ids) and 8 per row (a resident chunk's rep / urow), as large as the
 // slot's work space at least; allocated by the slot's first deduplicated call (be_free waits for the streams)
 static int ensure_dedup(lcv_ctx* ctx, size_t cap, int slot) {
-  if (cap < ctx->work_cap[slot]) cap = ctx->work_cap[slot];
-  if (cap <= ctx->dedup_cap[slot] && ctx->dedup_mem[slot]) return LCV_OK;
-  LCV_TRY(dev_alloc_grow(ctx, &ctx->dedup_mem[slot], &ctx->dedup_cap[slot], cap, fields_bind(nullptr, kDedupFields, nullptr, cap, 0)));
-  fields_bind(&ctx->Dslot[slot], kDedupFields, (uint8_t*)ctx->dedup_mem[slot], cap, 0);
+  Slot& s = ctx->slot[slot];
+  cap = std::max(cap, s.work.cap);
+  if (s.dedup.p && cap <= s.dedup.cap) return LCV_OK;
+  LCV_TRY(s.dedup.renew(ctx, cap, fields_bind(nullptr, kDedupFields, nullptr, cap, 0)));
+  fields_bind(&s.D, kDedupFields, s.dedup.p, cap, 0);
   return LCV_OK;
 }
 // the batch-verification scratch of `slot` (lcv_set_rlc), laid out for the slot's work-space capacity of this moment
-// (pk_s stands in for W.pk, with W's stride), so it follows the work space when that grows; allocated by the slot's
-// first call with the mode on (be_free waits for the streams)
+// (pk_s stands in for W.pk, with W's stride), so it follows the work space when that grows; zero-filled; allocated by
+// the slot's first call with the mode on (be_free waits for the streams)
 static int ensure_rlc(lcv_ctx* ctx, int slot) {
-  const size_t cap = ctx->work_cap[slot];
-  if (cap == ctx->rlc_cap[slot] && ctx->rlc_mem[slot]) return LCV_OK;
-  if (ctx->rlc_mem[slot]) be_free(ctx, ctx->rlc_mem[slot]);
-  ctx->rlc_mem[slot] = nullptr;
-  ctx->rlc_cap[slot] = 0;
-  const size_t total = fields_bind(nullptr, kRlcFields, nullptr, cap, 0);
-  LCV_TRY(be_alloc(ctx, &ctx->rlc_mem[slot], total));
-  LCV_TRY(be_memset(ctx, ctx->rlc_mem[slot], 0, total));
-  fields_bind(&ctx->Rslot[slot], kRlcFields, (uint8_t*)ctx->rlc_mem[slot], cap, 0);
-  ctx->rlc_cap[slot] = cap;
+  Slot& s = ctx->slot[slot];
+  const size_t cap = s.work.cap;
+  if (s.rlc.p && cap == s.rlc.cap) return LCV_OK;
+  LCV_TRY(s.rlc.renew(ctx, cap, fields_bind(nullptr, kRlcFields, nullptr, cap, 0), true));
+  fields_bind(&s.R, kRlcFields, s.rlc.p, cap, 0);
   return LCV_OK;
 }
 // the BLS stages' view of a deduplicated chunk of m items: the compact columns where they read the batch's and W's
@@ -450,18 +508,19 @@ static void dedup_batch_view(const DedupDev& D, uint32_t m, BatchDev& Bu, Work& 
   Wu.comm_id = D.comm_id;
 }
 
+// the five arrays of ncomm committees, all or none: a failed allocation leaves `cb` empty
 static int ensure_committees(lcv_ctx* ctx, CommitteeBufs& cb, size_t ncomm, uint32_t raw_stride) {
-  if (ncomm > cb.ncomm_cap || raw_stride != cb.raw_stride || !cb.raw) {
-    if (cb.raw) { be_free(ctx, cb.raw); be_free(ctx, cb.pts); be_free(ctx, cb.sum_all); be_free(ctx, cb.badmask); be_free(ctx, cb.key_status); }
-    cb = CommitteeBufs();
-    void *a, *b, *c, *d, *e;
-    LCV_TRY(be_alloc(ctx, &a, ncomm * raw_stride));
-    LCV_TRY(be_alloc(ctx, &b, ncomm * 512 * 24 * 4));
-    LCV_TRY(be_alloc(ctx, &c, ncomm * 36 * 4));
-    LCV_TRY(be_alloc(ctx, &d, ncomm * 16 * 4));
-    LCV_TRY(be_alloc(ctx, &e, ncomm * 512));
-    cb.raw = (uint8_t*)a; cb.pts = (uint32_t*)b; cb.sum_all = (uint32_t*)c; cb.badmask = (uint32_t*)d;
-    cb.key_status = (uint8_t*)e;
+  if (ncomm > cb.ncomm_cap || raw_stride != cb.raw_stride || !cb.raw.p) {
+    cb.release(ctx);
+    int rc = cb.raw.renew(ctx, ncomm, ncomm * raw_stride);
+    if (rc == LCV_OK) rc = cb.pts.renew(ctx, ncomm, ncomm * 512 * 24 * 4);
+    if (rc == LCV_OK) rc = cb.sum_all.renew(ctx, ncomm, ncomm * 36 * 4);
+    if (rc == LCV_OK) rc = cb.badmask.renew(ctx, ncomm, ncomm * 16 * 4);
+    if (rc == LCV_OK) rc = cb.key_status.renew(ctx, ncomm, ncomm * 512);
+    if (rc != LCV_OK) {
+      cb.release(ctx);
+      return rc;
+    }
     cb.ncomm_cap = ncomm;
     cb.raw_stride = raw_stride;
   }
@@ -472,11 +531,11 @@ static int ensure_committees(lcv_ctx* ctx, CommitteeBufs& cb, size_t ncomm, uint
 static CommitteeDev committee_view(const CommitteeBufs& cb, const uint8_t* next_raw) {
   CommitteeDev C;
   C.next_raw = next_raw;
-  C.pts = cb.pts;
-  C.sum_all = cb.sum_all;
-  C.badmask = cb.badmask;
-  C.key_status = cb.key_status;
-  C.raw = cb.raw;
+  C.pts = (uint32_t*)cb.pts.p;
+  C.sum_all = (uint32_t*)cb.sum_all.p;
+  C.badmask = (uint32_t*)cb.badmask.p;
+  C.key_status = cb.key_status.p;
+  C.raw = cb.raw.p;
   C.raw_stride = cb.raw_stride;
   C.ncomm = cb.ncomm;
   return C;
@@ -498,10 +557,11 @@ static int upload_sop(lcv_ctx* ctx) {
   enum { NSRC = 18 };
   const Src src[NSRC] = {LCV_SOP_SRC(lines), LCV_SOP_SRC(miller_acc), LCV_SOP_SRC(fexp), LCV_SOP_SRC(h2c),
                          LCV_SOP_SRC(miller), LCV_SOP_SRC(f12mul)};
-  size_t off[NSRC], total = 0;
-  for (int k = 0; k < NSRC; ++k) { off[k] = total; total += (src[k].bytes + 255) & ~(size_t)255; }
-  LCV_TRY(be_alloc(ctx, &ctx->sop_mem, total));
-  uint8_t* m = (uint8_t*)ctx->sop_mem;
+  size_t off[NSRC];
+  Layout l;
+  for (int k = 0; k < NSRC; ++k) off[k] = l.take(src[k].bytes);
+  LCV_TRY(ctx->sop_mem.grow(ctx, l.total()));
+  uint8_t* m = ctx->sop_mem.p;
   for (int k = 0; k < NSRC; ++k) LCV_TRY(be_h2d(ctx, m + off[k], src[k].p, src[k].bytes));
   auto view = [&](int k, uint32_t rounds, uint32_t slots, uint32_t nconst) {
     return SopView{(const uint32_t*)(m + off[3 * k]), (const uint32_t*)(m + off[3 * k + 1]),
@@ -811,30 +871,16 @@ int lcv_init(int device, lcv_ctx** out) {
 
 void lcv_destroy(lcv_ctx* ctx) {
   if (!ctx) return;
-  if (ctx->table_mem) be_free(ctx, ctx->table_mem);
-  for (CommitteeBufs* cb : {&ctx->store, &ctx->adhoc, &ctx->table}) {
-    if (cb->raw) { be_free(ctx, cb->raw); be_free(ctx, cb->pts); be_free(ctx, cb->sum_all); be_free(ctx, cb->badmask); be_free(ctx, cb->key_status); }
-  }
-  for (int k = 0; k < LCV_SLOTS; ++k) {
-    if (ctx->work_mem[k]) be_free(ctx, ctx->work_mem[k]);
-    if (ctx->seg_mem[k]) be_free(ctx, ctx->seg_mem[k]);
-    if (ctx->dedup_mem[k]) be_free(ctx, ctx->dedup_mem[k]);
-    if (ctx->rlc_mem[k]) be_free(ctx, ctx->rlc_mem[k]);
-    if (ctx->plan_pin[k]) be_host_free(ctx, ctx->plan_pin[k]);
-  }
-  if (ctx->sop_mem) be_free(ctx, ctx->sop_mem);
-  if (ctx->enc_mem) be_free(ctx, ctx->enc_mem);
-  if (ctx->dec_mem) be_free(ctx, ctx->dec_mem);
-  if (ctx->dec_pin) be_host_free(ctx, ctx->dec_pin);
-  if (ctx->comm_buf) be_free(ctx, ctx->comm_buf);
-  for (void* p : ctx->comm_retired) be_free(ctx, p);
-  auto free_host_slot = [ctx](HostSlot& h) {
-    if (h.dev) be_free(ctx, h.dev);
-    if (h.pinned) be_host_free(ctx, h.pinned);
-    if (h.out) be_host_free(ctx, h.out);
-  };
-  for (HostSlot& h : ctx->hslot) free_host_slot(h);
-  free_host_slot(ctx->hsync);
+  // every owner, before the backend goes
+  ctx->table_mem.release(ctx);
+  for (CommitteeBufs* cb : {&ctx->store, &ctx->adhoc, &ctx->table}) cb->release(ctx);
+  for (Slot& s : ctx->slot) s.release(ctx);
+  for (DevBuf* b : {&ctx->sop_mem, &ctx->enc_mem, &ctx->dec_mem}) b->release(ctx);
+  ctx->dec_pin.release(ctx);
+  ctx->comm_buf.release(ctx);
+  for (DevBuf& b : ctx->comm_retired) b.release(ctx);
+  for (Slot& s : ctx->slot) s.host.release(ctx);
+  ctx->hsync.release(ctx);
   if (ctx->comm_ready) be_comm_destroy(ctx);
   be_destroy(ctx);
   delete ctx;
@@ -843,11 +889,11 @@ void lcv_destroy(lcv_ctx* ctx) {
 int lcv_set_store(lcv_ctx* ctx, uint64_t finalized_slot, const uint8_t* cur, const uint8_t* next, uint8_t* key_status_out) {
   if (!ctx || !cur || !next) return fail(ctx, LCV_EINVAL, "lcv_set_store: null argument");
   LCV_TRY(ensure_committees(ctx, ctx->store, 2, K_SC));
-  LCV_TRY(be_h2d(ctx, ctx->store.raw, cur, K_SC));
-  LCV_TRY(be_h2d(ctx, ctx->store.raw + K_SC, next, K_SC));
+  LCV_TRY(be_h2d(ctx, ctx->store.raw.p, cur, K_SC));
+  LCV_TRY(be_h2d(ctx, ctx->store.raw.p + K_SC, next, K_SC));
   be_reset_timings(ctx);
   LCV_TRY(build_committees(ctx, ctx->store));
-  if (key_status_out) LCV_TRY(be_d2h(ctx, key_status_out, ctx->store.key_status, 1024));
+  if (key_status_out) LCV_TRY(be_d2h(ctx, key_status_out, ctx->store.key_status.p, 1024));
   LCV_TRY(be_sync(ctx));
   uint32_t any = 0;
   for (int k = 0; k < K_SC; ++k) any |= next[k];
@@ -915,13 +961,13 @@ static bool col_per_row(const ColSpec& s) { return s.dev >= 0 && s.count != CN_P
 // nd BLS items (0: no grouping)
 static void batch_layout(BatchCols& c, size_t n, size_t np, bool stores, size_t ng, size_t nd = 0) {
   const size_t count[] = {n, np, stores ? n : 0, ng, ng ? ng + 1 : 0, ng ? n : 0, nd ? n : 0, nd};  // by ColCount
-  c.total = 0;
+  Layout l;
   for (int k = 0; k < BATCH_COLS; ++k) {
     c.src[k] = nullptr;
     c.bytes[k] = kBatchCols[k].width * count[kBatchCols[k].count];
-    c.off[k] = c.total;
-    c.total += (c.bytes[k] + 255) & ~(size_t)255;
+    c.off[k] = l.take(c.bytes[k]);
   }
+  c.total = l.total();
   c.n = n;
   c.np = np;
 }
@@ -992,26 +1038,22 @@ static void dedup_comm_rows(const lcv_ctx* ctx, const uint32_t* store_index, con
 }
 // the grouping of a one-chunk host batch about to be staged: classes, then items by (class, committee row), into
 // the context's scratch; `dd` then names the two columns that travel with the batch.  Off (dd.m == 0) while the mode
-// is, and for a batch batch_cols is about to refuse
-static int dedup_stage(lcv_ctx* ctx, const char* who, const lcv_update_batch* hb, const uint32_t* store_index, DedupCols& dd) {
+// is, and for a batch batch_cols is about to refuse.  Allocates host memory: within the boundary (guarded)
+static int dedup_stage(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index, DedupCols& dd) {
   dd = DedupCols{nullptr, nullptr, 0};
   if (!dedup_on(ctx) || hb->n == 0 || hb->n > ctx->chunk || !hb->attested.beacon || !hb->signature_slot || !hb->sync_bits ||
       !hb->sync_signature)
     return LCV_OK;
   const uint32_t n = (uint32_t)hb->n;
-  try {
-    ctx->dd_cls.resize(n);
-    ctx->dd_rep.resize(n);
-    ctx->dd_urow.resize(n);
-    if (store_index) ctx->dd_comm.resize(n);
-    dedup_classes(hb->attested.beacon, hb->signature_slot, hb->sync_bits, hb->sync_signature, n, ctx->dedup_hash_bits,
-                  ctx->dd_cls.data(), ctx->dd_table);
-    if (store_index) dedup_comm_rows(ctx, store_index, hb->signature_slot, n, ctx->dd_comm.data());
-    dd.m = dedup_plan(ctx->dd_cls.data(), store_index ? ctx->dd_comm.data() : nullptr, n, ctx->dedup_hash_bits,
-                      ctx->dd_rep.data(), ctx->dd_urow.data(), ctx->dd_table);
-  } catch (...) {  // an extern "C" entry point must not let an exception out
-    return fail(ctx, LCV_ENOMEM, std::string(who) + ": out of host memory");
-  }
+  ctx->dd_cls.resize(n);
+  ctx->dd_rep.resize(n);
+  ctx->dd_urow.resize(n);
+  if (store_index) ctx->dd_comm.resize(n);
+  dedup_classes(hb->attested.beacon, hb->signature_slot, hb->sync_bits, hb->sync_signature, n, ctx->dedup_hash_bits,
+                ctx->dd_cls.data(), ctx->dd_table);
+  if (store_index) dedup_comm_rows(ctx, store_index, hb->signature_slot, n, ctx->dd_comm.data());
+  dd.m = dedup_plan(ctx->dd_cls.data(), store_index ? ctx->dd_comm.data() : nullptr, n, ctx->dedup_hash_bits,
+                    ctx->dd_rep.data(), ctx->dd_urow.data(), ctx->dd_table);
   dd.rep = ctx->dd_rep.data();
   dd.urow = ctx->dd_urow.data();
   return LCV_OK;
@@ -1022,7 +1064,8 @@ static int dedup_stage(lcv_ctx* ctx, const char* who, const lcv_update_batch* hb
 static int dedup_chunk(lcv_ctx* ctx, const lcv_dbatch* db, int slot, size_t base, uint32_t n, DedupRun& R) {
   LCV_TRY(ensure_dedup(ctx, n, slot));
   be_set_slot(ctx, slot);
-  R.D = ctx->Dslot[slot];
+  Slot& s = ctx->slot[slot];
+  R.D = s.D;
   if (db->plan_m) {
     R.rep = db->plan_rep;
     R.urow = db->plan_urow;
@@ -1030,20 +1073,16 @@ static int dedup_chunk(lcv_ctx* ctx, const lcv_dbatch* db, int slot, size_t base
     return LCV_OK;
   }
   LCV_TRY(be_wait_event(ctx, EV_PLAN));  // the slot's previous grouping has left the pinned buffer
-  LCV_TRY(host_alloc_grow(ctx, &ctx->plan_pin[slot], &ctx->plan_pin_cap[slot], 8 * (size_t)n));
-  uint32_t* rep = (uint32_t*)ctx->plan_pin[slot];
+  LCV_TRY(s.plan_pin.grow(ctx, 8 * (size_t)n));
+  uint32_t* rep = (uint32_t*)s.plan_pin.p;
   uint32_t* urow = rep + n;
   const bool table = !db->h_store.empty();
-  try {
-    if (table) {
-      ctx->dd_comm.resize(n);
-      dedup_comm_rows(ctx, db->h_store.data() + base, db->h_sig_slot.data() + base, n, ctx->dd_comm.data());
-    }
-    R.m = dedup_plan(db->cls.data() + base, table ? ctx->dd_comm.data() : nullptr, n, ctx->dedup_hash_bits, rep, urow,
-                     ctx->dd_table);
-  } catch (...) {
-    return fail(ctx, LCV_ENOMEM, "validate: out of host memory");
+  if (table) {
+    ctx->dd_comm.resize(n);
+    dedup_comm_rows(ctx, db->h_store.data() + base, db->h_sig_slot.data() + base, n, ctx->dd_comm.data());
   }
+  R.m = dedup_plan(db->cls.data() + base, table ? ctx->dd_comm.data() : nullptr, n, ctx->dedup_hash_bits, rep, urow,
+                   ctx->dd_table);
   LCV_TRY(be_h2d(ctx, R.D.rep, rep, 4 * (size_t)n));
   LCV_TRY(be_h2d(ctx, R.D.urow, urow, 4 * (size_t)R.m));
   LCV_TRY(be_mark(ctx, EV_PLAN, 0));
@@ -1054,15 +1093,45 @@ static int dedup_chunk(lcv_ctx* ctx, const lcv_dbatch* db, int slot, size_t base
 
 extern "C" {
 
+void lcv_batch_free(lcv_ctx* ctx, lcv_dbatch* b) {
+  if (!ctx || !b) return;
+  b->mem.release(ctx);
+  delete b;
+}
+
+// A resident batch in the making: batch_new allocates it for the layout c and binds its columns; it is abandoned
+// (freed) when the call returns, on every path, unless it has been handed out
+struct NewBatch {
+  lcv_ctx* ctx;
+  lcv_dbatch* db = nullptr;
+  explicit NewBatch(lcv_ctx* c) : ctx(c) {}
+  NewBatch(const NewBatch&) = delete;
+  NewBatch& operator=(const NewBatch&) = delete;
+  ~NewBatch() { lcv_batch_free(ctx, db); }
+  int hand_out(lcv_dbatch** out) {
+    *out = db;
+    db = nullptr;
+    return LCV_OK;
+  }
+};
+static int batch_new(lcv_ctx* ctx, const BatchCols& c, NewBatch& nb) {
+  nb.db = new (std::nothrow) lcv_dbatch();
+  if (!nb.db) return fail(ctx, LCV_ENOMEM, "resident batch: out of host memory");
+  LCV_TRY(nb.db->mem.grow(ctx, c.total));
+  bind_batch(nb.db, nb.db->mem.p, c);
+  return LCV_OK;
+}
+
 static int batch_upload(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index, lcv_dbatch** out) {
   if (!ctx || !hb || !out) return fail(ctx, LCV_EINVAL, "lcv_batch_upload: null argument");
   *out = nullptr;
-  BatchCols c;
-  LCV_TRY(batch_cols(ctx, hb, c, "lcv_batch_upload", store_index));
-  lcv_dbatch* db = new (std::nothrow) lcv_dbatch();
-  if (!db) return LCV_ENOMEM;
-  if (dedup_on(ctx)) {  // the class column, and what a table batch's committee choice reads, stay on the host
-    try {
+  return guarded(ctx, "lcv_batch_upload", [&]() -> int {
+    BatchCols c;
+    LCV_TRY(batch_cols(ctx, hb, c, "lcv_batch_upload", store_index));
+    NewBatch nb(ctx);
+    LCV_TRY(batch_new(ctx, c, nb));
+    lcv_dbatch* db = nb.db;
+    if (dedup_on(ctx)) {  // the class column, and what a table batch's committee choice reads, stay on the host
       db->cls.resize(c.n);
       dedup_classes(hb->attested.beacon, hb->signature_slot, hb->sync_bits, hb->sync_signature, (uint32_t)c.n,
                     ctx->dedup_hash_bits, db->cls.data(), ctx->dd_table);
@@ -1070,23 +1139,11 @@ static int batch_upload(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t
         db->h_store.assign(store_index, store_index + c.n);
         db->h_sig_slot.assign(hb->signature_slot, hb->signature_slot + c.n);
       }
-    } catch (...) {  // an extern "C" entry point must not let an exception out
-      delete db;
-      return fail(ctx, LCV_ENOMEM, "lcv_batch_upload: out of host memory");
     }
-  }
-  int rc = be_alloc(ctx, &db->mem, c.total);
-  if (rc != LCV_OK) { delete db; return rc; }
-  uint8_t* m = (uint8_t*)db->mem;
-  for (int k = 0; k < BATCH_COLS; ++k) {
-    rc = be_h2d(ctx, m + c.off[k], c.src[k], c.bytes[k]);
-    if (rc != LCV_OK) { be_free(ctx, db->mem); delete db; return rc; }
-  }
-  bind_batch(db, m, c);
-  rc = be_sync(ctx);
-  if (rc != LCV_OK) { be_free(ctx, db->mem); delete db; return rc; }
-  *out = db;
-  return LCV_OK;
+    for (int k = 0; k < BATCH_COLS; ++k) LCV_TRY(be_h2d(ctx, db->mem.p + c.off[k], c.src[k], c.bytes[k]));
+    LCV_TRY(be_sync(ctx));
+    return nb.hand_out(out);
+  });
 }
 
 int lcv_batch_upload(lcv_ctx* ctx, const lcv_update_batch* hb, lcv_dbatch** out) {
@@ -1098,12 +1155,6 @@ int lcv_batch_upload(lcv_ctx* ctx, const lcv_update_batch* hb, lcv_dbatch** out)
 int lcv_batch_upload_stores(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index, lcv_dbatch** out) {
   if (!store_index) return fail(ctx, LCV_EINVAL, "lcv_batch_upload_stores: null argument");
   return batch_upload(ctx, hb, store_index, out);
-}
-
-void lcv_batch_free(lcv_ctx* ctx, lcv_dbatch* b) {
-  if (!ctx || !b) return;
-  if (b->mem) be_free(ctx, b->mem);
-  delete b;
 }
 
 int lcv_batch_shape(lcv_ctx* ctx, const lcv_dbatch* b, uint64_t* n_out, uint64_t* npool_out) {
@@ -1150,10 +1201,10 @@ static void seg_bind(FoldReq& f, uint8_t* m, const BatchCols& c) {
   f.seg_dev.in = m + c.off[COL_SEG_IN];
 }
 static int ensure_fold_seg(lcv_ctx* ctx, int slot, size_t nseg) {
-  if (nseg <= ctx->seg_cap[slot] && ctx->seg_mem[slot]) return LCV_OK;
-  size_t cap = 2 * ctx->seg_cap[slot] > nseg ? 2 * ctx->seg_cap[slot] : nseg;
-  if (cap < 64) cap = 64;
-  return dev_alloc_grow(ctx, &ctx->seg_mem[slot], &ctx->seg_cap[slot], cap, cap * FOLD_RESULT_BYTES);
+  DevBuf& seg = ctx->slot[slot].seg;
+  if (seg.p && nseg <= seg.cap) return LCV_OK;
+  const size_t cap = std::max({nseg, 2 * seg.cap, (size_t)64});  // doubles
+  return seg.renew(ctx, cap, cap * FOLD_RESULT_BYTES);
 }
 static int fold_seg_stage(lcv_ctx* ctx, const Work& W, const StoreDev& S, const FoldSegDev& G, uint32_t nseg) {
   return stage(ctx, ST_FOLD, [&] { return be_launch_team(ctx, F_fold_seg{W, S, G}, nseg); });
@@ -1234,7 +1285,7 @@ static int validate_prepare(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot,
   v.seg_dev = FoldSegDev{};
   if (segs) {
     v.seg_dev = fold->seg_dev;
-    v.seg_dev.out = (uint8_t*)ctx->seg_mem[v.slot];
+    v.seg_dev.out = ctx->slot[v.slot].seg.p;
   }
   v.fold_bytes = segs ? (size_t)FOLD_RESULT_BYTES * segs->nseg : (size_t)FOLD_RESULT_BYTES;
   v.P.cfg = ctx->cfg;
@@ -1243,7 +1294,7 @@ static int validate_prepare(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot,
   v.P.next_known = ctx->next_known;
   for (int k = 0; k < 8; ++k) v.P.gvr[k] = host_be32(gvr + 4 * k);
   // (the table path never reads the pool rows' store-equality flag: item_nsc_team gets a valid row to compare)
-  v.C = table ? committee_view(ctx->table, ctx->table.raw) : committee_view(ctx->store, ctx->store.raw + K_SC);
+  v.C = table ? committee_view(ctx->table, ctx->table.raw.p) : committee_view(ctx->store, ctx->store.raw.p + K_SC);
   v.S = table ? &ctx->table_dev : nullptr;
   return LCV_OK;
 }
@@ -1252,8 +1303,8 @@ static int validate_prepare(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot,
 // one place.  bls_chunk: a chunk of a batch that has its grouping (staged) or its class column (resident) runs the
 // BLS half once per distinct item under lcv_set_dedup; otherwise, and always with the mode off, once per row
 static void count_items(ValidateRun& v, uint64_t rows, uint64_t items) {
-  v.ctx->dd_rows[v.slot] += rows;
-  v.ctx->dd_items[v.slot] += items;
+  v.ctx->slot[v.slot].dd_rows += rows;
+  v.ctx->slot[v.slot].dd_items += items;
 }
 // rlc_chunk: a chunk of `items` items on the batch engine under lcv_set_rlc gets the slot's scratch, the next batch
 // counter and its groups counted for lcv_last_rlc (the batch's first chunk on a slot zeroes that slot's count of retried
@@ -1268,15 +1319,16 @@ static int rlc_chunk(ValidateRun& v, int sl, uint32_t items, RlcRun& run, const 
   *L = nullptr;
   if (!v.rlc || items == 0 || fan_on(ctx, items)) return LCV_OK;
   LCV_TRY(ensure_rlc(ctx, sl));
-  run.D = ctx->Rslot[sl];
+  run.D = ctx->slot[sl].R;
   for (int k = 0; k < 8; ++k) run.key.seed[k] = ctx->rlc_seed[k];
   run.key.counter = ctx->rlc_counter++;
   run.shift = 0;
   while ((1u << run.shift) < ctx->rlc_group) ++run.shift;
-  const bool first = !(ctx->rl_used[v.slot] & (1u << sl));
+  Slot& counted = ctx->slot[v.slot];
+  const bool first = !(counted.rl_used & (1u << sl));
   LCV_TRY(be_memset(ctx, run.D.cnt, 0, first ? 2 * sizeof(uint32_t) : sizeof(uint32_t)));
-  ctx->rl_used[v.slot] |= 1u << sl;
-  ctx->rl_groups[v.slot] += (items + ctx->rlc_group - 1) / ctx->rlc_group;
+  counted.rl_used |= 1u << sl;
+  counted.rl_groups += (items + ctx->rlc_group - 1) / ctx->rlc_group;
   *L = &run;
   return LCV_OK;
 }
@@ -1308,11 +1360,12 @@ static int chunk_results(ValidateRun& v, size_t base, uint32_t m) {
     // one chunk: both arrays (and a fold's result) into pinned memory without a wait each, handed out by
     // validate_finish after its sync
     HostSlot& h = ctx->hsync;
-    LCV_TRY(host_alloc_grow(ctx, &h.out, &h.out_cap, 2 * (size_t)m + v.fold_bytes));
-    LCV_TRY(be_d2h(ctx, h.out, ctx->W.verdict, m));
-    LCV_TRY(be_d2h(ctx, h.out + m, ctx->W.reason, m));
-    if (v.segs) LCV_TRY(be_d2h(ctx, h.out + 2 * (size_t)m, v.seg_dev.out, v.fold_bytes));
-    else if (q.fold) LCV_TRY(be_d2h(ctx, h.out + 2 * (size_t)m, ctx->W.fold_out, sizeof(FoldResult)));
+    LCV_TRY(h.out.grow(ctx, 2 * (size_t)m + v.fold_bytes));
+    uint8_t* out = h.out.p;
+    LCV_TRY(be_d2h(ctx, out, ctx->W.verdict, m));
+    LCV_TRY(be_d2h(ctx, out + m, ctx->W.reason, m));
+    if (v.segs) LCV_TRY(be_d2h(ctx, out + 2 * (size_t)m, v.seg_dev.out, v.fold_bytes));
+    else if (q.fold) LCV_TRY(be_d2h(ctx, out + 2 * (size_t)m, ctx->W.fold_out, sizeof(FoldResult)));
     v.pinned_out = true;
   } else {
     if (q.verdict_host) LCV_TRY(be_d2h(ctx, q.verdict_host + base, ctx->W.verdict, m));
@@ -1327,7 +1380,7 @@ static int validate_finish(ValidateRun& v) {
   const ValidateReq& q = v.q;
   LCV_TRY(be_sync(ctx));
   if (v.pinned_out) {
-    const uint8_t* out = ctx->hsync.out;
+    const uint8_t* out = ctx->hsync.out.p;
     if (q.verdict_host) memcpy(q.verdict_host, out, v.n);
     if (q.reason_host) memcpy(q.reason_host, out + v.n, v.n);
     if (v.segs && q.fold->out) fold_seg_scatter(q.fold->out, out + 2 * v.n, v.segs->store.data(), v.segs->nseg);
@@ -1347,7 +1400,7 @@ static int validate_rotating(ValidateRun& v) {
     const size_t base = c * cap;
     const uint32_t m = (uint32_t)((n - base) < cap ? (n - base) : cap);
     be_set_slot(ctx, (int)(c % LCV_SLOTS));
-    const Work& Wc = ctx->Wslot[c % LCV_SLOTS];
+    const Work& Wc = ctx->slot[c % LCV_SLOTS].W;
     if (q.verdict_host) LCV_TRY(be_d2h(ctx, q.verdict_host + base, Wc.verdict, m));
     if (q.reason_host) LCV_TRY(be_d2h(ctx, q.reason_host + base, Wc.reason, m));
     if (q.verdict_dev) LCV_TRY(be_d2d(ctx, q.verdict_dev + base, Wc.verdict, m));
@@ -1420,22 +1473,24 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
   const int ns = ctx->pipe_streams < 4 ? ctx->pipe_streams : 4;  // lcv_set_pipeline: min(streams, 4)
   const bool piped = !v.async && ns > 1 && ctx->pipe_chunks > 1;
   v.dedup = dedup_on(ctx) && !piped && (db->plan_m > 0 || !db->cls.empty());
-  ctx->dd_rows[v.slot] = ctx->dd_items[v.slot] = 0;
+  Slot& s = ctx->slot[v.slot];
+  s.dd_rows = s.dd_items = 0;
   v.rlc = rlc_on(ctx) && !piped;
-  ctx->rl_groups[v.slot] = 0;
-  ctx->rl_used[v.slot] = 0;
+  s.rl_groups = 0;
+  s.rl_used = 0;
   const bool marks_were_off = ctx->marks_off;
   if (v.async) {
     ctx->marks_off = true;  // nothing collects an asynchronous batch's stage marks
-    ctx->hslot[v.slot].staged = false;
-    ctx->hslot[v.slot].folded = false;
-    ctx->hslot[v.slot].seg_folded = false;
+    s.host.staged = s.host.folded = s.host.seg_folded = false;
   }
-  const int rc = piped ? validate_sliced(v, ns) : (!v.async && v.n > v.cap) ? validate_rotating(v) : validate_single(v);
+  // (the boundary: a resident chunk's grouping under lcv_set_dedup allocates host memory, dedup_chunk)
+  const int rc = guarded(ctx, "validate", [&] {
+    return piped ? validate_sliced(v, ns) : (!v.async && v.n > v.cap) ? validate_rotating(v) : validate_single(v);
+  });
   // whatever the schedule and its outcome: the caller's marks setting, slot 0 and its work space are the active ones again
   ctx->marks_off = marks_were_off;
   be_set_slot(ctx, 0);
-  if (ctx->work_mem[0]) ctx->W = ctx->Wslot[0];
+  if (ctx->slot[0].work.p) ctx->W = ctx->slot[0].W;
   return rc;
 }
 
@@ -1508,7 +1563,7 @@ static void stage_columns(uint8_t* dst, const BatchCols& c) {
 // buffer and ONE DMA into h's reused device copy, on the slot's main stream, instead of a device allocation, one
 // copy per column and a free per call; h.db then names the device columns, and fold->seg_dev the grouping's.
 // slot < 0: the synchronous entries, h = ctx->hsync, on slot 0.  slot >= 0 (lcv_validate_async and its kin, h =
-// ctx->hslot[slot]): the staging buffer is reused only after the slot's previous batch has left it (EV_H2D,
+// ctx->slot[slot].host): the staging buffer is reused only after the slot's previous batch has left it (EV_H2D,
 // recorded behind the copy), the slot is waited for before a buffer it may still use is regrown, h.out is grown
 // for the verdicts, the reasons and a fold's result (a segmented fold's: one per store present), and slot 0 is
 // the active one again on return
@@ -1517,25 +1572,25 @@ static int stage_host_batch(lcv_ctx* ctx, const char* who, const lcv_update_batc
   const bool async = slot >= 0;
   const FoldSegs* segs = fold ? fold->segs : nullptr;
   DedupCols dd;
-  LCV_TRY(dedup_stage(ctx, who, hb, store_index, dd));
+  LCV_TRY(dedup_stage(ctx, hb, store_index, dd));
   LCV_TRY(batch_cols(ctx, hb, c, who, store_index, segs, dd.m ? &dd : nullptr));
   be_set_slot(ctx, async ? slot : 0);
   const size_t out_bytes = 2 * c.n + (size_t)FOLD_RESULT_BYTES * (segs ? segs->nseg : 1);
   int rc = async ? be_wait_event(ctx, EV_H2D) : LCV_OK;
-  if (async && rc == LCV_OK && (c.total > h.pinned_cap || out_bytes > h.out_cap)) rc = be_sync_slot(ctx);
-  if (rc == LCV_OK) rc = host_alloc_grow(ctx, &h.pinned, &h.pinned_cap, c.total);
-  if (async && rc == LCV_OK) rc = host_alloc_grow(ctx, &h.out, &h.out_cap, out_bytes);
-  if (rc == LCV_OK) rc = dev_alloc_grow(ctx, &h.dev, &h.dev_cap, c.total, c.total);
+  if (async && rc == LCV_OK && (c.total > h.pinned.cap || out_bytes > h.out.cap)) rc = be_sync_slot(ctx);
+  if (rc == LCV_OK) rc = h.pinned.grow(ctx, c.total);
+  if (async && rc == LCV_OK) rc = h.out.grow(ctx, out_bytes);
+  if (rc == LCV_OK) rc = h.dev.grow(ctx, c.total);
   if (rc == LCV_OK) {
-    stage_columns(h.pinned, c);
+    stage_columns(h.pinned.p, c);
     be_set_slot(ctx, async ? slot : 0);  // (be_free above may not keep the slot)
-    rc = be_h2d(ctx, h.dev, h.pinned, c.total);
+    rc = be_h2d(ctx, h.dev.p, h.pinned.p, c.total);
     if (async && rc == LCV_OK) rc = be_mark(ctx, EV_H2D, 0);
   }
   if (async) be_set_slot(ctx, 0);
   if (rc != LCV_OK) return rc;
-  bind_batch(&h.db, (uint8_t*)h.dev, c);
-  if (segs) seg_bind(*fold, (uint8_t*)h.dev, c);
+  bind_batch(&h.db, h.dev.p, c);
+  if (segs) seg_bind(*fold, h.dev.p, c);
   return LCV_OK;
 }
 
@@ -1552,36 +1607,39 @@ static int store_index_check(lcv_ctx* ctx, const char* who, const uint32_t* stor
 // (lcv_validate_stores_async), the 14th column staged with the others
 static int validate_async_host(lcv_ctx* ctx, const char* who, const lcv_update_batch* hb, const uint32_t* store_index,
                                uint64_t current_slot, const uint8_t* gvr, int slot, FoldReq* fold = nullptr) {
-  const FoldSegs* segs = fold ? fold->segs : nullptr;  // (a segmented fold's grouping has checked every index)
-  if (store_index && !segs) LCV_TRY(store_index_check(ctx, who, store_index, hb->n));  // before the DMA
-  HostSlot& h = ctx->hslot[slot];
-  BatchCols c;
-  LCV_TRY(stage_host_batch(ctx, who, hb, store_index, fold, slot, h, c));
-  ValidateReq q;
-  q.slot = slot;
-  q.fold = fold;
-  LCV_TRY(validate_impl(ctx, &h.db, current_slot, gvr, q));
-  be_set_slot(ctx, slot);
-  const Work& W = ctx->Wslot[slot];
-  int rc = be_d2h(ctx, h.out, W.verdict, c.n);
-  if (rc == LCV_OK) rc = be_d2h(ctx, h.out + c.n, W.reason, c.n);
-  if (rc == LCV_OK && segs) rc = be_d2h(ctx, h.out + 2 * c.n, ctx->seg_mem[slot], (size_t)FOLD_RESULT_BYTES * segs->nseg);
-  else if (rc == LCV_OK && fold) rc = be_d2h(ctx, h.out + 2 * c.n, W.fold_out, sizeof(FoldResult));
-  be_set_slot(ctx, 0);
-  if (rc != LCV_OK) return rc;
-  h.out_n = c.n;
-  h.staged = true;
-  h.folded = fold != nullptr && !segs;
-  h.seg_folded = segs != nullptr;
-  if (segs) {
-    try {
-      h.seg_store = segs->store;
-    } catch (...) {  // an extern "C" entry point must not let an exception out
-      h.staged = h.seg_folded = false;
-      return fail(ctx, LCV_ENOMEM, std::string(who) + ": out of host memory");
+  return guarded(ctx, who, [&]() -> int {
+    const FoldSegs* segs = fold ? fold->segs : nullptr;  // (a segmented fold's grouping has checked every index)
+    if (store_index && !segs) LCV_TRY(store_index_check(ctx, who, store_index, hb->n));  // before the DMA
+    Slot& s = ctx->slot[slot];
+    HostSlot& h = s.host;
+    BatchCols c;
+    LCV_TRY(stage_host_batch(ctx, who, hb, store_index, fold, slot, h, c));
+    ValidateReq q;
+    q.slot = slot;
+    q.fold = fold;
+    LCV_TRY(validate_impl(ctx, &h.db, current_slot, gvr, q));
+    be_set_slot(ctx, slot);
+    uint8_t* out = h.out.p;
+    int rc = be_d2h(ctx, out, s.W.verdict, c.n);
+    if (rc == LCV_OK) rc = be_d2h(ctx, out + c.n, s.W.reason, c.n);
+    if (rc == LCV_OK && segs) rc = be_d2h(ctx, out + 2 * c.n, s.seg.p, (size_t)FOLD_RESULT_BYTES * segs->nseg);
+    else if (rc == LCV_OK && fold) rc = be_d2h(ctx, out + 2 * c.n, s.W.fold_out, sizeof(FoldResult));
+    be_set_slot(ctx, 0);
+    if (rc != LCV_OK) return rc;
+    h.out_n = c.n;
+    h.staged = true;
+    h.folded = fold != nullptr && !segs;
+    h.seg_folded = segs != nullptr;
+    if (segs) {
+      try {
+        h.seg_store = segs->store;
+      } catch (...) {  // the slot holds no results that lcv_slot_wait_stores_fold could scatter
+        h.staged = h.seg_folded = false;
+        throw;
+      }
     }
-  }
-  return LCV_OK;
+    return LCV_OK;
+  });
 }
 
 int lcv_validate_async(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t current_slot, const uint8_t* gvr, int slot) {
@@ -1603,20 +1661,21 @@ int lcv_validate_stores_async(lcv_ctx* ctx, const lcv_update_batch* hb, const ui
 
 int lcv_slot_wait(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint8_t* reason_out) {
   if (!ctx || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_slot_wait: slot must be 0..7");
-  HostSlot& h = ctx->hslot[slot];
+  Slot& s = ctx->slot[slot];
+  HostSlot& h = s.host;
   if (h.staged) {  // a host-input batch (lcv_validate_async): its results are already on their way to pinned memory
     if (n > h.out_n) return fail(ctx, LCV_EINVAL, "lcv_slot_wait: more rows than the slot's batch");
     be_set_slot(ctx, slot);
     const int rc = be_sync_slot(ctx);
     be_set_slot(ctx, 0);
     if (rc != LCV_OK) return rc;
-    if (n && verdict_out) memcpy(verdict_out, h.out, n);
-    if (n && reason_out) memcpy(reason_out, h.out + h.out_n, n);
+    if (n && verdict_out) memcpy(verdict_out, h.out.p, n);
+    if (n && reason_out) memcpy(reason_out, h.out.p + h.out_n, n);
     return LCV_OK;
   }
-  if (n > ctx->work_cap[slot] || (n && !ctx->work_mem[slot])) return fail(ctx, LCV_EINVAL, "lcv_slot_wait: more rows than the slot holds");
+  if (n > s.work.cap) return fail(ctx, LCV_EINVAL, "lcv_slot_wait: more rows than the slot holds");
   be_set_slot(ctx, slot);
-  const Work& W = ctx->Wslot[slot];
+  const Work& W = s.W;
   int rc = LCV_OK;
   if (n && verdict_out) rc = be_d2h(ctx, verdict_out, W.verdict, n);
   if (rc == LCV_OK && n && reason_out) rc = be_d2h(ctx, reason_out, W.reason, n);
@@ -1634,19 +1693,21 @@ static int validate_host(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_
   q.verdict_host = verdict_out;
   q.reason_host = reason_out;
   q.fold = fold;
-  if (ctx && hb && gvr && (table ? ctx->table_set : ctx->store_set) && hb->n > 0 && hb->n <= ctx->chunk) {
-    // one chunk (the reference's per-update call shape among them): staged like lcv_validate_async's, waited for here
-    BatchCols c;
-    LCV_TRY(stage_host_batch(ctx, "lcv_validate_updates", hb, store_index, fold, -1, ctx->hsync, c));
-    return validate_impl(ctx, &ctx->hsync.db, current_slot, gvr, q);  // returns synced
-  }
-  if (fold) return fail(ctx, LCV_EINVAL, "lcv_validate_fold: null argument, no store set, or not 0 < n <= one chunk");
-  // larger batches (and invalid arguments, reported by the upload): a device batch per call
-  lcv_dbatch* db = nullptr;
-  LCV_TRY(batch_upload(ctx, hb, store_index, &db));
-  int rc = validate_impl(ctx, db, current_slot, gvr, q);
-  lcv_batch_free(ctx, db);
-  return rc;
+  return guarded(ctx, "lcv_validate_updates", [&]() -> int {
+    if (ctx && hb && gvr && (table ? ctx->table_set : ctx->store_set) && hb->n > 0 && hb->n <= ctx->chunk) {
+      // one chunk (the reference's per-update call shape among them): staged like lcv_validate_async's, waited for here
+      BatchCols c;
+      LCV_TRY(stage_host_batch(ctx, "lcv_validate_updates", hb, store_index, fold, -1, ctx->hsync, c));
+      return validate_impl(ctx, &ctx->hsync.db, current_slot, gvr, q);  // returns synced
+    }
+    if (fold) return fail(ctx, LCV_EINVAL, "lcv_validate_fold: null argument, no store set, or not 0 < n <= one chunk");
+    // larger batches (and invalid arguments, reported by the upload): a device batch per call
+    lcv_dbatch* db = nullptr;
+    LCV_TRY(batch_upload(ctx, hb, store_index, &db));
+    int rc = validate_impl(ctx, db, current_slot, gvr, q);
+    lcv_batch_free(ctx, db);
+    return rc;
+  });
 }
 
 int lcv_validate_updates(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t current_slot, const uint8_t* gvr,
@@ -1683,10 +1744,10 @@ int lcv_validate_async_fold(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t c
 
 int lcv_slot_wait_fold(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint8_t* reason_out, lcv_fold_result* out) {
   if (!ctx || !out || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_slot_wait_fold: null argument or slot not in 0..7");
-  HostSlot& h = ctx->hslot[slot];
+  HostSlot& h = ctx->slot[slot].host;
   if (!h.staged || !h.folded) return fail(ctx, LCV_ESTATE, "lcv_slot_wait_fold: the slot's batch was not enqueued with a fold");
   LCV_TRY(lcv_slot_wait(ctx, slot, n, verdict_out, reason_out));  // waits for the slot
-  memcpy(out, h.out + 2 * h.out_n, sizeof(FoldResult));
+  memcpy(out, h.out.p + 2 * h.out_n, sizeof(FoldResult));
   return LCV_OK;
 }
 
@@ -1698,30 +1759,26 @@ int lcv_debug_fold(lcv_ctx* ctx, const uint8_t* rank, const uint8_t* verdict, ui
   FoldState s;
   LCV_TRY(fold_state_in(ctx, "lcv_debug_fold", in, s));
   // the three fields F_fold touches, in an allocation of their own (a whole work space of n rows is not needed)
-  const size_t o_ver = (rank_index((size_t)n) + 255) & ~(size_t)255, o_out = o_ver + (((size_t)n + 255) & ~(size_t)255);
-  void* mem = nullptr;
+  Layout l;
+  const size_t o_rank = l.take(rank_index((size_t)n)), o_ver = l.take((size_t)n), o_out = l.total();
+  Scratch mem(ctx);
   be_set_slot(ctx, 0);
-  LCV_TRY(be_alloc(ctx, &mem, o_out + FOLD_RESULT_BYTES));
-  uint8_t* m = (uint8_t*)mem;
+  LCV_TRY(mem.alloc(o_out + FOLD_RESULT_BYTES));
   Work W = Work{};
   W.cap = (uint32_t)n;
-  W.rank = m;
-  W.verdict = m + o_ver;
-  W.fold_out = m + o_out;
+  W.rank = mem.p + o_rank;
+  W.verdict = mem.p + o_ver;
+  W.fold_out = mem.p + o_out;
   be_reset_timings(ctx);
   FoldResult res;
-  auto body = [&]() -> int {
-    LCV_TRY(be_h2d(ctx, W.rank, rank, rank_index((size_t)n)));
-    LCV_TRY(be_h2d(ctx, W.verdict, verdict, (size_t)n));
-    LCV_TRY(stage(ctx, ST_FOLD, [&] {
-      return be_launch_team(ctx, F_fold{W, s, store_finalized_slot, next_known ? 1u : 0u, (uint32_t)n}, 1);
-    }));
-    LCV_TRY(be_d2h(ctx, &res, W.fold_out, sizeof(res)));
-    return be_sync(ctx);
-  };
-  const int rc = body();
-  be_free(ctx, mem);  // (waits for the streams)
-  if (rc != LCV_OK) return rc;
+  LCV_TRY(be_h2d(ctx, W.rank, rank, rank_index((size_t)n)));
+  LCV_TRY(be_h2d(ctx, W.verdict, verdict, (size_t)n));
+  LCV_TRY(stage(ctx, ST_FOLD, [&] {
+    return be_launch_team(ctx, F_fold{W, s, store_finalized_slot, next_known ? 1u : 0u, (uint32_t)n}, 1);
+  }));
+  LCV_TRY(be_d2h(ctx, &res, W.fold_out, sizeof(res)));
+  LCV_TRY(be_sync(ctx));
+  mem.release();  // (waits for the streams)
   be_collect_timings(ctx);
   memcpy(out, &res, sizeof(res));
   return LCV_OK;
@@ -1740,15 +1797,13 @@ int lcv_rank_updates(lcv_ctx* ctx, const lcv_update_batch* hb, uint8_t* rank_out
   const size_t width[6] = {K_BEACON, K_BEACON, K_NSC_BRANCH, K_FIN_BRANCH, 64, 8};
   const uint8_t* src[6] = {hb->attested.beacon, hb->finalized.beacon, hb->nsc_branch, hb->finality_branch, hb->sync_bits,
                            (const uint8_t*)hb->signature_slot};
-  size_t off[7], total = 0;
-  for (int k = 0; k < 7; ++k) {
-    off[k] = total;
-    total += ((k < 6 ? width[k] : (size_t)RANK_BYTES) * piece + 255) & ~(size_t)255;
-  }
-  void* mem = nullptr;
+  size_t off[7];
+  Layout l;
+  for (int k = 0; k < 7; ++k) off[k] = l.take((k < 6 ? width[k] : (size_t)RANK_BYTES) * piece);
+  Scratch mem(ctx);
   be_set_slot(ctx, 0);
-  LCV_TRY(be_alloc(ctx, &mem, total));
-  uint8_t* m = (uint8_t*)mem;
+  LCV_TRY(mem.alloc(l.total()));
+  uint8_t* m = mem.p;
   BatchDev B = {};
   B.att_beacon = m + off[0]; B.fin_beacon = m + off[1]; B.nsc_branch = m + off[2]; B.finality_branch = m + off[3];
   B.bits = m + off[4]; B.sig_slot = (const uint64_t*)(m + off[5]);
@@ -1757,21 +1812,16 @@ int lcv_rank_updates(lcv_ctx* ctx, const lcv_update_batch* hb, uint8_t* rank_out
   Params P = {};
   P.cfg = ctx->cfg;
   be_reset_timings(ctx);
-  auto body = [&]() -> int {
-    for (size_t base = 0; base < n; base += piece) {
-      const size_t len = n - base < piece ? n - base : piece;
-      for (int k = 0; k < 6; ++k) LCV_TRY(be_h2d(ctx, m + off[k], src[k] + width[k] * base, width[k] * len));
-      B.n = (uint32_t)len;
-      LCV_TRY(rank_stage(ctx, B, P, W, (uint32_t)len));
-      LCV_TRY(be_d2h(ctx, rank_out + rank_index(base), W.rank, rank_index(len)));
-      LCV_TRY(be_sync(ctx));  // the caller's pageable memory: each piece has left before the buffers are reused
-    }
-    be_collect_timings(ctx);
-    return LCV_OK;
-  };
-  const int rc = body();
-  be_free(ctx, mem);  // (waits for the streams)
-  return rc;
+  for (size_t base = 0; base < n; base += piece) {
+    const size_t len = n - base < piece ? n - base : piece;
+    for (int k = 0; k < 6; ++k) LCV_TRY(be_h2d(ctx, m + off[k], src[k] + width[k] * base, width[k] * len));
+    B.n = (uint32_t)len;
+    LCV_TRY(rank_stage(ctx, B, P, W, (uint32_t)len));
+    LCV_TRY(be_d2h(ctx, rank_out + rank_index(base), W.rank, rank_index(len)));
+    LCV_TRY(be_sync(ctx));  // the caller's pageable memory: each piece has left before the buffers are reused
+  }
+  be_collect_timings(ctx);
+  return LCV_OK;  // (the scratch's free waits for the streams)
 }
 
 // ---- store table: a store snapshot per update (a catch-up over several sync-committee periods, whose updates
@@ -1793,60 +1843,56 @@ int lcv_set_store_table(lcv_ctx* ctx, const lcv_store_table* t, uint8_t* key_sta
       return fail(ctx, LCV_EINVAL, "lcv_set_store_table: next[" + std::to_string(s) + "] = " + std::to_string(t->next[s]) +
                                        " is neither a committee row (ncomm " + std::to_string(nc) + ") nor LCV_STORE_NEXT_UNKNOWN");
   }
-  // an all-zero committee as `next` means "not known" (is_next_sync_committee_known, sync-protocol.md:316-317):
-  // decided once per committee row, here
-  std::vector<uint8_t> zero_row(nc, 0);
-  for (size_t c = 0; c < nc; ++c) {
-    const uint8_t* row = t->committees + (size_t)K_SC * c;
-    uint32_t any = 0;
-    for (int k = 0; k < K_SC; ++k) any |= row[k];
-    zero_row[c] = any ? 0 : 1;
-  }
-  const size_t o_cur = (8 * ns + 255) & ~(size_t)255, o_next = o_cur + ((4 * ns + 255) & ~(size_t)255),
-               bytes = o_next + ((4 * ns + 255) & ~(size_t)255);
-  std::vector<uint32_t> next(ns);
-  for (size_t s = 0; s < ns; ++s)
-    next[s] = (t->next[s] == LCV_STORE_NEXT_UNKNOWN || zero_row[t->next[s]]) ? (uint32_t)STORE_NEXT_UNKNOWN : t->next[s];
-  // the store columns also stay on the host, as the device gets them: lcv_set_dedup's grouping makes item_pre_table's
-  // committee choice there (dedup_comm_rows)
-  std::vector<uint64_t> host_fin(t->finalized_slot, t->finalized_slot + ns);
-  std::vector<uint32_t> host_cur(t->current, t->current + ns);
-  // drain: batches in flight on any work-space slot read the table's committees and store columns, so every
-  // slot's streams are waited for before that memory is rewritten or freed.  A batch already enqueued thus
-  // finishes under the table it was enqueued under; work enqueued after this call sees the new one
-  be_set_slot(ctx, 0);
-  LCV_TRY(be_sync(ctx));
-  ctx->table_set = false;
-  auto body = [&]() -> int {
-    LCV_TRY(ensure_committees(ctx, ctx->table, nc, K_SC));
-    if (ns > ctx->table_store_cap || !ctx->table_mem) {
-      if (ctx->table_mem) be_free(ctx, ctx->table_mem);
-      ctx->table_mem = nullptr;
-      ctx->table_store_cap = 0;
-      LCV_TRY(be_alloc(ctx, &ctx->table_mem, bytes));
-      ctx->table_store_cap = ns;
+  return guarded(ctx, "lcv_set_store_table", [&]() -> int {
+    // an all-zero committee as `next` means "not known" (is_next_sync_committee_known, sync-protocol.md:316-317):
+    // decided once per committee row, here
+    std::vector<uint8_t> zero_row(nc, 0);
+    for (size_t c = 0; c < nc; ++c) {
+      const uint8_t* row = t->committees + (size_t)K_SC * c;
+      uint32_t any = 0;
+      for (int k = 0; k < K_SC; ++k) any |= row[k];
+      zero_row[c] = any ? 0 : 1;
     }
-    uint8_t* m = (uint8_t*)ctx->table_mem;
-    LCV_TRY(be_h2d(ctx, ctx->table.raw, t->committees, (size_t)K_SC * nc));
-    LCV_TRY(be_h2d(ctx, m, t->finalized_slot, 8 * ns));
-    LCV_TRY(be_h2d(ctx, m + o_cur, t->current, 4 * ns));
-    LCV_TRY(be_h2d(ctx, m + o_next, next.data(), 4 * ns));
-    ctx->table_dev = StoreDev{(const uint64_t*)m, (const uint32_t*)(m + o_cur), (const uint32_t*)(m + o_next), (uint32_t)ns};
-    be_reset_timings(ctx);
-    LCV_TRY(build_committees(ctx, ctx->table));
-    if (key_status_out) LCV_TRY(be_d2h(ctx, key_status_out, ctx->table.key_status, 512 * nc));
+    Layout l;
+    const size_t o_fin = l.take(8 * ns), o_cur = l.take(4 * ns), o_next = l.take(4 * ns);
+    std::vector<uint32_t> next(ns);
+    for (size_t s = 0; s < ns; ++s)
+      next[s] = (t->next[s] == LCV_STORE_NEXT_UNKNOWN || zero_row[t->next[s]]) ? (uint32_t)STORE_NEXT_UNKNOWN : t->next[s];
+    // the store columns also stay on the host, as the device gets them: lcv_set_dedup's grouping makes item_pre_table's
+    // committee choice there (dedup_comm_rows)
+    std::vector<uint64_t> host_fin(t->finalized_slot, t->finalized_slot + ns);
+    std::vector<uint32_t> host_cur(t->current, t->current + ns);
+    // drain: batches in flight on any work-space slot read the table's committees and store columns, so every
+    // slot's streams are waited for before that memory is rewritten or freed.  A batch already enqueued thus
+    // finishes under the table it was enqueued under; work enqueued after this call sees the new one
+    be_set_slot(ctx, 0);
+    LCV_TRY(be_sync(ctx));
+    ctx->table_set = false;
+    auto body = [&]() -> int {
+      LCV_TRY(ensure_committees(ctx, ctx->table, nc, K_SC));
+      LCV_TRY(ctx->table_mem.grow(ctx, ns, l.total()));
+      uint8_t* m = ctx->table_mem.p;
+      LCV_TRY(be_h2d(ctx, ctx->table.raw.p, t->committees, (size_t)K_SC * nc));
+      LCV_TRY(be_h2d(ctx, m + o_fin, t->finalized_slot, 8 * ns));
+      LCV_TRY(be_h2d(ctx, m + o_cur, t->current, 4 * ns));
+      LCV_TRY(be_h2d(ctx, m + o_next, next.data(), 4 * ns));
+      ctx->table_dev = StoreDev{(const uint64_t*)(m + o_fin), (const uint32_t*)(m + o_cur), (const uint32_t*)(m + o_next), (uint32_t)ns};
+      be_reset_timings(ctx);
+      LCV_TRY(build_committees(ctx, ctx->table));
+      if (key_status_out) LCV_TRY(be_d2h(ctx, key_status_out, ctx->table.key_status.p, 512 * nc));
+      return LCV_OK;
+    };
+    int rc = body();
+    const int rs = be_sync(ctx);  // (also after a failure: `next` leaves scope with no copy pending)
+    if (rc == LCV_OK) rc = rs;
+    if (rc != LCV_OK) return rc;
+    be_collect_timings(ctx);  // the table build's kernel time: lcv_last_timings' setup stage
+    ctx->tab_fin.swap(host_fin);
+    ctx->tab_cur.swap(host_cur);
+    ctx->tab_next.swap(next);
+    ctx->table_set = true;
     return LCV_OK;
-  };
-  int rc = body();
-  const int rs = be_sync(ctx);  // (also after a failure: `next` leaves scope with no copy pending)
-  if (rc == LCV_OK) rc = rs;
-  if (rc != LCV_OK) return rc;
-  be_collect_timings(ctx);  // the table build's kernel time: lcv_last_timings' setup stage
-  ctx->tab_fin.swap(host_fin);
-  ctx->tab_cur.swap(host_cur);
-  ctx->tab_next.swap(next);
-  ctx->table_set = true;
-  return LCV_OK;
+  });
 }
 
 int lcv_validate_updates_stores(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index,
@@ -1862,39 +1908,36 @@ int lcv_validate_updates_stores(lcv_ctx* ctx, const lcv_update_batch* hb, const 
 // store_index_check's pass, grouping as it goes: every index against nstore (naming the first offending row), and
 // the rows keyed by (store, row).  Sorting the keys is the stable grouping — skipped when the rows already come
 // store by store — so the cost is O(n log n) whatever the table's size, and nothing here is sized by nstore.
-// Then the present stores' fold states are checked and gathered (in: indexed by store row).
+// Then the present stores' fold states are checked and gathered (in: indexed by store row).  Allocates host memory:
+// within the boundary (guarded)
 static int fold_segments(lcv_ctx* ctx, const char* who, const uint32_t* store_index, uint64_t n, uint64_t nstore,
                          const lcv_fold_state* in, FoldSegs& g) {
-  try {
-    g.key.resize(n);
-    bool sorted = true;
-    for (uint64_t i = 0; i < n; ++i) {
-      if (store_index[i] >= nstore)
-        return fail(ctx, LCV_EINVAL, std::string(who) + ": store_index[" + std::to_string(i) + "] = " +
-                                         std::to_string(store_index[i]) + " is not a store row (nstore " +
-                                         std::to_string(nstore) + ")");
-      g.key[i] = ((uint64_t)store_index[i] << 32) | i;
-      if (i && g.key[i] < g.key[i - 1]) sorted = false;
-    }
-    if (!sorted) std::sort(g.key.begin(), g.key.end());
-    g.store.clear();
-    g.off.clear();
-    g.in.clear();
-    g.row.resize(n);
-    for (uint64_t j = 0; j < n; ++j) {
-      const uint32_t s = (uint32_t)(g.key[j] >> 32);
-      if (j == 0 || s != g.store.back()) {
-        g.store.push_back(s);
-        g.off.push_back((uint32_t)j);
-      }
-      g.row[j] = (uint32_t)g.key[j];
-    }
-    g.off.push_back((uint32_t)n);
-    g.nseg = (uint32_t)g.store.size();
-    g.in.resize(g.nseg);
-  } catch (...) {  // an extern "C" entry point must not let an exception out
-    return fail(ctx, LCV_ENOMEM, std::string(who) + ": out of host memory");
+  g.key.resize(n);
+  bool sorted = true;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (store_index[i] >= nstore)
+      return fail(ctx, LCV_EINVAL, std::string(who) + ": store_index[" + std::to_string(i) + "] = " +
+                                       std::to_string(store_index[i]) + " is not a store row (nstore " +
+                                       std::to_string(nstore) + ")");
+    g.key[i] = ((uint64_t)store_index[i] << 32) | i;
+    if (i && g.key[i] < g.key[i - 1]) sorted = false;
   }
+  if (!sorted) std::sort(g.key.begin(), g.key.end());
+  g.store.clear();
+  g.off.clear();
+  g.in.clear();
+  g.row.resize(n);
+  for (uint64_t j = 0; j < n; ++j) {
+    const uint32_t s = (uint32_t)(g.key[j] >> 32);
+    if (j == 0 || s != g.store.back()) {
+      g.store.push_back(s);
+      g.off.push_back((uint32_t)j);
+    }
+    g.row[j] = (uint32_t)g.key[j];
+  }
+  g.off.push_back((uint32_t)n);
+  g.nseg = (uint32_t)g.store.size();
+  g.in.resize(g.nseg);
   for (uint32_t k = 0; k < g.nseg; ++k)
     LCV_TRY(fold_state_in(ctx, (std::string(who) + ": in[" + std::to_string(g.store[k]) + "]").c_str(), &in[g.store[k]], g.in[k]));
   return LCV_OK;
@@ -1907,12 +1950,14 @@ int lcv_validate_stores_fold(lcv_ctx* ctx, const lcv_update_batch* hb, const uin
   if (hb->n == 0 || hb->n > LCV_FOLD_MAX_ROWS || hb->n > ctx->chunk)
     return fail(ctx, LCV_EINVAL, "lcv_validate_stores_fold: need 0 < n <= 65536 (one chunk): cut larger batches and carry each store's `next` forward");
   if (!ctx->table_set) return fail(ctx, LCV_ESTATE, "lcv_validate_stores_fold: lcv_set_store_table has not been called");
-  LCV_TRY(fold_segments(ctx, "lcv_validate_stores_fold", store_index, hb->n, ctx->table_dev.nstore, in, ctx->segs));
-  FoldReq req;
-  req.in = FoldState{};
-  req.out = out;
-  req.segs = &ctx->segs;
-  return validate_host(ctx, hb, store_index, current_slot, gvr, verdict_out, reason_out, &req);
+  return guarded(ctx, "lcv_validate_stores_fold", [&]() -> int {
+    LCV_TRY(fold_segments(ctx, "lcv_validate_stores_fold", store_index, hb->n, ctx->table_dev.nstore, in, ctx->segs));
+    FoldReq req;
+    req.in = FoldState{};
+    req.out = out;
+    req.segs = &ctx->segs;
+    return validate_host(ctx, hb, store_index, current_slot, gvr, verdict_out, reason_out, &req);
+  });
 }
 
 int lcv_validate_stores_async_fold(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_t* store_index,
@@ -1922,23 +1967,25 @@ int lcv_validate_stores_async_fold(lcv_ctx* ctx, const lcv_update_batch* hb, con
   if (hb->n == 0 || hb->n > LCV_FOLD_MAX_ROWS || hb->n > ctx->chunk)
     return fail(ctx, LCV_EINVAL, "lcv_validate_stores_async_fold: need 0 < n <= 65536 (one chunk) per call");
   if (!ctx->table_set) return fail(ctx, LCV_ESTATE, "lcv_validate_stores_async_fold: lcv_set_store_table has not been called");
-  LCV_TRY(fold_segments(ctx, "lcv_validate_stores_async_fold", store_index, hb->n, ctx->table_dev.nstore, in, ctx->segs));
-  FoldReq req;
-  req.in = FoldState{};
-  req.out = nullptr;  // the results wait in the slot's pinned area for lcv_slot_wait_stores_fold
-  req.segs = &ctx->segs;
-  return validate_async_host(ctx, "lcv_validate_stores_async_fold", hb, store_index, current_slot, gvr, slot, &req);
+  return guarded(ctx, "lcv_validate_stores_async_fold", [&]() -> int {
+    LCV_TRY(fold_segments(ctx, "lcv_validate_stores_async_fold", store_index, hb->n, ctx->table_dev.nstore, in, ctx->segs));
+    FoldReq req;
+    req.in = FoldState{};
+    req.out = nullptr;  // the results wait in the slot's pinned area for lcv_slot_wait_stores_fold
+    req.segs = &ctx->segs;
+    return validate_async_host(ctx, "lcv_validate_stores_async_fold", hb, store_index, current_slot, gvr, slot, &req);
+  });
 }
 
 int lcv_slot_wait_stores_fold(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint8_t* reason_out,
                               lcv_fold_result* out) {
   if (!ctx || !out || slot < 0 || slot >= LCV_SLOTS)
     return fail(ctx, LCV_EINVAL, "lcv_slot_wait_stores_fold: null argument or slot not in 0..7");
-  HostSlot& h = ctx->hslot[slot];
+  HostSlot& h = ctx->slot[slot].host;
   if (!h.staged || !h.seg_folded)
     return fail(ctx, LCV_ESTATE, "lcv_slot_wait_stores_fold: the slot's batch was not enqueued by lcv_validate_stores_async_fold");
   LCV_TRY(lcv_slot_wait(ctx, slot, n, verdict_out, reason_out));  // waits for the slot
-  fold_seg_scatter(out, h.out + 2 * h.out_n, h.seg_store.data(), h.seg_store.size());
+  fold_seg_scatter(out, h.out.p + 2 * h.out_n, h.seg_store.data(), h.seg_store.size());
   return LCV_OK;
 }
 
@@ -1951,50 +1998,40 @@ int lcv_debug_fold_stores(lcv_ctx* ctx, const uint8_t* rank, const uint8_t* verd
     return fail(ctx, LCV_EINVAL, "lcv_debug_fold_stores: null argument");
   if (n == 0 || n > LCV_FOLD_MAX_ROWS) return fail(ctx, LCV_EINVAL, "lcv_debug_fold_stores: need 0 < n <= 65536");
   if (nstore == 0 || nstore > 0xffffffffull) return fail(ctx, LCV_EINVAL, "lcv_debug_fold_stores: need 0 < nstore < 2^32");
-  FoldSegs& g = ctx->segs;
-  LCV_TRY(fold_segments(ctx, "lcv_debug_fold_stores", store_index, n, nstore, in, g));
-  std::vector<uint32_t> next;
-  std::vector<uint8_t> res;
-  try {
-    next.resize(nstore);
-    res.resize((size_t)FOLD_RESULT_BYTES * g.nseg);
-  } catch (...) {
-    return fail(ctx, LCV_ENOMEM, "lcv_debug_fold_stores: out of host memory");
-  }
-  for (uint64_t s = 0; s < nstore; ++s) next[s] = next_known[s] ? 0u : (uint32_t)STORE_NEXT_UNKNOWN;
-  const size_t ng = g.nseg;
-  const void* src[8] = {rank, verdict, store_finalized_slot, next.data(), g.store.data(), g.off.data(), g.row.data(), g.in.data()};
-  const size_t bytes[8] = {rank_index((size_t)n), (size_t)n, 8 * (size_t)nstore, 4 * (size_t)nstore, 4 * ng, 4 * (ng + 1),
-                           4 * (size_t)n, sizeof(FoldState) * ng};
-  size_t off[9], total = 0;
-  for (int k = 0; k < 9; ++k) {
-    off[k] = total;
-    total += ((k < 8 ? bytes[k] : (size_t)FOLD_RESULT_BYTES * ng) + 255) & ~(size_t)255;
-  }
-  void* mem = nullptr;
-  be_set_slot(ctx, 0);
-  LCV_TRY(be_alloc(ctx, &mem, total));
-  uint8_t* m = (uint8_t*)mem;
-  Work W = Work{};
-  W.cap = (uint32_t)n;
-  W.rank = m + off[0];
-  W.verdict = m + off[1];
-  const StoreDev S = {(const uint64_t*)(m + off[2]), nullptr, (const uint32_t*)(m + off[3]), (uint32_t)nstore};
-  const FoldSegDev G = {(const uint32_t*)(m + off[4]), (const uint32_t*)(m + off[5]), (const uint32_t*)(m + off[6]),
-                        m + off[7], m + off[8]};
-  be_reset_timings(ctx);
-  auto body = [&]() -> int {
+  return guarded(ctx, "lcv_debug_fold_stores", [&]() -> int {
+    FoldSegs& g = ctx->segs;
+    LCV_TRY(fold_segments(ctx, "lcv_debug_fold_stores", store_index, n, nstore, in, g));
+    std::vector<uint32_t> next(nstore);
+    std::vector<uint8_t> res((size_t)FOLD_RESULT_BYTES * g.nseg);
+    for (uint64_t s = 0; s < nstore; ++s) next[s] = next_known[s] ? 0u : (uint32_t)STORE_NEXT_UNKNOWN;
+    const size_t ng = g.nseg;
+    const void* src[8] = {rank, verdict, store_finalized_slot, next.data(), g.store.data(), g.off.data(), g.row.data(), g.in.data()};
+    const size_t bytes[8] = {rank_index((size_t)n), (size_t)n, 8 * (size_t)nstore, 4 * (size_t)nstore, 4 * ng, 4 * (ng + 1),
+                             4 * (size_t)n, sizeof(FoldState) * ng};
+    size_t off[9];
+    Layout l;
+    for (int k = 0; k < 9; ++k) off[k] = l.take(k < 8 ? bytes[k] : (size_t)FOLD_RESULT_BYTES * ng);
+    Scratch mem(ctx);
+    be_set_slot(ctx, 0);
+    LCV_TRY(mem.alloc(l.total()));
+    uint8_t* m = mem.p;
+    Work W = Work{};
+    W.cap = (uint32_t)n;
+    W.rank = m + off[0];
+    W.verdict = m + off[1];
+    const StoreDev S = {(const uint64_t*)(m + off[2]), nullptr, (const uint32_t*)(m + off[3]), (uint32_t)nstore};
+    const FoldSegDev G = {(const uint32_t*)(m + off[4]), (const uint32_t*)(m + off[5]), (const uint32_t*)(m + off[6]),
+                          m + off[7], m + off[8]};
+    be_reset_timings(ctx);
     for (int k = 0; k < 8; ++k) LCV_TRY(be_h2d(ctx, m + off[k], src[k], bytes[k]));
     LCV_TRY(fold_seg_stage(ctx, W, S, G, g.nseg));
     LCV_TRY(be_d2h(ctx, res.data(), G.out, res.size()));
-    return be_sync(ctx);
-  };
-  const int rc = body();
-  be_free(ctx, mem);  // (waits for the streams)
-  if (rc != LCV_OK) return rc;
-  be_collect_timings(ctx);
-  fold_seg_scatter(out, res.data(), g.store.data(), g.nseg);
-  return LCV_OK;
+    LCV_TRY(be_sync(ctx));
+    mem.release();  // (waits for the streams)
+    be_collect_timings(ctx);
+    fold_seg_scatter(out, res.data(), g.store.data(), g.nseg);
+    return LCV_OK;
+  });
 }
 
 // The communication buffer never blocks a collective call: lcv_comm_init sizes it for every slot's largest
@@ -2004,15 +2041,17 @@ int lcv_debug_fold_stores(lcv_ctx* ctx, const uint8_t* rank, const uint8_t* verd
 // (the bounded be_comm_wait comes later).  Outgrown buffers are retired and freed by lcv_destroy; growth is
 // geometric, so a context retires O(log n) of them.
 static size_t comm_buf_bytes_for(size_t nranks) { return kChunk * (nranks + 1) * LCV_SLOTS; }
-static int ensure_comm_buf(lcv_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->comm_buf_cap && ctx->comm_buf) return LCV_OK;
-  if (bytes < 2 * ctx->comm_buf_cap) bytes = 2 * ctx->comm_buf_cap;
-  void* p = nullptr;
-  LCV_TRY(be_alloc(ctx, &p, bytes));
-  if (ctx->comm_buf) ctx->comm_retired.push_back(ctx->comm_buf);
-  ctx->comm_buf = (uint8_t*)p;
-  ctx->comm_buf_cap = bytes;
-  return LCV_OK;
+static int ensure_comm_buf(lcv_ctx* ctx, const char* who, size_t bytes) {
+  if (ctx->comm_buf.p && bytes <= ctx->comm_buf.cap) return LCV_OK;
+  bytes = std::max(bytes, 2 * ctx->comm_buf.cap);  // doubles
+  return guarded(ctx, who, [&]() -> int {
+    ctx->comm_retired.reserve(ctx->comm_retired.size() + 1);  // (may throw: ahead of the allocation)
+    DevBuf fresh;
+    LCV_TRY(fresh.grow(ctx, bytes));
+    if (ctx->comm_buf.p) ctx->comm_retired.push_back(ctx->comm_buf);  // retired, not freed
+    ctx->comm_buf = fresh;
+    return LCV_OK;
+  });
 }
 
 // ---- multi-GPU: updates are sharded by contiguous index range, one process (and context) per GPU; the
@@ -2027,7 +2066,7 @@ int lcv_comm_init(lcv_ctx* ctx, int nranks, int rank, const uint8_t* id128) {
   if (ctx->comm_ready) return fail(ctx, LCV_ESTATE, "lcv_comm_init: communicator already initialised");
   LCV_TRY(be_comm_init(ctx, nranks, rank, id128));
   // every per-slot all-gather of up to a chunk per rank fits from the start (ensure_comm_buf)
-  LCV_TRY(ensure_comm_buf(ctx, comm_buf_bytes_for((size_t)nranks)));
+  LCV_TRY(ensure_comm_buf(ctx, "lcv_comm_init", comm_buf_bytes_for((size_t)nranks)));
   ctx->comm_ready = true;
   ctx->comm_nranks = nranks;
   ctx->comm_rank = rank;
@@ -2108,16 +2147,16 @@ int lcv_comm_destroy(lcv_ctx* ctx) {
 int lcv_slot_allgather(lcv_ctx* ctx, int slot, uint64_t n, uint64_t per_rank, uint8_t* verdict_all_out) {
   if (!ctx || !verdict_all_out || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_slot_allgather: bad arguments");
   LCV_TRY(comm_usable(ctx, "lcv_slot_allgather"));
-  if (n > per_rank || n > ctx->work_cap[slot] || (n && !ctx->work_mem[slot]))
+  if (n > per_rank || n > ctx->slot[slot].work.cap)
     return fail(ctx, LCV_EINVAL, "lcv_slot_allgather: n larger than per_rank or than the slot's batch");
   const size_t R = (size_t)ctx->comm_nranks, region = per_rank * (R + 1);
-  LCV_TRY(ensure_comm_buf(ctx, region * LCV_SLOTS));
-  uint8_t* send = ctx->comm_buf + region * (size_t)slot;
+  LCV_TRY(ensure_comm_buf(ctx, "lcv_slot_allgather", region * LCV_SLOTS));
+  uint8_t* send = ctx->comm_buf.p + region * (size_t)slot;
   uint8_t* recv = send + per_rank;
-  ctx->hslot[slot].staged = false;  // this slot's results leave through the all-gather
+  ctx->slot[slot].host.staged = false;  // this slot's results leave through the all-gather
   be_set_slot(ctx, slot);
   int rc = be_memset(ctx, send, 0, per_rank);
-  if (rc == LCV_OK && n) rc = be_d2d(ctx, send, ctx->Wslot[slot].verdict, n);
+  if (rc == LCV_OK && n) rc = be_d2d(ctx, send, ctx->slot[slot].W.verdict, n);
   if (rc == LCV_OK) rc = be_comm_allgather(ctx, send, recv, per_rank);
   // bounded: a dead peer fails the call instead of hanging it.  The wait comes BEFORE the copy into the
   // caller's (pageable) memory: such a copy blocks the host until the stream reaches it, i.e. forever
@@ -2135,9 +2174,9 @@ int lcv_validate_sharded(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
   LCV_TRY(comm_usable(ctx, "lcv_validate_sharded"));
   if (db->n > per_rank) return fail(ctx, LCV_EINVAL, "lcv_validate_sharded: shard larger than per_rank");
   const size_t R = (size_t)ctx->comm_nranks;
-  LCV_TRY(ensure_comm_buf(ctx, per_rank * (R + 1)));
-  uint8_t* send = ctx->comm_buf;
-  uint8_t* recv = ctx->comm_buf + per_rank;
+  LCV_TRY(ensure_comm_buf(ctx, "lcv_validate_sharded", per_rank * (R + 1)));
+  uint8_t* send = ctx->comm_buf.p;
+  uint8_t* recv = send + per_rank;
   // only the padding tail is zeroed: the verdicts [0, n) are written by the chunks' own slot streams
   // (validate_rotating), which nothing orders after a memset on this stream
   LCV_TRY(be_memset(ctx, send + db->n, 0, per_rank - db->n));
@@ -2186,18 +2225,22 @@ static const uint8_t* field_addr(const void* obj, const Field& f, size_t cap, si
   return slot_get(obj, f.slot) + f.esize * field_index(f, cap, pool_cap, i, r);
 }
 
+static int work_check(lcv_ctx* ctx, uint64_t cap, uint64_t slice, int nslots);
 extern "C" int lcv_debug_work_check(lcv_ctx* ctx, uint64_t cap, uint64_t slice, int nslots) {
   if (!ctx || cap == 0 || slice == 0 || nslots < 1 || nslots > LCV_SLOTS)
     return fail(ctx, LCV_EINVAL, "lcv_debug_work_check: cap, slice > 0, 1 <= nslots <= 8");
+  return guarded(ctx, "lcv_debug_work_check", [&] { return work_check(ctx, cap, slice, nslots); });
+}
+static int work_check(lcv_ctx* ctx, uint64_t cap, uint64_t slice, int nslots) {
   for (int s = 0; s < nslots; ++s) {
     LCV_TRY(ensure_work(ctx, cap, 5, s));  // a committee pool of 5
     LCV_TRY(ensure_dedup(ctx, cap, s));    // and the slot's deduplication scratch (lcv_set_dedup), checked in (2)
     LCV_TRY(ensure_rlc(ctx, s));           // and its batch-verification scratch (lcv_set_rlc), likewise
   }
-  ctx->W = ctx->Wslot[0];
+  ctx->W = ctx->slot[0].W;
   // (1) slices: item j of work_view(W, b) is item b + j of W, element for element, in every per-item field
   for (int s = 0; s < nslots; ++s) {
-    const Work& W = ctx->Wslot[s];
+    const Work& W = ctx->slot[s].W;
     const size_t C = W.cap, Pc = W.pool_cap;
     for (size_t b = 0; b < C; b += slice) {
       const Work V = work_view(W, b);
@@ -2229,10 +2272,10 @@ extern "C" int lcv_debug_work_check(lcv_ctx* ctx, uint64_t cap, uint64_t slice, 
     rg.push_back({lo, hi, s, std::string(prefix) + f.name});
   };
   for (int s = 0; s < nslots; ++s) {
-    const Work& W = ctx->Wslot[s];
+    const Work& W = ctx->slot[s].W;
     for (const Field& f : kWorkFields) ranges(s, &W, f, "", W.cap, W.pool_cap);
-    for (const Field& f : kDedupFields) ranges(s, &ctx->Dslot[s], f, "dedup_", W.cap, 0);
-    for (const Field& f : kRlcFields) ranges(s, &ctx->Rslot[s], f, "rlc_", W.cap, 0);
+    for (const Field& f : kDedupFields) ranges(s, &ctx->slot[s].D, f, "dedup_", W.cap, 0);
+    for (const Field& f : kRlcFields) ranges(s, &ctx->slot[s].R, f, "rlc_", W.cap, 0);
   }
   for (size_t a = 0; a < rg.size(); ++a)
     for (size_t b = a + 1; b < rg.size(); ++b)
@@ -2301,15 +2344,15 @@ int lcv_set_rlc(lcv_ctx* ctx, uint32_t group, const uint8_t* seed32) {
 // blocking read each, here and not on the asynchronous path
 int lcv_last_rlc(lcv_ctx* ctx, int slot, uint64_t* groups, uint64_t* retried_rows) {
   if (!ctx || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_last_rlc: slot must be 0..7");
-  if (groups) *groups = ctx->rl_groups[slot];
+  if (groups) *groups = ctx->slot[slot].rl_groups;
   if (!retried_rows) return LCV_OK;
   uint64_t total = 0;
   int rc = LCV_OK;
   for (int s = 0; s < LCV_SLOTS && rc == LCV_OK; ++s) {
-    if (!(ctx->rl_used[slot] & (1u << s)) || !ctx->rlc_mem[s]) continue;
+    if (!(ctx->slot[slot].rl_used & (1u << s)) || !ctx->slot[s].rlc.p) continue;
     uint32_t c = 0;
     be_set_slot(ctx, s);
-    rc = be_d2h(ctx, &c, ctx->Rslot[s].cnt + 1, sizeof(c));
+    rc = be_d2h(ctx, &c, ctx->slot[s].R.cnt + 1, sizeof(c));
     if (rc == LCV_OK) rc = be_sync_slot(ctx);
     total += c;
   }
@@ -2329,8 +2372,8 @@ int lcv_set_dedup(lcv_ctx* ctx, int on) {
 
 int lcv_last_dedup(lcv_ctx* ctx, int slot, uint64_t* rows, uint64_t* items) {
   if (!ctx || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_last_dedup: slot must be 0..7");
-  if (rows) *rows = ctx->dd_rows[slot];
-  if (items) *items = ctx->dd_items[slot];
+  if (rows) *rows = ctx->slot[slot].dd_rows;
+  if (items) *items = ctx->slot[slot].dd_items;
   return LCV_OK;
 }
 
@@ -2369,7 +2412,8 @@ int lcv_last_timings(lcv_ctx* ctx, float* ms_out, int max_stages, int* nstages) 
 
 // ---- FastAggregateVerify
 // agg_items (> n only for one FastAggregateVerify call over > 512 keys, n == 1): rows of cid / bits
-// describe agg_items 512-key slices whose aggregates are summed into item 0
+// describe agg_items 512-key slices whose aggregates are summed into item 0.  Allocates host memory (the cached
+// table's bytes): within the boundary (guarded)
 static int fav_impl(lcv_ctx* ctx, const uint8_t* committees, uint64_t ncomm, const uint32_t* cid, const uint8_t* bits,
                     const uint8_t* msg, const uint8_t* sig, uint64_t n, uint8_t* verdict_out, uint8_t* agg_out,
                     uint8_t* agg_status_out, uint64_t agg_items = 0, uint64_t msg_len = 32) {
@@ -2383,26 +2427,24 @@ static int fav_impl(lcv_ctx* ctx, const uint8_t* committees, uint64_t ncomm, con
   // the decoded, KeyValidated and summed tables of the previous call are reused when this call passes
   // byte-identical tables (the reference's usage: one committee signs a whole period's updates)
   const size_t table_bytes = ncomm * 512 * 48;
-  const bool cached = ctx->adhoc.raw && ctx->adhoc.ncomm == ncomm && ctx->adhoc_src.size() == table_bytes &&
+  const bool cached = ctx->adhoc.raw.p && ctx->adhoc.ncomm == ncomm && ctx->adhoc_src.size() == table_bytes &&
                       memcmp(ctx->adhoc_src.data(), committees, table_bytes) == 0;
   if (!cached) {
     ctx->adhoc_src.clear();
     LCV_TRY(ensure_committees(ctx, ctx->adhoc, ncomm, 512 * 48));
-    LCV_TRY(be_h2d(ctx, ctx->adhoc.raw, committees, table_bytes));
+    LCV_TRY(be_h2d(ctx, ctx->adhoc.raw.p, committees, table_bytes));
     LCV_TRY(build_committees(ctx, ctx->adhoc));
     ctx->adhoc_src.assign(committees, committees + table_bytes);
   }
   CommitteeDev C = committee_view(ctx->adhoc, nullptr);
-  void* tmp = nullptr;
-  const size_t tb = rows * (K_BITS + K_SIG + 32);
-  LCV_TRY(be_alloc(ctx, &tmp, tb));
-  uint8_t* t = (uint8_t*)tmp;
+  Scratch mtmp(ctx), tmp(ctx);  // mtmp: a message that is not 32 bytes (n == 1): its bytes, hashed into b0 on device
+  LCV_TRY(tmp.alloc(rows * (K_BITS + K_SIG + 32)));
+  uint8_t* t = tmp.p;
   int rc = be_h2d(ctx, t, bits, K_BITS * rows);
   if (rc == LCV_OK && sig) rc = be_h2d(ctx, t + K_BITS * rows, sig, K_SIG * n);
-  void* mtmp = nullptr;  // a message that is not 32 bytes (n == 1): its bytes, hashed into b0 on device
   if (rc == LCV_OK && msg && msg_len != 32) {
-    rc = be_alloc(ctx, &mtmp, msg_len ? msg_len : 1);
-    if (rc == LCV_OK) rc = be_h2d(ctx, mtmp, msg, msg_len);
+    rc = mtmp.alloc(msg_len ? msg_len : 1);
+    if (rc == LCV_OK) rc = be_h2d(ctx, mtmp.p, msg, msg_len);
   } else if (rc == LCV_OK && msg) {
     rc = be_h2d(ctx, t + (K_BITS + K_SIG) * rows, msg, 32 * n);
   }
@@ -2414,8 +2456,8 @@ static int fav_impl(lcv_ctx* ctx, const uint8_t* committees, uint64_t ncomm, con
   B.sig = t + 64 * rows;
   B.n = (uint32_t)n;
   if (rc == LCV_OK && verdict_out) {
-    if (mtmp) {
-      rc = be_launch(ctx, F_msg_import_b0{(const uint8_t*)mtmp, msg_len, ctx->W}, 1);
+    if (mtmp.p) {
+      rc = be_launch(ctx, F_msg_import_b0{mtmp.p, msg_len, ctx->W}, 1);
       ctx->W.msg_b0 = 1;
     } else {
       rc = be_launch(ctx, F_msg_import{t + (K_BITS + K_SIG) * rows, ctx->W}, (uint32_t)n);
@@ -2430,8 +2472,8 @@ static int fav_impl(lcv_ctx* ctx, const uint8_t* committees, uint64_t ncomm, con
     if (rc == LCV_OK) rc = be_d2h(ctx, agg_status_out, ctx->W.agg_status, n);
   }
   if (rc == LCV_OK) rc = be_sync(ctx);
-  be_free(ctx, tmp);
-  if (mtmp) be_free(ctx, mtmp);
+  tmp.release();
+  mtmp.release();
   be_collect_timings(ctx);
   return rc;
 }
@@ -2440,7 +2482,9 @@ int lcv_fast_aggregate_verify_batch(lcv_ctx* ctx, const uint8_t* committees, uin
                                     const uint8_t* bits64, const uint8_t* msg32, const uint8_t* sig96, uint64_t n,
                                     uint8_t* verdict_out) {
   if (!msg32 || !sig96 || !verdict_out) return fail(ctx, LCV_EINVAL, "fast_aggregate_verify_batch: null argument");
-  return fav_impl(ctx, committees, ncomm, cid, bits64, msg32, sig96, n, verdict_out, nullptr, nullptr);
+  return guarded(ctx, "fast_aggregate_verify_batch", [&] {
+    return fav_impl(ctx, committees, ncomm, cid, bits64, msg32, sig96, n, verdict_out, nullptr, nullptr);
+  });
 }
 
 int lcv_fast_aggregate_verify(lcv_ctx* ctx, const uint8_t* pks, uint64_t npk, const uint8_t* msg, uint64_t msg_len,
@@ -2455,50 +2499,53 @@ int lcv_fast_aggregate_verify(lcv_ctx* ctx, const uint8_t* pks, uint64_t npk, co
   // select its keys, and the slices' aggregates are summed on the device (item_agg_fold)
   const uint64_t m = (npk + 511) / 512;
   if (m > kChunk) return fail(ctx, LCV_EINVAL, "fast_aggregate_verify: too many pubkeys");
-  std::vector<uint8_t> table(m * 512 * 48, 0), bits(m * 64, 0);
-  std::vector<uint32_t> cid(m);
-  memcpy(table.data(), pks, npk * 48);
-  for (uint64_t j = 0; j < npk; ++j) bits[j / 8] |= (uint8_t)(1u << (j % 8));
-  for (uint64_t k = 0; k < m; ++k) cid[k] = (uint32_t)k;
-  uint8_t v = 0;
-  LCV_TRY(fav_impl(ctx, table.data(), m, cid.data(), bits.data(), msg32, sig96, 1, &v, nullptr, nullptr, m > 1 ? m : 0,
-                   msg_len));
-  *result = v ? 1 : 0;
-  return LCV_OK;
+  return guarded(ctx, "fast_aggregate_verify", [&]() -> int {
+    std::vector<uint8_t> table(m * 512 * 48, 0), bits(m * 64, 0);
+    std::vector<uint32_t> cid(m);
+    memcpy(table.data(), pks, npk * 48);
+    for (uint64_t j = 0; j < npk; ++j) bits[j / 8] |= (uint8_t)(1u << (j % 8));
+    for (uint64_t k = 0; k < m; ++k) cid[k] = (uint32_t)k;
+    uint8_t v = 0;
+    LCV_TRY(fav_impl(ctx, table.data(), m, cid.data(), bits.data(), msg32, sig96, 1, &v, nullptr, nullptr, m > 1 ? m : 0,
+                     msg_len));
+    *result = v ? 1 : 0;
+    return LCV_OK;
+  });
 }
 
 int lcv_debug_aggregate(lcv_ctx* ctx, const uint8_t* committees, uint64_t ncomm, const uint32_t* cid,
                         const uint8_t* bits64, uint64_t n, uint8_t* out96, uint8_t* status) {
   if (!out96 || !status) return fail(ctx, LCV_EINVAL, "debug_aggregate: null argument");
-  return fav_impl(ctx, committees, ncomm, cid, bits64, nullptr, nullptr, n, nullptr, out96, status);
+  return guarded(ctx, "debug_aggregate", [&] {
+    return fav_impl(ctx, committees, ncomm, cid, bits64, nullptr, nullptr, n, nullptr, out96, status);
+  });
 }
 
 }  // extern "C"
 
 // ---- generic "bytes in -> kernel -> bytes out" helper
-template <class MakeF>
-static int simple_call(lcv_ctx* ctx, uint64_t n, const std::vector<std::pair<const void*, size_t>>& ins,
-                       const std::vector<std::pair<void*, size_t>>& outs, MakeF make) {
+// (the boundary: the offsets and pointers are host vectors)
+typedef std::initializer_list<std::pair<const void*, size_t>> SimpleIns;
+typedef std::initializer_list<std::pair<void*, size_t>> SimpleOuts;
+template <class MakeF> static int simple_call(lcv_ctx* ctx, uint64_t n, SimpleIns ins, SimpleOuts outs, MakeF make) {
   if (!ctx) return LCV_EINVAL;
   if (n == 0) return LCV_OK;
   if (n > 0xffffffffull) return fail(ctx, LCV_EINVAL, "n too large");
-  size_t total = 0;
-  std::vector<size_t> offs;
-  for (auto& p : ins) { offs.push_back(total); total += (p.second + 255) & ~(size_t)255; }
-  for (auto& p : outs) { offs.push_back(total); total += (p.second + 255) & ~(size_t)255; }
-  void* mem = nullptr;
-  LCV_TRY(be_alloc(ctx, &mem, total ? total : 256));
-  uint8_t* m = (uint8_t*)mem;
-  int rc = LCV_OK;
-  for (size_t k = 0; k < ins.size() && rc == LCV_OK; ++k) rc = be_h2d(ctx, m + offs[k], ins[k].first, ins[k].second);
-  std::vector<uint8_t*> dptr;
-  for (size_t k = 0; k < ins.size() + outs.size(); ++k) dptr.push_back(m + offs[k]);
-  if (rc == LCV_OK) rc = make(dptr);
-  for (size_t k = 0; k < outs.size() && rc == LCV_OK; ++k)
-    rc = be_d2h(ctx, outs[k].first, m + offs[ins.size() + k], outs[k].second);
-  if (rc == LCV_OK) rc = be_sync(ctx);
-  be_free(ctx, mem);
-  return rc;
+  return guarded(ctx, "simple_call", [&]() -> int {
+    Layout l;
+    std::vector<size_t> offs;
+    for (auto& p : ins) offs.push_back(l.take(p.second));
+    for (auto& p : outs) offs.push_back(l.take(p.second));
+    Scratch mem(ctx);
+    LCV_TRY(mem.alloc(l.total() ? l.total() : 256));
+    std::vector<uint8_t*> dptr;
+    for (size_t off : offs) dptr.push_back(mem.p + off);
+    size_t k = 0;
+    for (auto& p : ins) LCV_TRY(be_h2d(ctx, dptr[k++], p.first, p.second));
+    LCV_TRY(make(dptr));
+    for (auto& p : outs) LCV_TRY(be_d2h(ctx, p.first, dptr[k++], p.second));
+    return be_sync(ctx);  // (then the scratch's free)
+  });
 }
 
 extern "C" {
@@ -2506,8 +2553,8 @@ extern "C" {
 int lcv_merkle_branch_batch(lcv_ctx* ctx, const uint8_t* leaf32, const uint8_t* branch, uint32_t depth, uint64_t index,
                             const uint8_t* root32, uint64_t n, uint8_t* out) {
   if (!ctx || !leaf32 || !root32 || !out || (depth && !branch) || depth > 64) return fail(ctx, LCV_EINVAL, "merkle: bad arguments");
-  std::vector<uint8_t> dummy(32, 0);
-  const uint8_t* br = depth ? branch : dummy.data();
+  static const uint8_t dummy[32] = {};
+  const uint8_t* br = depth ? branch : dummy;
   const size_t brb = depth ? (size_t)32 * depth * n : 32;
   return simple_call(ctx, n, {{leaf32, 32 * n}, {br, brb}, {root32, 32 * n}}, {{out, n}}, [&](std::vector<uint8_t*>& d) {
     return be_launch(ctx, F_merkle{d[0], d[1], d[2], d[3], depth, index}, (uint32_t)n);
@@ -2634,7 +2681,8 @@ int lcv_debug_rlc_scale(lcv_ctx* ctx, const uint8_t* p96, const uint64_t* r_u64,
 // One device allocation per call: the view tables, the cases, the stage-0 / stage-1 scratch rows, the reasons (and
 // what a caller adds: `extra`).  Every index a kernel follows is checked on the host before anything is launched.
 struct ProdRun {
-  void* mem = nullptr;
+  Scratch mem;
+  explicit ProdRun(lcv_ctx* ctx) : mem(ctx) {}
   uint8_t* extra = nullptr;  // the caller's part of the allocation
   uint8_t* reason = nullptr; // [n]
   ProdStates S; ProdBlocks K; ProdCases C; ProdScratch X;
@@ -2678,20 +2726,15 @@ static int prod_views(lcv_ctx* ctx, const lcv_state_views* s, uint64_t ns, const
                          b->signature, b->execution, b->exec_kind, b->body_roots};
   const size_t bytes[NV] = {8 * ns, (size_t)K_BEACON * ns, 8 * ns, 32 * ns, 32 * PROD_STATE_FIELDS * ns, 4 * ns, 4 * ns, 8 * nb, 8 * nb,
                             32 * nb, 32 * nb, 64 * nb, 96 * nb, (size_t)K_EXEC * nb, nb, 32 * PROD_BODY_FIELDS * nb};
-  auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  size_t off[NV], total = 0;
-  for (int k = 0; k < NV; ++k) { off[k] = total; total += pad(bytes[k]); }
-  size_t ixoff[8];
-  for (int k = 0; k < nix; ++k) { ixoff[k] = total; total += pad(4 * n); }
-  const size_t o_pool = total; total += pool ? 0 : pad((size_t)K_SC * ncomm);
-  const size_t o_root = total; total += pad(32 * ncomm);
-  const size_t o_flag = total; total += pad(ncomm);
-  const size_t o_blk = total; total += pad((size_t)PROD_BLK_ROW * nb);
-  const size_t o_st = total; total += pad((size_t)PROD_ST_ROW * ns);
-  const size_t o_reason = total; total += pad(n);
-  const size_t o_extra = total; total += pad(extra_bytes);
-  LCV_TRY(be_alloc(ctx, &R.mem, total));
-  uint8_t* m = (uint8_t*)R.mem;
+  Layout l;
+  size_t off[NV], ixoff[8];
+  for (int k = 0; k < NV; ++k) off[k] = l.take(bytes[k]);
+  for (int k = 0; k < nix; ++k) ixoff[k] = l.take(4 * n);
+  const size_t o_pool = l.take(pool ? 0 : (size_t)K_SC * ncomm), o_root = l.take(32 * ncomm), o_flag = l.take(ncomm);
+  const size_t o_blk = l.take((size_t)PROD_BLK_ROW * nb), o_st = l.take((size_t)PROD_ST_ROW * ns);
+  const size_t o_reason = l.take(n), o_extra = l.take(extra_bytes);
+  LCV_TRY(R.mem.alloc(l.total()));
+  uint8_t* m = R.mem.p;
   for (int k = 0; k < NV; ++k) LCV_TRY(be_h2d(ctx, m + off[k], src[k], bytes[k]));
   for (int k = 0; k < nix; ++k) LCV_TRY(be_h2d(ctx, m + ixoff[k], ix[k], 4 * n));
   if (!pool) {
@@ -2776,34 +2819,25 @@ int lcv_create_updates_resident(lcv_ctx* ctx, const lcv_state_views* states, uin
   // the batch: lcv_batch_upload's layout, the pool = the committee rows and one all-zero row
   BatchCols c;
   batch_layout(c, n, ncomm + 1, false, 0);
-  lcv_dbatch* db = new (std::nothrow) lcv_dbatch();
-  if (!db) return LCV_ENOMEM;
+  NewBatch nb_(ctx);
   be_set_slot(ctx, 0);
-  int rc = be_alloc(ctx, &db->mem, c.total);
-  if (rc != LCV_OK) { delete db; return rc; }
-  uint8_t* m = (uint8_t*)db->mem;
-  bind_batch(db, m, c);
-  ProdRun R;
+  LCV_TRY(batch_new(ctx, c, nb_));
+  lcv_dbatch* db = nb_.db;
+  uint8_t* pool = db->mem.p + c.off[COL_NSC_POOL];
+  ProdRun R(ctx);  // (its scratch is freed, waiting for the streams, ahead of an abandoned batch)
   be_reset_timings(ctx);
-  auto body = [&]() -> int {
-    LCV_TRY(be_h2d(ctx, m + c.off[COL_NSC_POOL], committees, (size_t)K_SC * ncomm));
-    LCV_TRY(be_memset(ctx, m + c.off[COL_NSC_POOL] + (size_t)K_SC * ncomm, 0, K_SC));
-    const void* ix[5] = {cases->state, cases->block, cases->attested_state, cases->attested_block, cases->finalized_block};
-    LCV_TRY(prod_views(ctx, states, ns, blocks, nb, committees, db->B.nsc_pool, ncomm, ix, 5, n, 0, R));
-    LCV_TRY(stage(ctx, ST_PRODUCE_ROWS, [&] {
-      return be_launch_team(ctx, F_prod_rows{R.S, R.K, R.C, R.X, prod_out(db->B), ctx->cfg, (uint32_t)kind,
-                                             (uint32_t)ncomm, R.reason}, (uint32_t)n);
-    }));
-    LCV_TRY(be_d2h(ctx, reason_out, R.reason, n));
-    LCV_TRY(be_sync(ctx));
-    be_collect_timings(ctx);
-    return LCV_OK;
-  };
-  rc = body();
-  if (R.mem) be_free(ctx, R.mem);  // (waits for the streams)
-  if (rc != LCV_OK) { be_free(ctx, db->mem); delete db; return rc; }
-  *out = db;
-  return LCV_OK;
+  LCV_TRY(be_h2d(ctx, pool, committees, (size_t)K_SC * ncomm));
+  LCV_TRY(be_memset(ctx, pool + (size_t)K_SC * ncomm, 0, K_SC));
+  const void* ix[5] = {cases->state, cases->block, cases->attested_state, cases->attested_block, cases->finalized_block};
+  LCV_TRY(prod_views(ctx, states, ns, blocks, nb, committees, db->B.nsc_pool, ncomm, ix, 5, n, 0, R));
+  LCV_TRY(stage(ctx, ST_PRODUCE_ROWS, [&] {
+    return be_launch_team(ctx, F_prod_rows{R.S, R.K, R.C, R.X, prod_out(db->B), ctx->cfg, (uint32_t)kind,
+                                           (uint32_t)ncomm, R.reason}, (uint32_t)n);
+  }));
+  LCV_TRY(be_d2h(ctx, reason_out, R.reason, n));
+  LCV_TRY(be_sync(ctx));
+  be_collect_timings(ctx);
+  return nb_.hand_out(out);
 }
 
 int lcv_batch_download(lcv_ctx* ctx, lcv_dbatch* b, const uint32_t* rows, uint64_t nrows, const lcv_update_batch* out) {
@@ -2821,19 +2855,14 @@ int lcv_batch_download(lcv_ctx* ctx, lcv_dbatch* b, const uint32_t* rows, uint64
   BatchCols c;
   batch_layout(c, nrows, 0, false, 0);
   const size_t o_rows = c.total;
-  void* mem = nullptr;
-  LCV_TRY(be_alloc(ctx, &mem, c.total + 4 * nrows));
+  Scratch mem(ctx);
+  LCV_TRY(mem.alloc(c.total + 4 * nrows));
   lcv_dbatch t;
-  bind_batch(&t, (uint8_t*)mem, c);
-  auto body = [&]() -> int {
-    LCV_TRY(be_h2d(ctx, (uint8_t*)mem + o_rows, rows, 4 * nrows));
-    LCV_TRY(be_launch_team(ctx, F_prod_pick{b->B, (const uint32_t*)((uint8_t*)mem + o_rows), prod_out(t.B)}, (uint32_t)nrows));
-    LCV_TRY(prod_copy_out(ctx, t.B, nrows, out, false, 0));
-    return be_sync(ctx);
-  };
-  const int rc = body();
-  be_free(ctx, mem);
-  return rc;
+  bind_batch(&t, mem.p, c);
+  LCV_TRY(be_h2d(ctx, mem.p + o_rows, rows, 4 * nrows));
+  LCV_TRY(be_launch_team(ctx, F_prod_pick{b->B, (const uint32_t*)(mem.p + o_rows), prod_out(t.B)}, (uint32_t)nrows));
+  LCV_TRY(prod_copy_out(ctx, t.B, nrows, out, false, 0));
+  return be_sync(ctx);
 }
 
 int lcv_create_updates(lcv_ctx* ctx, const lcv_state_views* states, uint64_t ns, const lcv_block_views* blocks,
@@ -2852,24 +2881,19 @@ int lcv_create_updates(lcv_ctx* ctx, const lcv_state_views* states, uint64_t ns,
 int lcv_rank_resident(lcv_ctx* ctx, lcv_dbatch* b, uint8_t* rank_out) {
   if (!ctx || !b || !rank_out) return fail(ctx, LCV_EINVAL, "lcv_rank_resident: null argument");
   if (b->n == 0) return LCV_OK;
-  void* mem = nullptr;
+  Scratch mem(ctx);
   be_set_slot(ctx, 0);
-  LCV_TRY(be_alloc(ctx, &mem, rank_index(b->n)));
+  LCV_TRY(mem.alloc(rank_index(b->n)));
   Work W = Work{};
-  W.rank = (uint8_t*)mem;
+  W.rank = mem.p;
   Params P = {};
   P.cfg = ctx->cfg;
   be_reset_timings(ctx);
-  auto body = [&]() -> int {
-    LCV_TRY(rank_stage(ctx, b->B, P, W, (uint32_t)b->n));
-    LCV_TRY(be_d2h(ctx, rank_out, W.rank, rank_index(b->n)));
-    LCV_TRY(be_sync(ctx));
-    be_collect_timings(ctx);
-    return LCV_OK;
-  };
-  const int rc = body();
-  be_free(ctx, mem);
-  return rc;
+  LCV_TRY(rank_stage(ctx, b->B, P, W, (uint32_t)b->n));
+  LCV_TRY(be_d2h(ctx, rank_out, W.rank, rank_index(b->n)));
+  LCV_TRY(be_sync(ctx));
+  be_collect_timings(ctx);
+  return LCV_OK;
 }
 
 int lcv_create_bootstraps(lcv_ctx* ctx, const lcv_state_views* states, uint64_t ns, const lcv_block_views* blocks,
@@ -2887,29 +2911,25 @@ int lcv_create_bootstraps(lcv_ctx* ctx, const lcv_state_views* states, uint64_t 
   LCV_TRY(prod_check_index(ctx, who, "state_idx", state_idx, n, ns));
   LCV_TRY(prod_check_index(ctx, who, "block_idx", block_idx, n, nb));
   const size_t width[5] = {K_BEACON, K_EXEC, K_EXEC_BRANCH, 4, K_NSC_BRANCH};
-  size_t off[5], extra = 0;
-  for (int k = 0; k < 5; ++k) { off[k] = extra; extra += (width[k] * n + 255) & ~(size_t)255; }
-  ProdRun R;
+  size_t off[5];
+  Layout extra;
+  for (int k = 0; k < 5; ++k) off[k] = extra.take(width[k] * n);
+  ProdRun R(ctx);
   be_set_slot(ctx, 0);
   be_reset_timings(ctx);
-  auto body = [&]() -> int {
-    const void* ix[2] = {state_idx, block_idx};
-    LCV_TRY(prod_views(ctx, states, ns, blocks, nb, committees, nullptr, ncomm, ix, 2, n, extra, R));
-    uint8_t* e = R.extra;
-    const ProdBootOut O = {e + off[0], e + off[1], e + off[2], (uint32_t*)(e + off[3]), e + off[4], R.reason};
-    LCV_TRY(stage(ctx, ST_PRODUCE_ROWS, [&] {
-      return be_launch_team(ctx, F_prod_boot{R.S, R.K, R.idx0, R.idx1, R.X, O, ctx->cfg, (uint32_t)ncomm}, (uint32_t)n);
-    }));
-    void* dst[5] = {beacon112, exec832, exec_branch128, committee_index, committee_branch160};
-    for (int k = 0; k < 5; ++k) LCV_TRY(be_d2h(ctx, dst[k], e + off[k], width[k] * n));
-    LCV_TRY(be_d2h(ctx, reason_out, R.reason, n));
-    LCV_TRY(be_sync(ctx));
-    be_collect_timings(ctx);
-    return LCV_OK;
-  };
-  const int rc = body();
-  if (R.mem) be_free(ctx, R.mem);
-  return rc;
+  const void* ix[2] = {state_idx, block_idx};
+  LCV_TRY(prod_views(ctx, states, ns, blocks, nb, committees, nullptr, ncomm, ix, 2, n, extra.total(), R));
+  uint8_t* e = R.extra;
+  const ProdBootOut O = {e + off[0], e + off[1], e + off[2], (uint32_t*)(e + off[3]), e + off[4], R.reason};
+  LCV_TRY(stage(ctx, ST_PRODUCE_ROWS, [&] {
+    return be_launch_team(ctx, F_prod_boot{R.S, R.K, R.idx0, R.idx1, R.X, O, ctx->cfg, (uint32_t)ncomm}, (uint32_t)n);
+  }));
+  void* dst[5] = {beacon112, exec832, exec_branch128, committee_index, committee_branch160};
+  for (int k = 0; k < 5; ++k) LCV_TRY(be_d2h(ctx, dst[k], e + off[k], width[k] * n));
+  LCV_TRY(be_d2h(ctx, reason_out, R.reason, n));
+  LCV_TRY(be_sync(ctx));
+  be_collect_timings(ctx);
+  return LCV_OK;
 }
 
 }  // extern "C"
@@ -2949,38 +2969,34 @@ int lcv_batch_encode(lcv_ctx* ctx, lcv_dbatch* b, const uint32_t* rows, uint64_t
   uint64_t chunk = LCV_ENCODE_SCRATCH_BYTES / pitch;
   if (ctx->enc_chunk && ctx->enc_chunk < chunk) chunk = ctx->enc_chunk;
   if (m < chunk) chunk = m;
-  auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_meta = pad(chunk * pitch), o_rows = o_meta + pad(chunk * ENC_META_BYTES);
-  const size_t total = o_rows + pad(4 * chunk);
-  std::vector<uint8_t> meta;
-  try {
-    meta.resize(m * ENC_META_BYTES);
-  } catch (...) {  // an extern "C" entry point must not let an exception out
-    return fail(ctx, LCV_ENOMEM, std::string(who) + ": out of host memory");
-  }
-  be_set_slot(ctx, 0);
-  LCV_TRY(dev_alloc_grow(ctx, &ctx->enc_mem, &ctx->enc_cap, total, total));
-  uint8_t* d = (uint8_t*)ctx->enc_mem;
-  be_reset_timings(ctx);
-  for (uint64_t c0 = 0; c0 < m; c0 += chunk) {
-    const uint64_t mc = std::min(chunk, m - c0);
-    if (rows) LCV_TRY(be_h2d(ctx, d + o_rows, rows + c0, 4 * mc));
-    const EncArgs A = {b->B, rows ? (const uint32_t*)(d + o_rows) : nullptr, (uint32_t)c0, d, d + o_meta, ctx->cfg,
-                       (uint32_t)kind, (int32_t)fork, (uint32_t)pitch};
-    LCV_TRY(stage(ctx, ST_WIRE_ENCODE, [&] { return be_launch_team(ctx, F_wire_enc{A}, (uint32_t)mc); }));
-    LCV_TRY(be_d2h(ctx, out + c0 * pitch, d, mc * pitch));
-    LCV_TRY(be_d2h(ctx, meta.data() + c0 * ENC_META_BYTES, d + o_meta, mc * ENC_META_BYTES));
-  }
-  LCV_TRY(be_sync(ctx));
-  be_collect_timings(ctx);
-  for (uint64_t i = 0; i < m; ++i) {
-    const uint8_t* r = meta.data() + i * ENC_META_BYTES;
-    memcpy(&len_out[i], r, 4);
-    fork_out[i] = r[4];
-    status_out[i] = r[5];
-    memcpy(version_out + 4 * i, r + 8, 4);
-  }
-  return LCV_OK;
+  Layout l;
+  const size_t o_area = l.take(chunk * pitch), o_meta = l.take(chunk * ENC_META_BYTES), o_rows = l.take(4 * chunk);
+  return guarded(ctx, who, [&]() -> int {
+    std::vector<uint8_t> meta(m * ENC_META_BYTES);
+    be_set_slot(ctx, 0);
+    LCV_TRY(ctx->enc_mem.grow(ctx, l.total()));
+    uint8_t* d = ctx->enc_mem.p;
+    be_reset_timings(ctx);
+    for (uint64_t c0 = 0; c0 < m; c0 += chunk) {
+      const uint64_t mc = std::min(chunk, m - c0);
+      if (rows) LCV_TRY(be_h2d(ctx, d + o_rows, rows + c0, 4 * mc));
+      const EncArgs A = {b->B, rows ? (const uint32_t*)(d + o_rows) : nullptr, (uint32_t)c0, d + o_area, d + o_meta, ctx->cfg,
+                         (uint32_t)kind, (int32_t)fork, (uint32_t)pitch};
+      LCV_TRY(stage(ctx, ST_WIRE_ENCODE, [&] { return be_launch_team(ctx, F_wire_enc{A}, (uint32_t)mc); }));
+      LCV_TRY(be_d2h(ctx, out + c0 * pitch, d + o_area, mc * pitch));
+      LCV_TRY(be_d2h(ctx, meta.data() + c0 * ENC_META_BYTES, d + o_meta, mc * ENC_META_BYTES));
+    }
+    LCV_TRY(be_sync(ctx));
+    be_collect_timings(ctx);
+    for (uint64_t i = 0; i < m; ++i) {
+      const uint8_t* r = meta.data() + i * ENC_META_BYTES;
+      memcpy(&len_out[i], r, 4);
+      fork_out[i] = r[4];
+      status_out[i] = r[5];
+      memcpy(version_out + 4 * i, r + 8, 4);
+    }
+    return LCV_OK;
+  });
 }
 
 int lcv_encode_updates(lcv_ctx* ctx, const lcv_update_batch* batch, int kind, int fork, uint8_t* out, uint32_t* len_out,
@@ -3009,15 +3025,16 @@ int lcv_encode_updates(lcv_ctx* ctx, const lcv_update_batch* batch, int kind, in
 // the batch allocated, the rows.  The other kinds have one pool row, SyncCommittee(), and take the second pass only.
 struct DecScratch { size_t meta, stage_bytes, rec, pairs, differ, pool_src, total; };
 static DecScratch dec_scratch(size_t msg_bytes, size_t n) {
-  auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  Layout l;
   DecScratch s;
-  s.meta = pad(msg_bytes);
-  s.stage_bytes = s.meta + n * DEC_META_BYTES;
-  s.rec = pad(s.stage_bytes);
-  s.pairs = s.rec + pad(n * DEC_REC_BYTES);
-  s.differ = s.pairs + pad(n * DEC_PAIR_BYTES);
-  s.pool_src = s.differ + pad(4 * n);
-  s.total = s.pool_src + pad(8 * (n + 1));
+  l.take(msg_bytes);  // the messages, at offset 0
+  s.meta = l.take(n * DEC_META_BYTES);
+  s.stage_bytes = s.meta + n * DEC_META_BYTES;  // what the one DMA moves
+  s.rec = l.take(n * DEC_REC_BYTES);
+  s.pairs = l.take(n * DEC_PAIR_BYTES);
+  s.differ = l.take(4 * n);
+  s.pool_src = l.take(8 * (n + 1));
+  s.total = l.total();
   return s;
 }
 
@@ -3109,43 +3126,35 @@ int lcv_batch_decode(lcv_ctx* ctx, const uint8_t* buf, uint64_t buf_len, const u
       return fail(ctx, LCV_EINVAL, who + ": staged bytes above LCV_DECODE_MAX_BYTES at message " + std::to_string(i));
   }
   if (n == 0) return LCV_OK;
-  const DecScratch S = dec_scratch((size_t)msg_bytes, (size_t)n);
-  std::vector<uint8_t> rec;
-  std::vector<uint32_t> nsc_index, rep, cand;
-  std::vector<uint64_t> coff, pool_src;
-  std::vector<CopyPiece> pieces;
-  try {
-    rec.resize(n * DEC_REC_BYTES);
-    nsc_index.assign(n, 0u);
+  return guarded(ctx, who.c_str(), [&]() -> int {
+    const DecScratch S = dec_scratch((size_t)msg_bytes, (size_t)n);
+    std::vector<uint8_t> rec(n * DEC_REC_BYTES);
+    std::vector<uint32_t> nsc_index(n, 0u), rep, cand;
+    std::vector<uint64_t> coff, pool_src(1, DEC_NO_COMMITTEE);
+    std::vector<CopyPiece> pieces;
     pieces.reserve(n);
-  } catch (...) {  // an extern "C" entry point must not let an exception out
-    return fail(ctx, LCV_ENOMEM, who + ": out of host memory");
-  }
-  be_set_slot(ctx, 0);
-  LCV_TRY(host_alloc_grow(ctx, &ctx->dec_pin, &ctx->dec_pin_cap, S.stage_bytes));
-  LCV_TRY(dev_alloc_grow(ctx, &ctx->dec_mem, &ctx->dec_cap, S.total, S.total));
-  uint8_t* pin = ctx->dec_pin;
-  uint8_t* d = (uint8_t*)ctx->dec_mem;
-  {  // staging: the messages (host threads above 8 MB), the padding, the meta records
-    uint64_t o = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-      const uint32_t f = forks ? (uint32_t)forks[i] : (uint32_t)fork;
-      const uint32_t len = (uint32_t)lengths[i];  // (<= LCV_DECODE_MAX_BYTES < 2^32)
-      memcpy(pin + S.meta + DEC_META_BYTES * i, &o, 8);
-      memcpy(pin + S.meta + DEC_META_BYTES * i + 8, &len, 4);
-      memcpy(pin + S.meta + DEC_META_BYTES * i + 12, &f, 4);
-      if (lengths[i]) pieces.push_back({pin + o, buf + offsets[i], (size_t)lengths[i]});
-      o += (lengths[i] + 15) & ~(uint64_t)15;
+    be_set_slot(ctx, 0);
+    LCV_TRY(ctx->dec_pin.grow(ctx, S.stage_bytes));
+    LCV_TRY(ctx->dec_mem.grow(ctx, S.total));
+    uint8_t* pin = ctx->dec_pin.p;
+    uint8_t* d = ctx->dec_mem.p;
+    {  // staging: the messages (host threads above 8 MB), the padding, the meta records
+      uint64_t o = 0;
+      for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t f = forks ? (uint32_t)forks[i] : (uint32_t)fork;
+        const uint32_t len = (uint32_t)lengths[i];  // (<= LCV_DECODE_MAX_BYTES < 2^32)
+        memcpy(pin + S.meta + DEC_META_BYTES * i, &o, 8);
+        memcpy(pin + S.meta + DEC_META_BYTES * i + 8, &len, 4);
+        memcpy(pin + S.meta + DEC_META_BYTES * i + 12, &f, 4);
+        if (lengths[i]) pieces.push_back({pin + o, buf + offsets[i], (size_t)lengths[i]});
+        o += (lengths[i] + 15) & ~(uint64_t)15;
+      }
+      memset(pin + o, 0, 16);
+      copy_pieces(pieces, (size_t)msg_bytes);
     }
-    memset(pin + o, 0, 16);
-    copy_pieces(pieces, (size_t)msg_bytes);
-  }
-  be_reset_timings(ctx);
-  LCV_TRY(be_h2d(ctx, d, pin, S.stage_bytes));
-  DecArgs A = {d, d + S.meta, d + S.rec, ProdOut{}, (uint32_t)kind, (uint32_t)DEC_PLAN};
-  uint64_t npool = 1;
-  try {
-    pool_src.assign(1, DEC_NO_COMMITTEE);
+    be_reset_timings(ctx);
+    LCV_TRY(be_h2d(ctx, d, pin, S.stage_bytes));
+    DecArgs A = {d, d + S.meta, d + S.rec, ProdOut{}, (uint32_t)kind, (uint32_t)DEC_PLAN};
     if (kind == 0) {
       LCV_TRY(stage(ctx, ST_WIRE_DECODE, [&] { return be_launch_team(ctx, F_wire_dec{A}, (uint32_t)n); }));
       LCV_TRY(be_d2h(ctx, rec.data(), d + S.rec, n * DEC_REC_BYTES));
@@ -3177,23 +3186,16 @@ int lcv_batch_decode(lcv_ctx* ctx, const uint8_t* buf, uint64_t buf_len, const u
           nsc_index[i] = ix[rep[i]];
         }
       }
-      npool = pool_src.size();
     }
-  } catch (...) {
-    return fail(ctx, LCV_ENOMEM, who + ": out of host memory");
-  }
-  // the batch: lcv_batch_upload's layout
-  BatchCols c;
-  batch_layout(c, n, npool, false, 0);
-  lcv_dbatch* db = new (std::nothrow) lcv_dbatch();
-  if (!db) return LCV_ENOMEM;
-  int rc = be_alloc(ctx, &db->mem, c.total);
-  if (rc != LCV_OK) { delete db; return rc; }
-  uint8_t* m = (uint8_t*)db->mem;
-  bind_batch(db, m, c);
-  auto body = [&]() -> int {
+    const uint64_t npool = pool_src.size();
+    // the batch: lcv_batch_upload's layout
+    BatchCols c;
+    batch_layout(c, n, npool, false, 0);
+    NewBatch nb(ctx);
+    LCV_TRY(batch_new(ctx, c, nb));
+    uint8_t* m = nb.db->mem.p;
     LCV_TRY(be_h2d(ctx, m + c.off[COL_NSC_INDEX], nsc_index.data(), 4 * n));
-    A.O = prod_out(db->B);
+    A.O = prod_out(nb.db->B);
     A.phase = DEC_ROWS;
     if (kind == 0) A.rec = nullptr;  // (the first pass left the records)
     LCV_TRY(stage(ctx, ST_WIRE_DECODE, [&] { return be_launch_team(ctx, F_wire_dec{A}, (uint32_t)n); }));
@@ -3207,13 +3209,9 @@ int lcv_batch_decode(lcv_ctx* ctx, const uint8_t* buf, uint64_t buf_len, const u
     }
     LCV_TRY(be_sync(ctx));
     be_collect_timings(ctx);
-    return LCV_OK;
-  };
-  rc = body();
-  if (rc != LCV_OK) { be_free(ctx, db->mem); delete db; return rc; }
-  for (uint64_t i = 0; i < n; ++i) status_out[i] = rec[DEC_REC_BYTES * i] ? 1 : 0;
-  *out = db;
-  return LCV_OK;
+    for (uint64_t i = 0; i < n; ++i) status_out[i] = rec[DEC_REC_BYTES * i] ? 1 : 0;
+    return nb.hand_out(out);
+  });
 }
 
 }  // extern "C"

@@ -50,7 +50,15 @@ static int be_wait_event(lcv_ctx*, int) { return 0; }
 static int be_fork_to(lcv_ctx*, int) { return 0; }
 static int be_join_from(lcv_ctx*, int) { return 0; }
 static int be_sync_slot(lcv_ctx*) { return 0; }
-static void be_host_free(lcv_ctx*, void* p) { free(p); }
+#ifdef LCV_ALLOC_CHECK
+// tools/driver_alloc_check.cpp: the live device / pinned allocations, the allocations made so far, and the one that
+// fails (counted down; -1: none)
+static long g_live[2] = {0, 0}, g_allocs = 0, g_fail_in = -1;
+#define LCV_LIVE(pinned, d) (g_live[pinned] += (d))
+#else
+#define LCV_LIVE(pinned, d) ((void)0)
+#endif
+static void be_host_free(lcv_ctx*, void* p) { LCV_LIVE(1, -1); free(p); }
 static size_t be_event_pool_size(lcv_ctx*) { return 0; }
 
 #include "lcv_driver.inc"
@@ -60,16 +68,24 @@ static int be_init(lcv_ctx* ctx, int device) {
   return LCV_OK;
 }
 static void be_destroy(lcv_ctx*) {}
-static int be_alloc(lcv_ctx* ctx, void** p, size_t bytes) {
+static int host_calloc(lcv_ctx* ctx, void** p, size_t bytes, int pinned) {
+#ifdef LCV_ALLOC_CHECK
+  ++g_allocs;
+  if (g_fail_in >= 0 && g_fail_in-- == 0) return fail(ctx, LCV_ENOMEM, "hostsim: out of memory (injected)");
+#endif
   *p = calloc(1, bytes ? bytes : 1);
-  return *p ? LCV_OK : fail(ctx, LCV_ENOMEM, "hostsim: out of memory");
+  if (!*p) return fail(ctx, LCV_ENOMEM, "hostsim: out of memory");
+  LCV_LIVE(pinned, 1);
+  return LCV_OK;
 }
-static void be_free(lcv_ctx*, void* p) { free(p); }
-static int be_host_alloc(lcv_ctx* ctx, void** p, size_t bytes) { return be_alloc(ctx, p, bytes); }
-static int be_h2d(lcv_ctx*, void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return LCV_OK; }
-static int be_d2h(lcv_ctx*, void* dst, const void* src, size_t bytes) { memcpy(dst, src, bytes); return LCV_OK; }
-static int be_d2d(lcv_ctx*, void* dst, const void* src, size_t bytes) { memmove(dst, src, bytes); return LCV_OK; }
-static int be_memset(lcv_ctx*, void* p, int v, size_t bytes) { memset(p, v, bytes); return LCV_OK; }
+static int be_alloc(lcv_ctx* ctx, void** p, size_t bytes) { return host_calloc(ctx, p, bytes, 0); }
+static void be_free(lcv_ctx*, void* p) { LCV_LIVE(0, -1); free(p); }
+static int be_host_alloc(lcv_ctx* ctx, void** p, size_t bytes) { return host_calloc(ctx, p, bytes, 1); }
+// (an empty copy may come with a null pointer: an optional column that a batch does not carry)
+static int be_h2d(lcv_ctx*, void* dst, const void* src, size_t bytes) { if (bytes) memcpy(dst, src, bytes); return LCV_OK; }
+static int be_d2h(lcv_ctx*, void* dst, const void* src, size_t bytes) { if (bytes) memcpy(dst, src, bytes); return LCV_OK; }
+static int be_d2d(lcv_ctx*, void* dst, const void* src, size_t bytes) { if (bytes) memmove(dst, src, bytes); return LCV_OK; }
+static int be_memset(lcv_ctx*, void* p, int v, size_t bytes) { if (bytes) memset(p, v, bytes); return LCV_OK; }
 static int be_sync(lcv_ctx*) { return LCV_OK; }
 template <class F> static int be_launch(lcv_ctx*, const F& f, uint32_t n) {
 #pragma omp parallel for schedule(dynamic, 1)
