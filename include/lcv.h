@@ -370,13 +370,48 @@ int lcv_debug_engine_log(lcv_ctx* ctx, uint64_t* out8, int reset);
  * column (and in the CPU-baseline build, whose direct path runs every row).
  * lcv_debug_dedup_hash_bits is a test hook: the host hash is truncated to `bits` bits (default 64; 0 makes every
  * row collide, so that only the full compare separates classes).
- * Out of scope: resident batches made on the device (lcv_create_updates_resident, lcv_batch_decode: no host bytes to
- * class; they run without deduplication); merging across chunks or across batches in flight; lcv_fast_aggregate_verify_batch;
+ * Resident batches made on the device (lcv_create_updates_resident, lcv_batch_decode, lcv_batch_fan_out of an
+ * unclassed batch) have no host bytes to class: they run without deduplication until lcv_batch_classify (below) has
+ * classed them where they lie.
+ * Out of scope: merging across chunks or across batches in flight; lcv_fast_aggregate_verify_batch;
  * merging committee-table rows of equal content; skipping the BLS work of items all of whose rows failed a
  * pre-check. */
 int lcv_set_dedup(lcv_ctx* ctx, int on);
 int lcv_last_dedup(lcv_ctx* ctx, int slot, uint64_t* rows, uint64_t* items);
 int lcv_debug_dedup_hash_bits(lcv_ctx* ctx, int bits);
+/* ---- Classes of a resident batch, made on the device; fanning a resident batch out to stores.  A relay keeps its
+ * rows on the device: bytes -> lcv_batch_decode -> lcv_batch_classify -> lcv_batch_fan_out(rows, store_index) ->
+ * lcv_validate_resident* under lcv_set_dedup -> lcv_batch_encode(rows = accepted); the host never holds a row and each
+ * distinct signature is checked once.
+ * lcv_batch_classify gives any resident batch (uploaded, decoded, created, fanned out), whatever lcv_set_dedup says, the
+ * class column a batch uploaded with the mode on has: cls[i] = the first row whose (attested beacon header,
+ * signature_slot, sync_bits, sync_signature) equal row i's, bytewise.  A kernel folds every row's 280 tuple bytes into
+ * a 64-bit key, the host groups the keys (truncated to lcv_debug_dedup_hash_bits' bits) and a second kernel compares
+ * every row but a group's first with that first row in full; groups whose members differ are split and compared again
+ * (one launch per extra distinct content under one key value).  Rows merge only on a full compare.  The batch then
+ * keeps the column on the host (with signature_slot, and store_index where it carries one: one device-to-host copy
+ * each), and every later validation with the mode on groups it as an uploaded batch.  *classes_out: the number of
+ * distinct classes.  Classifying again yields the same column.  A batch of no rows: LCV_OK, 0 classes.  A null argument:
+ * LCV_EINVAL.  Synchronous, on work-space slot 0's stream: wait for pending slots first.  Device scratch: 20 bytes per
+ * row of a chunk (lcv_debug_set_chunk), freed on return; longer batches take one launch per chunk of rows or pairs.
+ * lcv_last_classify_timings: kernel time of the last classify, [0] the keys, [1] the compares; not stages of
+ * lcv_last_timings, which reads all zero after a classify.
+ * lcv_debug_batch_classes (test hook): the n class labels of a batch; LCV_EINVAL for a batch that has none.
+ * lcv_batch_fan_out makes a resident batch of n rows: row i is row rows[i] of src (each < src's n, repeats allowed;
+ * rows == NULL: row i, and n must be src's n), gathered on the device as lcv_batch_download's row list is; src's whole
+ * pool is copied device to device, so nsc_index stays valid.  store_index != NULL: the result is a table batch with that
+ * column, as lcv_batch_upload_stores makes (checked against the table at validation time, not here); NULL: a
+ * single-store batch.  The classes of a classed src are inherited on the host (cls[i] = src's cls[rows[i]]: equal
+ * labels, equal tuples); the result of an unclassed src is unclassed.  Refused with LCV_EINVAL before any launch,
+ * lcv_last_error naming the first offender, *out = NULL: a null ctx, src or out; rows and store_index both NULL; n == 0
+ * or n >= 2^32 - 1; rows[i] >= src's n.  Synchronous, on slot 0's stream; freed by lcv_batch_free.
+ * Out of scope: an asynchronous relay on the eight slots; classing inside lcv_batch_decode or
+ * lcv_create_updates_resident by default; merging across chunks; bootstraps. */
+int lcv_batch_classify(lcv_ctx* ctx, lcv_dbatch* b, uint64_t* classes_out);
+int lcv_last_classify_timings(lcv_ctx* ctx, float ms_out[2]);
+int lcv_debug_batch_classes(lcv_ctx* ctx, const lcv_dbatch* b, uint32_t* out /* n */);
+int lcv_batch_fan_out(lcv_ctx* ctx, lcv_dbatch* src, const uint32_t* rows, const uint32_t* store_index, uint64_t n,
+                      lcv_dbatch** out);
 
 /* ---- Batch verification: one final exponentiation per group of rows (randomised linear combination, as blst's
  * verify_multiple_aggregate_signatures).  For a group of G consecutive items of a chunk (the rows; under
@@ -616,8 +651,8 @@ int lcv_debug_set_encode_chunk(lcv_ctx* ctx, uint64_t rows);
  * The host copies the messages into a pinned buffer of the context (16-byte aligned each; messages that overlap or
  * repeat in buf are staged twice) and one DMA moves it into a device scratch; both grow on demand and are kept.
  * Synchronous, on work-space slot 0's stream: wait for pending slots first.
- * No deduplication: a batch made this way has no host bytes to class and is validated without deduplication under
- * lcv_set_dedup, as lcv_create_updates_resident's batches are.
+ * Deduplication: a batch made this way has no host bytes to class and, like lcv_create_updates_resident's, is
+ * validated without deduplication under lcv_set_dedup until lcv_batch_classify has classed it on the device.
  * lcv_last_decode_timings: kernel time of the last decode, [0] the decode kernel's passes, [1] the committee
  * compares and the pool gather (0 for kinds 1 and 2).  These launches are not stages of lcv_last_timings, which
  * reads all zero after a decode.

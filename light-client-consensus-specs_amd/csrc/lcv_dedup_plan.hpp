@@ -5,6 +5,7 @@
 //   dedup_classes  store-independent class of every row: rows with equal (attested beacon header, signature_slot,
 //                  sync_committee_bits, sync_committee_signature) get the index of the first such row
 //   dedup_plan     the grouping of one chunk: rows with equal (class, committee row) are one item
+//   dedup_confirm_groups  the host loop of a grouping whose full compares run elsewhere (on the device)
 // Both are one pass over an open-addressing table: O(n) expected.  Rows are merged only on a full compare of their
 // keys; the hash only picks where to look (hash_bits < 64 truncates it — 0 makes every row collide — so tests can
 // show that).
@@ -85,6 +86,43 @@ inline void dedup_classes(const uint8_t* att_beacon, const uint64_t* sig_slot, c
                memcmp(bits + (size_t)DEDUP_BITS * a, bits + (size_t)DEDUP_BITS * i, DEDUP_BITS) == 0;
       },
       [&](uint32_t i) { cls[i] = i; }, [&](uint32_t a, uint32_t i) { cls[i] = a; });
+}
+
+// Groups made on a hash alone, settled by full compares somebody else runs (the device: lcv_batch_decode's committee
+// pool, lcv_batch_classify's classes).  rep[r] = the tentative representative of row r, the first row of its hash
+// group (rep[r] == r for a representative; rows outside the grouping are never looked at); `pending` lists, ascending,
+// the rows with rep[r] != r.  confirm(pending, rep, differ) compares row pending[k] with row rep[pending[k]] in full
+// for every k, sets differ[k] (pending.size() entries, non-zero: they differ) and returns 0, or an error code, which
+// ends the loop.  The rows of a group that differ form the next candidate group under their lowest row, which becomes
+// a representative, and the compare repeats: one call per extra distinct content under one hash value.  On return
+// rep[r] is the first row whose content equals row r's.
+template <class Confirm>
+inline int dedup_confirm_groups(std::vector<uint32_t>& rep, std::vector<uint32_t>& pending, Confirm confirm) {
+  const uint32_t none = 0xffffffffu;
+  std::vector<uint32_t> next, differ, touched, newrep(rep.size(), none);
+  while (!pending.empty()) {
+    const size_t m = pending.size();
+    differ.assign(m, 0u);
+    const int rc = confirm(pending, rep, differ);
+    if (rc != 0) return rc;
+    next.clear();
+    touched.clear();
+    for (size_t k = 0; k < m; ++k) {
+      if (!differ[k]) continue;
+      const uint32_t r = pending[k], old = rep[r];
+      if (newrep[old] == none) {  // the lowest differing row of its group: a representative of its own
+        newrep[old] = r;
+        touched.push_back(old);
+        rep[r] = r;
+      } else {
+        rep[r] = newrep[old];
+        next.push_back(r);
+      }
+    }
+    for (uint32_t old : touched) newrep[old] = none;
+    pending.swap(next);
+  }
+  return 0;
 }
 
 // The grouping of a chunk of n rows: row i has class cls[i] (any labels: equal labels = equal BLS inputs apart from

@@ -39,8 +39,8 @@ static const char* kStageNames[ST_COUNT] = {"nsc_htr", "pre_checks", "h2c_sswu",
                                             "dedup_gather", "rlc_scale", "rlc_product", "rlc_spread", "rlc_retry",
                                             "wire_encode"};
 // lcv_batch_decode's launches: timed like the others, but past the public list (lcv_stage_name, lcv_last_timings);
-// lcv_last_decode_timings reports them
-enum { ST_WIRE_DECODE = ST_COUNT, ST_DECODE_POOL, ST_TOTAL };
+// lcv_last_decode_timings reports them; likewise lcv_batch_classify's (lcv_last_classify_timings)
+enum { ST_WIRE_DECODE = ST_COUNT, ST_DECODE_POOL, ST_CLASS_KEY, ST_CLASS_CONFIRM, ST_TOTAL };
 
 #define LCV_TRY(x)                    \
   do {                                \
@@ -134,7 +134,9 @@ struct lcv_dbatch {
   // lcv_set_dedup.  A resident batch uploaded while the mode was on keeps its class column on the host (cls[i]: the
   // first row whose BLS inputs equal row i's; empty: uploaded with the mode off, validated without deduplication), and
   // a table batch also the two columns the committee choice of a row depends on, so that every validation can group
-  // the rows under the table of that moment.  A staged host batch brings its grouping along instead (batch_cols
+  // the rows under the table of that moment.  lcv_batch_classify makes the same columns for any resident batch, on the
+  // device; lcv_batch_fan_out's result inherits them (any labels: equal labels, equal BLS inputs apart from the
+  // committee).  A staged host batch brings its grouping along instead (batch_cols
   // COL_DEDUP_REP, COL_DEDUP_UROW; plan_m items, 0: none)
   std::vector<uint32_t> cls, h_store;
   std::vector<uint64_t> h_sig_slot;
@@ -3042,10 +3044,10 @@ static DecScratch dec_scratch(size_t msg_bytes, size_t n) {
 // first row whose committee equals row i's.  The rows are grouped by their (truncated) hash alone; then every row but
 // a group's first is compared in full with its tentative representative on the device (F_sc_confirm), the rows that
 // differ form the next candidate group under their lowest row, and the compare repeats: one launch per extra distinct
-// content under one hash value, none at 64 bits in practice.  coff[i]: the scratch offset of row i's committee
+// content under one hash value, none at 64 bits in practice (the loop: dedup_confirm_groups, which lcv_batch_classify
+// shares).  coff[i]: the scratch offset of row i's committee
 static int dec_resolve_pool(lcv_ctx* ctx, uint8_t* d, const DecScratch& S, const std::vector<uint32_t>& cand,
                             const uint8_t* rec, const std::vector<uint64_t>& coff, std::vector<uint32_t>& rep) {
-  const uint32_t none = 0xffffffffu;
   auto hash_of = [&](uint32_t row) {
     uint64_t h;
     memcpy(&h, rec + (size_t)DEC_REC_BYTES * row + 8, 8);
@@ -3055,41 +3057,24 @@ static int dec_resolve_pool(lcv_ctx* ctx, uint8_t* d, const DecScratch& S, const
       (uint32_t)cand.size(), ctx->dec_hash_bits, ctx->dec_table, [&](uint32_t j) { return hash_of(cand[j]); },
       [](uint32_t, uint32_t) { return true; }, [&](uint32_t j) { rep[cand[j]] = cand[j]; },
       [&](uint32_t a, uint32_t j) { rep[cand[j]] = cand[a]; });
-  std::vector<uint32_t> pending, next, differ, touched, newrep(rep.size(), none);
+  std::vector<uint32_t> pending;
   std::vector<uint64_t> pairs;
   for (uint32_t r : cand)
     if (rep[r] != r) pending.push_back(r);
-  while (!pending.empty()) {
-    const size_t m = pending.size();
+  return dedup_confirm_groups(rep, pending, [&](const std::vector<uint32_t>& pend, const std::vector<uint32_t>& rp,
+                                                std::vector<uint32_t>& differ) -> int {
+    const size_t m = pend.size();
     pairs.resize(2 * m);
-    differ.resize(m);
     for (size_t k = 0; k < m; ++k) {
-      pairs[2 * k] = coff[pending[k]];
-      pairs[2 * k + 1] = coff[rep[pending[k]]];
+      pairs[2 * k] = coff[pend[k]];
+      pairs[2 * k + 1] = coff[rp[pend[k]]];
     }
     LCV_TRY(be_h2d(ctx, d + S.pairs, pairs.data(), DEC_PAIR_BYTES * m));
     const ScConfirmArgs A = {d, d + S.pairs, (uint32_t*)(d + S.differ)};
     LCV_TRY(stage(ctx, ST_DECODE_POOL, [&] { return be_launch_team(ctx, F_sc_confirm{A}, (uint32_t)m); }));
     LCV_TRY(be_d2h(ctx, differ.data(), d + S.differ, 4 * m));
-    LCV_TRY(be_sync(ctx));
-    next.clear();
-    touched.clear();
-    for (size_t k = 0; k < m; ++k) {
-      if (!differ[k]) continue;
-      const uint32_t r = pending[k], old = rep[r];
-      if (newrep[old] == none) {  // the lowest differing row of its group: a representative of its own
-        newrep[old] = r;
-        touched.push_back(old);
-        rep[r] = r;
-      } else {
-        rep[r] = newrep[old];
-        next.push_back(r);
-      }
-    }
-    for (uint32_t old : touched) newrep[old] = none;
-    pending.swap(next);
-  }
-  return LCV_OK;
+    return be_sync(ctx);
+  });
 }
 
 extern "C" {
@@ -3210,6 +3195,147 @@ int lcv_batch_decode(lcv_ctx* ctx, const uint8_t* buf, uint64_t buf_len, const u
     LCV_TRY(be_sync(ctx));
     be_collect_timings(ctx);
     for (uint64_t i = 0; i < n; ++i) status_out[i] = rec[DEC_REC_BYTES * i] ? 1 : 0;
+    return nb.hand_out(out);
+  });
+}
+
+// ------------------------------------------------------------------ the classes of a resident batch, and its fan-out
+// lcv_batch_classify: dedup_classes' column for a batch whose rows never were on the host.  F_dedup_key gives every
+// row a 64-bit key of its tuple, the host groups the keys alone (dedup_group under lcv_debug_dedup_hash_bits), and
+// every row but a group's first is compared in full with its tentative representative on the device
+// (F_dedup_confirm; dedup_confirm_groups splits the groups whose members differ).  Keys, pair lists and flags live
+// in one Scratch of the call, sized for one piece of ctx->chunk rows or pairs; a longer batch takes several launches
+int lcv_last_classify_timings(lcv_ctx* ctx, float ms_out[2]) {
+  if (!ctx || !ms_out) return fail(ctx, LCV_EINVAL, "lcv_last_classify_timings: null argument");
+  ms_out[0] = ctx->stage_ms[ST_CLASS_KEY];
+  ms_out[1] = ctx->stage_ms[ST_CLASS_CONFIRM];
+  return LCV_OK;
+}
+
+int lcv_debug_batch_classes(lcv_ctx* ctx, const lcv_dbatch* b, uint32_t* out) {
+  if (!ctx || !b || !out) return fail(ctx, LCV_EINVAL, "lcv_debug_batch_classes: null argument");
+  if (b->cls.size() != b->n || b->n == 0) return fail(ctx, LCV_EINVAL, "lcv_debug_batch_classes: the batch has no class column");
+  memcpy(out, b->cls.data(), 4 * (size_t)b->n);
+  return LCV_OK;
+}
+
+int lcv_batch_classify(lcv_ctx* ctx, lcv_dbatch* b, uint64_t* classes_out) {
+  const char* who = "lcv_batch_classify";
+  if (!ctx || !b || !classes_out) return fail(ctx, LCV_EINVAL, std::string(who) + ": null argument");
+  *classes_out = 0;
+  if (b->n == 0) return LCV_OK;
+  return guarded(ctx, who, [&]() -> int {
+    const size_t n = (size_t)b->n, piece = std::min(n, ctx->chunk);
+    std::vector<uint64_t> key(n), sig_slot(n);
+    std::vector<uint32_t> cls(n), store(b->B.store_index ? n : 0), pending, pairs;
+    Layout l;
+    const size_t o_key = l.take(8 * piece), o_pairs = l.take(8 * piece), o_differ = l.take(4 * piece);
+    be_set_slot(ctx, 0);
+    Scratch mem(ctx);
+    LCV_TRY(mem.alloc(l.total()));
+    uint64_t* key_dev = (uint64_t*)(mem.p + o_key);
+    uint32_t* pairs_dev = (uint32_t*)(mem.p + o_pairs);
+    uint32_t* differ_dev = (uint32_t*)(mem.p + o_differ);
+    be_reset_timings(ctx);
+    for (size_t base = 0; base < n; base += piece) {
+      const uint32_t m = (uint32_t)std::min(piece, n - base);
+      const F_dedup_key f = {chunk_view(b->B, base, m), key_dev};
+      LCV_TRY(stage(ctx, ST_CLASS_KEY, [&] { return be_launch_team(ctx, f, m); }));
+      LCV_TRY(be_d2h(ctx, key.data() + base, key_dev, 8 * (size_t)m));
+    }
+    // what the grouping at validate time reads of the rows (dedup_chunk, dedup_comm_rows), one copy per column
+    LCV_TRY(be_d2h(ctx, sig_slot.data(), b->B.sig_slot, 8 * n));
+    if (b->B.store_index) LCV_TRY(be_d2h(ctx, store.data(), b->B.store_index, 4 * n));
+    LCV_TRY(be_sync(ctx));
+    uint64_t classes = 0;
+    dedup_group(
+        (uint32_t)n, ctx->dedup_hash_bits, ctx->dd_table, [&](uint32_t i) { return key[i]; },
+        [](uint32_t, uint32_t) { return true; }, [&](uint32_t i) { cls[i] = i; }, [&](uint32_t a, uint32_t i) { cls[i] = a; });
+    for (size_t i = 0; i < n; ++i)
+      if (cls[i] != i) pending.push_back((uint32_t)i);
+    LCV_TRY(dedup_confirm_groups(cls, pending, [&](const std::vector<uint32_t>& pend, const std::vector<uint32_t>& rp,
+                                                   std::vector<uint32_t>& differ) -> int {
+      const size_t np = pend.size();
+      pairs.resize(2 * np);
+      for (size_t k = 0; k < np; ++k) {
+        const uint32_t a = pend[k], c = rp[a];
+        if (a >= n || c >= n) return fail(ctx, LCV_EINVAL, std::string(who) + ": pair " + std::to_string(k) + " names a row past the batch");
+        pairs[2 * k] = a;
+        pairs[2 * k + 1] = c;
+      }
+      for (size_t k0 = 0; k0 < np; k0 += piece) {
+        const uint32_t m = (uint32_t)std::min(piece, np - k0);
+        LCV_TRY(be_h2d(ctx, pairs_dev, pairs.data() + 2 * k0, 8 * (size_t)m));
+        const F_dedup_confirm f = {b->B, pairs_dev, differ_dev};
+        LCV_TRY(stage(ctx, ST_CLASS_CONFIRM, [&] { return be_launch_team(ctx, f, m); }));
+        LCV_TRY(be_d2h(ctx, differ.data() + k0, differ_dev, 4 * (size_t)m));
+      }
+      return be_sync(ctx);
+    }));
+    be_collect_timings(ctx);
+    for (size_t i = 0; i < n; ++i) classes += cls[i] == i;
+    // (nothing fails from here on: a batch classed before keeps its columns when the call does not succeed)
+    b->cls.swap(cls);
+    b->h_sig_slot.swap(sig_slot);
+    b->h_store.swap(store);
+    *classes_out = classes;
+    return LCV_OK;
+  });
+}
+
+// lcv_batch_fan_out: row i of the new batch = row rows[i] of src (rows null: row i), gathered on the device
+// (F_prod_pick, as lcv_batch_download's row list), the pool copied whole so that nsc_index stays valid, and the
+// store_index column attached as lcv_batch_upload_stores does (bind_batch records its largest entry).  The classes of
+// a classed source are inherited on the host: dedup_plan takes any labels
+int lcv_batch_fan_out(lcv_ctx* ctx, lcv_dbatch* src, const uint32_t* rows, const uint32_t* store_index, uint64_t n,
+                      lcv_dbatch** out) {
+  const char* who = "lcv_batch_fan_out";
+  if (out) *out = nullptr;
+  if (!ctx || !src || !out) return fail(ctx, LCV_EINVAL, std::string(who) + ": null argument");
+  if (!rows && !store_index) return fail(ctx, LCV_EINVAL, std::string(who) + ": rows and store_index are both null");
+  if (n == 0 || n >= 0xffffffffull) return fail(ctx, LCV_EINVAL, std::string(who) + ": need 0 < n < 2^32 - 1");
+  if (!rows && n != src->n)
+    return fail(ctx, LCV_EINVAL, std::string(who) + ": without rows, n = " + std::to_string(n) + " must be the source's " +
+                                     std::to_string(src->n) + " rows");
+  if (rows) LCV_TRY(prod_check_index(ctx, who, "rows", rows, n, src->n));
+  return guarded(ctx, who, [&]() -> int {
+    // (a single-store batch classed at upload keeps no signature_slot column: a table batch made from it reads its own)
+    const bool classed = !src->cls.empty(), slots = src->h_sig_slot.size() == src->n;
+    std::vector<uint32_t> cls, h_store;
+    std::vector<uint64_t> h_sig_slot;
+    if (classed) {
+      cls.resize(n);
+      if (slots || store_index) h_sig_slot.resize(n);
+      for (size_t i = 0; i < n; ++i) {
+        const size_t s = rows ? rows[i] : i;
+        cls[i] = src->cls[s];
+        if (slots) h_sig_slot[i] = src->h_sig_slot[s];
+      }
+      if (store_index) h_store.assign(store_index, store_index + n);
+    }
+    BatchCols c;
+    batch_layout(c, n, src->npool, store_index != nullptr, 0);
+    c.src[COL_STORE_INDEX] = store_index;
+    NewBatch nb(ctx);
+    be_set_slot(ctx, 0);
+    LCV_TRY(batch_new(ctx, c, nb));
+    lcv_dbatch* db = nb.db;
+    Scratch mem(ctx);  // (freed, waiting for the streams, ahead of an abandoned batch)
+    if (rows) {
+      LCV_TRY(mem.alloc(4 * n));
+      LCV_TRY(be_h2d(ctx, mem.p, rows, 4 * n));
+      LCV_TRY(be_launch_team(ctx, F_prod_pick{src->B, (const uint32_t*)mem.p, prod_out(db->B)}, (uint32_t)n));
+    } else {
+      for (const ColSpec& s : kBatchCols)
+        if (col_per_row(s) && s.prod >= 0) LCV_TRY(be_d2d(ctx, slot_get(&db->B, s.dev), slot_get(&src->B, s.dev), s.width * n));
+    }
+    LCV_TRY(be_d2d(ctx, db->mem.p + c.off[COL_NSC_POOL], src->B.nsc_pool, c.bytes[COL_NSC_POOL]));
+    LCV_TRY(be_h2d(ctx, db->mem.p + c.off[COL_STORE_INDEX], store_index, c.bytes[COL_STORE_INDEX]));
+    if (classed && store_index && !slots) LCV_TRY(be_d2h(ctx, h_sig_slot.data(), db->B.sig_slot, 8 * n));
+    LCV_TRY(be_sync(ctx));
+    db->cls.swap(cls);
+    db->h_sig_slot.swap(h_sig_slot);
+    db->h_store.swap(h_store);
     return nb.hand_out(out);
   });
 }

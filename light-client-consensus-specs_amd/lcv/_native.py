@@ -157,6 +157,10 @@ SIGNATURES = {
     "lcv_set_dedup": (C.c_int, [C.c_void_p, C.c_int]),
     "lcv_last_dedup": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p]),
     "lcv_debug_dedup_hash_bits": (C.c_int, [C.c_void_p, C.c_int]),
+    "lcv_batch_classify": (C.c_int, [C.c_void_p, C.c_void_p, u64p]),
+    "lcv_last_classify_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "lcv_debug_batch_classes": (C.c_int, [C.c_void_p, C.c_void_p, u32p]),
+    "lcv_batch_fan_out": (C.c_int, [C.c_void_p, C.c_void_p, u32p, u32p, C.c_uint64, C.POINTER(C.c_void_p)]),
     "lcv_set_rlc": (C.c_int, [C.c_void_p, C.c_uint32, u8p]),
     "lcv_last_rlc": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p]),
     "lcv_debug_rlc_coeffs": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u64p]),

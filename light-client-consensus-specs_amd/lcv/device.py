@@ -311,7 +311,8 @@ class Verifier:
         update relayed to many stores — share one run of the BLS half, and every row keeps its own pre-checks.
         Verdicts and reasons are those of the mode off.  Batches taken (validate*, upload) while the mode is on are
         grouped; a ResidentBatch uploaded with it off, or made on the device (create_updates_resident,
-        decode_resident: no host bytes to class), is validated without deduplication.  LcvError (status -1)
+        decode_resident: no host bytes to class), is validated without deduplication until classify_resident has
+        classed it.  LcvError (status -1)
         together with a multi-stream pipeline (set_pipeline streams > 1), from whichever call comes second."""
         self._check(self.lib.lcv_set_dedup(self.ctx, 1 if on else 0), "lcv_set_dedup")
         self.dedup = bool(on)
@@ -327,6 +328,46 @@ class Verifier:
         """Test hook (lcv_debug_dedup_hash_bits): set_dedup's host hash truncated to `bits` bits (64: whole; 0:
         every row collides, so only the full compare of the rows' bytes separates them)."""
         self._check(self.lib.lcv_debug_dedup_hash_bits(self.ctx, int(bits)), "lcv_debug_dedup_hash_bits")
+
+    def classify_resident(self, rb: ResidentBatch) -> int:
+        """Class a resident batch where it lies (lcv_batch_classify) -> the number of distinct classes.  Any resident
+        batch — uploaded, decode_resident's, create_updates_resident's, fan_out's — gets the class column a batch
+        uploaded under set_dedup(True) has (two kernels: a 64-bit key per row, then full compares of the rows the keys
+        pair up), whatever set_dedup says now; validation with the mode on then checks each distinct signature once."""
+        if not rb.handle:
+            return 0
+        m = C.c_uint64()
+        self._check(self.lib.lcv_batch_classify(self.ctx, rb.handle, C.byref(m)), "lcv_batch_classify")
+        return int(m.value)
+
+    def last_classify_timings(self) -> Tuple[float, float]:
+        """Kernel milliseconds of the last classify_resident (lcv_last_classify_timings): (the keys, the compares)."""
+        ms = (C.c_float * 2)()
+        self._check(self.lib.lcv_last_classify_timings(self.ctx, ms), "lcv_last_classify_timings")
+        return float(ms[0]), float(ms[1])
+
+    def debug_batch_classes(self, rb: ResidentBatch) -> np.ndarray:
+        """Test hook (lcv_debug_batch_classes): a batch's class column, cls[i] = the label of row i's class (at upload
+        and after classify_resident: the first row with row i's tuple).  LcvError for a batch that has none."""
+        out = np.zeros(max(rb.n, 1), np.uint32)
+        self._check(self.lib.lcv_debug_batch_classes(self.ctx, rb.handle, ptr(out, C.c_uint32)), "lcv_debug_batch_classes")
+        return out[:rb.n]
+
+    def fan_out(self, rb: ResidentBatch, rows=None, store_index=None) -> ResidentBatch:
+        """A new resident batch whose row i is row rows[i] of rb (lcv_batch_fan_out; repeats allowed; None: every row
+        in order), gathered on the device with rb's whole pool.  With `store_index` (one store-table row per row of the
+        result) it is a table batch, as upload(batch, store_index) makes; without, a single-store subset.  The classes
+        of a classed rb are inherited."""
+        ix = None if rows is None else np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        six = None if store_index is None else np.ascontiguousarray(store_index, np.uint32).reshape(-1)
+        n = rb.n if ix is None else ix.shape[0]
+        if six is not None and six.shape[0] != n:
+            raise ValueError("store_index needs one entry per row of the result")
+        h = C.c_void_p()
+        self._check(self.lib.lcv_batch_fan_out(self.ctx, rb.handle, None if ix is None or not n else ptr(ix, C.c_uint32),
+                                               None if six is None or not n else ptr(six, C.c_uint32), n, C.byref(h)),
+                    "lcv_batch_fan_out")
+        return ResidentBatch(self, h, n, stores=six is not None, npool=rb.npool)
 
     def set_rlc(self, group: int, seed: Optional[bytes] = None) -> None:
         """Randomised batch verification (lcv_set_rlc; off by default): groups of `group` (2, 4, ... 64) consecutive

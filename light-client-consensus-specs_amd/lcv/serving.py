@@ -5,15 +5,18 @@ batches of up to eight work-space slots in flight, a batch's upload and the host
 slots' kernels (lcv_validate_async, include/lcv.h).  This is the loop bench.py writes by hand, for any caller:
 single-store batches (Verifier.set_store) and table batches (Verifier.set_store_table, one store row per
 update) may be mixed in one stream.
+
+`relay_updates`: the relay's path with every row kept on the device — wire messages decoded, classed and fanned out
+to the stores of many clients, validated with each distinct signature checked once.
 """
 from __future__ import annotations
 
 from collections import deque
-from typing import Iterable, Iterator, Optional, Tuple, Union
+from typing import Iterable, Iterator, NamedTuple, Optional, Tuple, Union
 
 import numpy as np
 
-from .device import PackedUpdates, Verifier
+from .device import PackedUpdates, ResidentBatch, Verifier
 
 SLOTS = 8            # work-space slots of a context (LCV_SLOTS)
 MAX_ROWS = 65536     # rows of one asynchronous call
@@ -117,3 +120,50 @@ def validate_stream(verifier: Verifier, items: Iterable[Item], current_slot: int
             verifier.set_dedup(dedup_before)
         if rlc_group:
             verifier.set_rlc(rlc_before[0], rlc_before[1])
+
+
+class RelayResult(NamedTuple):
+    """relay_updates' result.  `ok[j]`: message j decoded (Verifier.decode_resident's status); `verdict[i]`,
+    `reason[i]`: pair i = (message rows[i], store store_index[i]); `dedup`: Verifier.last_dedup of the validation,
+    (pairs, distinct BLS items); `batch`: the fanned-out resident table batch, row i = pair i, the caller's to free —
+    Verifier.encode_resident(batch, kind, rows=np.flatnonzero(verdict)) serves the accepted pairs on."""
+    ok: np.ndarray
+    verdict: np.ndarray
+    reason: np.ndarray
+    dedup: Tuple[int, int]
+    batch: ResidentBatch
+
+
+def relay_updates(verifier: Verifier, messages, kind: str, fork, rows, store_index, current_slot: int,
+                  genesis_validators_root: bytes, dedup: bool = True) -> RelayResult:
+    """Wire messages in, one verdict per (message, store) pair out, no row on the host: decode_resident, (dedup)
+    classify_resident, fan_out(rows, store_index) and validate_resident against the store table that is set, under
+    set_dedup(dedup) — each distinct signature checked once — with the verifier's own setting restored afterwards.
+    `messages`, `kind`, `fork` as lcv.wire.decode_updates takes them; pair i is message rows[i] for the store of table
+    row store_index[i].  A malformed message is an all-zero row (ok False), and its pairs keep that row's verdict and
+    reason.  Synchronous; no other call may have slots in flight."""
+    ix = np.ascontiguousarray(rows, np.uint32).reshape(-1)
+    six = np.ascontiguousarray(store_index, np.uint32).reshape(-1)
+    if ix.shape != six.shape:
+        raise ValueError("one store_index per row")
+    decoded, ok = verifier.decode_resident(messages, kind, fork)
+    dedup_before = bool(verifier.dedup)
+    try:
+        if ix.size and ((ix >= decoded.n).any()):
+            raise ValueError(f"rows: message index out of range ({decoded.n} messages)")
+        if ix.size == 0:
+            return RelayResult(ok, np.zeros(0, bool), np.zeros(0, np.uint8), (0, 0), ResidentBatch(verifier, None, 0, True, decoded.npool))
+        if dedup:
+            verifier.classify_resident(decoded)
+        fanned = verifier.fan_out(decoded, ix, six)
+        try:
+            verifier.set_dedup(bool(dedup))
+            verdict, reason = verifier.validate_resident(fanned, current_slot, genesis_validators_root)
+            return RelayResult(ok, verdict.astype(bool), reason, verifier.last_dedup(), fanned)
+        except Exception:
+            fanned.free()
+            raise
+    finally:
+        decoded.free()
+        if verifier.dedup != dedup_before:
+            verifier.set_dedup(dedup_before)

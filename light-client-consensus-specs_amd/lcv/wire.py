@@ -155,10 +155,13 @@ def decode_updates(messages: Messages, kind: str = "update", fork="deneb",
     return batch
 
 
-def decode_updates_device(messages: Messages, kind: str = "update", fork="deneb", verifier=None, strict: bool = True):
+def decode_updates_device(messages: Messages, kind: str = "update", fork="deneb", verifier=None, strict: bool = True,
+                          classify: bool = False):
     """decode_updates on the device (lcv_batch_decode: the rows are written where validation reads them, the host
     never holds one) -> (ResidentBatch, ok).  `messages` and `fork` as decode_updates takes them.  With `strict`,
-    ValueError naming the first malformed indices, as decode_updates raises; the batch is freed first."""
+    ValueError naming the first malformed indices, as decode_updates raises; the batch is freed first.  With
+    `classify` the batch is classed on the device (Verifier.classify_resident), so that validation under set_dedup
+    checks each distinct signature once."""
     from .device import Verifier
     v = verifier if verifier is not None else Verifier(0)
     rb, ok = v.decode_resident(messages, kind, fork)
@@ -166,6 +169,8 @@ def decode_updates_device(messages: Messages, kind: str = "update", fork="deneb"
         rb.free()
         bad = np.flatnonzero(~ok)
         raise ValueError(f"malformed SSZ {kind} message(s) at index {bad[:8].tolist()}")
+    if classify:
+        v.classify_resident(rb)
     return rb, ok
 
 
