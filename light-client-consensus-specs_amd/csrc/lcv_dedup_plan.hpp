@@ -5,7 +5,8 @@
 //   dedup_classes  store-independent class of every row: rows with equal (attested beacon header, signature_slot,
 //                  sync_committee_bits, sync_committee_signature) get the index of the first such row
 //   dedup_plan     the grouping of one chunk: rows with equal (class, committee row) are one item
-//   dedup_confirm_groups  the host loop of a grouping whose full compares run elsewhere (on the device)
+//   dedup_confirm_groups  the host loop of a grouping whose full compares run elsewhere (on the device, on threads)
+//   dedup_pool_rows       the numbering of a decoded batch's committee pool (the host and the device wire decoders)
 // Both are one pass over an open-addressing table: O(n) expected.  Rows are merged only on a full compare of their
 // keys; the hash only picks where to look (hash_bits < 64 truncates it — 0 makes every row collide — so tests can
 // show that).
@@ -123,6 +124,30 @@ inline int dedup_confirm_groups(std::vector<uint32_t>& rep, std::vector<uint32_t
     pending.swap(next);
   }
   return 0;
+}
+
+// The committee pool of a decoded batch (lcv_ssz_decode_updates, lcv_batch_decode) from its grouping: rep[i] = the
+// first row whose committee equals row i's, or 0xffffffff for a row without one, which stands for SyncCommittee().
+// Pool rows are numbered in order of first occurrence and SyncCommittee() takes a row at its first use: index[i] =
+// row i's pool row, first[k] = the first row of pool row k, or 0xffffffff for the row of SyncCommittee().
+inline void dedup_pool_rows(const std::vector<uint32_t>& rep, uint32_t* index, std::vector<uint32_t>& first) {
+  const uint32_t none = 0xffffffffu;
+  uint32_t zero_ix = none;
+  first.clear();
+  for (uint32_t i = 0; i < (uint32_t)rep.size(); ++i) {
+    if (rep[i] == none) {
+      if (zero_ix == none) {
+        zero_ix = (uint32_t)first.size();
+        first.push_back(none);
+      }
+      index[i] = zero_ix;
+    } else if (rep[i] == i) {
+      index[i] = (uint32_t)first.size();
+      first.push_back(i);
+    } else {
+      index[i] = index[rep[i]];  // (rep[i] < i)
+    }
+  }
 }
 
 // The grouping of a chunk of n rows: row i has class cls[i] (any labels: equal labels = equal BLS inputs apart from

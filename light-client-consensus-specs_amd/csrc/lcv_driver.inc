@@ -394,7 +394,6 @@ template <class F> static int launch_sop(lcv_ctx* ctx, const F& f, uint32_t n, u
 // item (`rows`) and the kind, which names the kernels' own index function.  Allocation (ensure_work, ensure_dedup),
 // slicing (work_view) and the layout check (lcv_debug_work_check) are derived from these rows and those functions;
 // nothing else states a stride.  A new array is a new member and a new row here
-enum { K_BITS = 64, K_SIG = 96 };  // Bitvector[512], a compressed G2 point: the row widths lcv_ssz.hpp does not name
 enum FieldKind { FK_SOA, FK_F, FK_LINES, FK_POOL, FK_RANK, FK_SPACE, FK_ITEM };  // (field_index)
 struct Field { const char* name; size_t slot, esize, rows; FieldKind kind; };
 #define LCV_FIELD(T, m, rows, kind) {#m, offsetof(T, m), sizeof(*T().m), rows, kind}
@@ -2803,7 +2802,7 @@ int lcv_create_updates_resident(lcv_ctx* ctx, const lcv_state_views* states, uin
   if (out) *out = nullptr;
   if (!ctx || !states || !blocks || !committees || !cases || !reason_out || !out)
     return fail(ctx, LCV_EINVAL, std::string(who) + ": null argument");
-  if (kind < 0 || kind > 2) return fail(ctx, LCV_EINVAL, std::string(who) + ": kind is 0 (update), 1 (finality) or 2 (optimistic)");
+  if (!wire_kind_ok(kind)) return fail(ctx, LCV_EINVAL, std::string(who) + ": kind is 0 (update), 1 (finality) or 2 (optimistic)");
   if (n == 0) return LCV_OK;
   if (n >= 0xffffffffull) return fail(ctx, LCV_EINVAL, std::string(who) + ": need n < 2^32 - 1");
   if (!cases->state || !cases->block || !cases->attested_state || !cases->attested_block || !cases->finalized_block)
@@ -2940,12 +2939,11 @@ int lcv_create_bootstraps(lcv_ctx* ctx, const lcv_state_views* states, uint64_t 
 // The message areas are written into device scratch one chunk at a time and copied out before the scratch is reused:
 // at most LCV_ENCODE_SCRATCH_BYTES of areas, whatever the number of rows.  Copies and launches share one stream, so
 // a chunk's kernel starts after the previous chunk's areas have left.
-static const uint64_t kEncPitch[3] = {26880, 2096, 1040};
-static_assert(LCV_ENCODE_SCRATCH_BYTES >= 26880, "the scratch holds one message");
+static_assert(LCV_ENCODE_SCRATCH_BYTES >= wire_encode_pitch(WIRE_UPDATE), "the scratch holds one message");
 
 extern "C" {
 
-uint64_t lcv_encode_pitch(int kind) { return (kind >= 0 && kind <= 2) ? kEncPitch[kind] : 0; }
+uint64_t lcv_encode_pitch(int kind) { return wire_kind_ok(kind) ? wire_encode_pitch((uint32_t)kind) : 0; }
 
 int lcv_debug_set_encode_chunk(lcv_ctx* ctx, uint64_t rows) {
   if (!ctx) return LCV_EINVAL;
@@ -2958,8 +2956,8 @@ int lcv_batch_encode(lcv_ctx* ctx, lcv_dbatch* b, const uint32_t* rows, uint64_t
   const char* who = "lcv_batch_encode";
   if (!ctx || !b || !out || !len_out || !fork_out || !version_out || !status_out)
     return fail(ctx, LCV_EINVAL, std::string(who) + ": null argument");
-  if (kind < 0 || kind > 2) return fail(ctx, LCV_EINVAL, std::string(who) + ": kind is 0 (update), 1 (finality) or 2 (optimistic)");
-  if (fork < LCV_FORK_AUTO || fork > 2)
+  if (!wire_kind_ok(kind)) return fail(ctx, LCV_EINVAL, std::string(who) + ": kind is 0 (update), 1 (finality) or 2 (optimistic)");
+  if (fork != LCV_FORK_AUTO && !wire_fork_ok(fork))
     return fail(ctx, LCV_EINVAL, std::string(who) + ": fork is 0 (Deneb), 1 (Capella), 2 (Altair) or LCV_FORK_AUTO");
   if (rows) {
     if (nrows >= 0xffffffffull) return fail(ctx, LCV_EINVAL, std::string(who) + ": need nrows < 2^32 - 1");
@@ -2967,7 +2965,7 @@ int lcv_batch_encode(lcv_ctx* ctx, lcv_dbatch* b, const uint32_t* rows, uint64_t
   }
   const uint64_t m = rows ? nrows : b->n;
   if (m == 0) return LCV_OK;
-  const uint64_t pitch = kEncPitch[kind];
+  const uint64_t pitch = wire_encode_pitch((uint32_t)kind);
   uint64_t chunk = LCV_ENCODE_SCRATCH_BYTES / pitch;
   if (ctx->enc_chunk && ctx->enc_chunk < chunk) chunk = ctx->enc_chunk;
   if (m < chunk) chunk = m;
@@ -3006,8 +3004,8 @@ int lcv_encode_updates(lcv_ctx* ctx, const lcv_update_batch* batch, int kind, in
   const char* who = "lcv_encode_updates";
   if (!ctx || !batch || !out || !len_out || !fork_out || !version_out || !status_out)
     return fail(ctx, LCV_EINVAL, std::string(who) + ": null argument");
-  if (kind < 0 || kind > 2) return fail(ctx, LCV_EINVAL, std::string(who) + ": kind is 0 (update), 1 (finality) or 2 (optimistic)");
-  if (fork < LCV_FORK_AUTO || fork > 2)
+  if (!wire_kind_ok(kind)) return fail(ctx, LCV_EINVAL, std::string(who) + ": kind is 0 (update), 1 (finality) or 2 (optimistic)");
+  if (fork != LCV_FORK_AUTO && !wire_fork_ok(fork))
     return fail(ctx, LCV_EINVAL, std::string(who) + ": fork is 0 (Deneb), 1 (Capella), 2 (Altair) or LCV_FORK_AUTO");
   if (batch->n == 0) return LCV_OK;
   lcv_dbatch* db = nullptr;
@@ -3097,8 +3095,8 @@ int lcv_batch_decode(lcv_ctx* ctx, const uint8_t* buf, uint64_t buf_len, const u
   const std::string who = "lcv_batch_decode";
   if (out) *out = nullptr;
   if (!ctx || !buf || !offsets || !lengths || !status_out || !out) return fail(ctx, LCV_EINVAL, who + ": null argument");
-  if (kind < 0 || kind > 2) return fail(ctx, LCV_EINVAL, who + ": kind is 0 (update), 1 (finality) or 2 (optimistic)");
-  if (!forks && (fork < 0 || fork > 2)) return fail(ctx, LCV_EINVAL, who + ": fork is 0 (Deneb), 1 (Capella) or 2 (Altair)");
+  if (!wire_kind_ok(kind)) return fail(ctx, LCV_EINVAL, who + ": kind is 0 (update), 1 (finality) or 2 (optimistic)");
+  if (!forks && !wire_fork_ok(fork)) return fail(ctx, LCV_EINVAL, who + ": fork is 0 (Deneb), 1 (Capella) or 2 (Altair)");
   if (n > LCV_DECODE_MAX_ROWS)
     return fail(ctx, LCV_EINVAL, who + ": n = " + std::to_string(n) + " above LCV_DECODE_MAX_ROWS");
   uint64_t msg_bytes = 16;  // the zero padding behind the last message
@@ -3140,7 +3138,7 @@ int lcv_batch_decode(lcv_ctx* ctx, const uint8_t* buf, uint64_t buf_len, const u
     be_reset_timings(ctx);
     LCV_TRY(be_h2d(ctx, d, pin, S.stage_bytes));
     DecArgs A = {d, d + S.meta, d + S.rec, ProdOut{}, (uint32_t)kind, (uint32_t)DEC_PLAN};
-    if (kind == 0) {
+    if (kind == WIRE_UPDATE) {
       LCV_TRY(stage(ctx, ST_WIRE_DECODE, [&] { return be_launch_team(ctx, F_wire_dec{A}, (uint32_t)n); }));
       LCV_TRY(be_d2h(ctx, rec.data(), d + S.rec, n * DEC_REC_BYTES));
       LCV_TRY(be_sync(ctx));
@@ -3154,23 +3152,14 @@ int lcv_batch_decode(lcv_ctx* ctx, const uint8_t* buf, uint64_t buf_len, const u
         if (st || zero) continue;
         uint64_t o;
         memcpy(&o, pin + S.meta + DEC_META_BYTES * i, 8);
-        coff[i] = o + ((forks ? forks[i] : fork) == ENC_ALTAIR ? (uint64_t)K_BEACON : 4u);
+        coff[i] = o + wire_committee_off((forks ? forks[i] : fork) == WIRE_ALTAIR);
         cand.push_back((uint32_t)i);
       }
       LCV_TRY(dec_resolve_pool(ctx, d, S, cand, rec.data(), coff, rep));
-      // pool rows in order of first occurrence; SyncCommittee() takes a row at its first use
-      std::vector<uint32_t> ix(n, none);
-      uint32_t zero_ix = none;
+      std::vector<uint32_t> first;
+      dedup_pool_rows(rep, nsc_index.data(), first);
       pool_src.clear();
-      for (uint64_t i = 0; i < n; ++i) {
-        if (rep[i] == none) {
-          if (zero_ix == none) { zero_ix = (uint32_t)pool_src.size(); pool_src.push_back(DEC_NO_COMMITTEE); }
-          nsc_index[i] = zero_ix;
-        } else {
-          if (rep[i] == i) { ix[i] = (uint32_t)pool_src.size(); pool_src.push_back(coff[i]); }
-          nsc_index[i] = ix[rep[i]];
-        }
-      }
+      for (uint32_t f : first) pool_src.push_back(f == none ? DEC_NO_COMMITTEE : coff[f]);
     }
     const uint64_t npool = pool_src.size();
     // the batch: lcv_batch_upload's layout
@@ -3182,9 +3171,9 @@ int lcv_batch_decode(lcv_ctx* ctx, const uint8_t* buf, uint64_t buf_len, const u
     LCV_TRY(be_h2d(ctx, m + c.off[COL_NSC_INDEX], nsc_index.data(), 4 * n));
     A.O = prod_out(nb.db->B);
     A.phase = DEC_ROWS;
-    if (kind == 0) A.rec = nullptr;  // (the first pass left the records)
+    if (kind == WIRE_UPDATE) A.rec = nullptr;  // (the first pass left the records)
     LCV_TRY(stage(ctx, ST_WIRE_DECODE, [&] { return be_launch_team(ctx, F_wire_dec{A}, (uint32_t)n); }));
-    if (kind == 0) {
+    if (kind == WIRE_UPDATE) {
       LCV_TRY(be_h2d(ctx, d + S.pool_src, pool_src.data(), 8 * npool));
       const ScGatherArgs G = {d, (const uint64_t*)(d + S.pool_src), m + c.off[COL_NSC_POOL]};
       LCV_TRY(stage(ctx, ST_DECODE_POOL, [&] { return be_launch_team(ctx, F_sc_gather{G}, (uint32_t)npool); }));

@@ -8,19 +8,9 @@
 // (:220-240), hash_tree_root call sites (:427, :444, :463).
 #pragma once
 #include "lcv_sha.hpp"
+#include "lcv_wire_layout.hpp"  // the K_* sizes of the packed layouts
 
 namespace lcv {
-
-enum {
-  K_BEACON = 112,
-  K_EXEC = 832,
-  K_EXEC_BLOOM_OFF = 544,
-  K_EXEC_EXTRALEN_OFF = 800,
-  K_EXEC_BRANCH = 128,
-  K_NSC_BRANCH = 160,
-  K_FIN_BRANCH = 192,
-  K_SC = 24624,
-};
 
 // The network configuration the light-client path reads (lcv_set_config; mainnet by default): the
 // preset's SLOTS_PER_EPOCH and EPOCHS_PER_SYNC_COMMITTEE_PERIOD (UPDATE_TIMEOUT's factors,

@@ -1,175 +1,72 @@
-// SSZ wire decode of light-client messages into the packed SoA rows of include/lcv.h.
+// SSZ wire decode of light-client messages into the packed SoA rows of include/lcv.h, on the host.
 //
-// Containers (reference sync-protocol.md:96-101 LightClientHeader, :120-133 LightClientUpdate,
-// :138-148 LightClientFinalityUpdate, :153-160 LightClientOptimisticUpdate; Req/Resp and gossip
-// payloads p2p-interface.md) in SSZ wire form: fixed parts in field order, 4-byte little-endian
-// offsets for the variable-size fields (every LightClientHeader, because its ExecutionPayloadHeader
-// ends in extra_data: ByteList[32]).  Decoding is strict, as upstream SSZ deserialisation is: the
-// first offset must equal the fixed size, offsets are monotonic and in bounds, no trailing bytes,
-// extra_data <= 32 bytes.  A malformed message yields status 1 and an all-zero row.
+// The containers, their wire order and the rule for what is malformed are lcv_wire_layout.hpp's (the device decoder
+// and encoder read the same tables): decoding is strict, as upstream SSZ deserialisation is, and a malformed message
+// yields status 1 and an all-zero row.  This file maps the layout's columns to the columns of a batch (or to a
+// bootstrap's outputs) and walks the tables over one message.
 //
 // Finality / optimistic updates become the LightClientUpdate the reference builds from them
-// (sync-protocol.md:563-571 / :582-590): default next_sync_committee, zero next-committee branch,
-// and for optimistic updates a default finalized header and zero finality branch.
+// (sync-protocol.md:563-571 / :582-590): default next_sync_committee, zero next-committee branch, and for optimistic
+// updates a default finalized header and zero finality branch.  The row of an Altair-format message is the Capella
+// upgrade of its data (upgrade_lc_header_to_capella: empty execution and branch).
 //
-// Distinct next_sync_committee values are deduplicated by content (the device computes
-// HTR(SyncCommittee) once per pool row): pool_src[k] = byte offset in `buf` of pool row k's first
-// occurrence, or UINT64_MAX for SyncCommittee() (all zero).  Pure host code, no device work.
+// Distinct next_sync_committee values are deduplicated by content (the device computes HTR(SyncCommittee) once per
+// pool row): pool_src[k] = byte offset in `buf` of pool row k's first occurrence, or UINT64_MAX for SyncCommittee()
+// (all zero).  Pure host code, no device work.
 #include <cstdint>
 #include <cstring>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/lcv.h"
+#include "lcv_dedup_plan.hpp"
+#include "lcv_wire_layout.hpp"
 
 namespace {
 
-constexpr uint64_t kCommittee = 24624, kBeacon = 112, kExecRec = 832, kExecBranch = 128;
-constexpr uint64_t kNscBranch = 160, kFinBranch = 192, kBits = 64, kSig = 96;
-constexpr uint64_t kHeaderFixed = kBeacon + 4 + kExecBranch;  // 244
-constexpr uint64_t kExtraOffPos = 436;                        // extra_data offset inside the exec header
-constexpr uint64_t kMaxExtra = 32;
+using namespace lcv;
 
 inline uint32_t rd32(const uint8_t* p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
 
-// ExecutionPayloadHeader (Deneb 17 fields / Capella 15) -> 832 B record (layout: include/lcv.h)
-bool decode_exec(const uint8_t* p, uint64_t len, bool deneb, uint8_t* rec) {
-  const uint64_t fixed = deneb ? 584 : 568;
-  if (len < fixed || rd32(p + kExtraOffPos) != fixed) return false;
-  const uint64_t elen = len - fixed;
-  if (elen > kMaxExtra) return false;
-  std::memset(rec, 0, kExecRec);
-  uint64_t o = 0;
-  auto chunk = [&](int leaf, uint64_t n) { std::memcpy(rec + 32 * leaf, p + o, n); o += n; };
-  chunk(0, 32);                                   // parent_hash
-  chunk(1, 20);                                   // fee_recipient
-  chunk(2, 32);                                   // state_root
-  chunk(3, 32);                                   // receipts_root
-  std::memcpy(rec + 544, p + o, 256); o += 256;   // logs_bloom
-  chunk(5, 32);                                   // prev_randao
-  chunk(6, 8); chunk(7, 8); chunk(8, 8); chunk(9, 8);  // block_number, gas_limit, gas_used, timestamp
-  o += 4;                                         // extra_data offset (checked above)
-  chunk(11, 32);                                  // base_fee_per_gas (uint256 LE)
-  chunk(12, 32);                                  // block_hash
-  chunk(13, 32);                                  // transactions_root
-  chunk(14, 32);                                  // withdrawals_root
-  if (deneb) { chunk(15, 8); chunk(16, 8); }      // blob_gas_used, excess_blob_gas
-  std::memcpy(rec + 32 * 10, p + fixed, elen);    // extra_data
-  const uint32_t e32 = (uint32_t)elen;
-  std::memcpy(rec + 800, &e32, 4);
-  return true;
+// where one message's pieces go: p[column][part of a header's columns], null for a piece that is not stored
+struct Dest { uint8_t* p[WC_COLS][WH_PARTS]; };
+constexpr uint32_t kColBytes[WC_COLS][WH_PARTS] = {
+    {K_BEACON, K_EXEC, K_EXEC_BRANCH}, {K_SC}, {K_NSC_BRANCH}, {K_BEACON, K_EXEC, K_EXEC_BRANCH}, {K_FIN_BRANCH}, {K_BITS}, {K_SIG}, {8}};
+
+// row i of a batch (its committee goes to the pool, by content: no column of the row)
+Dest row_of(const lcv_update_batch* b, uint64_t i) {
+  const void* col[WC_COLS][WH_PARTS] = {
+      {b->attested.beacon, b->attested.execution, b->attested.exec_branch}, {}, {b->nsc_branch},
+      {b->finalized.beacon, b->finalized.execution, b->finalized.exec_branch}, {b->finality_branch}, {b->sync_bits},
+      {b->sync_signature}, {b->signature_slot}};
+  Dest d;
+  for (int c = 0; c < WC_COLS; ++c)
+    for (int h = 0; h < WH_PARTS; ++h)
+      d.p[c][h] = col[c][h] ? static_cast<uint8_t*>(const_cast<void*>(col[c][h])) + i * kColBytes[c][h] : nullptr;
+  return d;
 }
 
-// LightClientHeader: beacon (112) | offset(execution) | execution_branch (128) | execution
-bool decode_header(const uint8_t* p, uint64_t len, bool deneb, uint8_t* beacon, uint8_t* rec, uint8_t* branch) {
-  if (len < kHeaderFixed || rd32(p + kBeacon) != kHeaderFixed) return false;
-  if (!decode_exec(p + kHeaderFixed, len - kHeaderFixed, deneb, rec)) return false;
-  std::memcpy(beacon, p, kBeacon);
-  std::memcpy(branch, p + kBeacon + 4, kExecBranch);
-  return true;
-}
-
-struct Row {
-  const lcv_update_batch* b;
-  uint64_t i;
-  uint8_t* at(const uint8_t* col, uint64_t w) const { return const_cast<uint8_t*>(col) + i * w; }
-};
-
-void zero_row(const Row& r) {
-  const lcv_update_batch* b = r.b;
-  std::memset(r.at(b->attested.beacon, kBeacon), 0, kBeacon);
-  std::memset(r.at(b->attested.execution, kExecRec), 0, kExecRec);
-  std::memset(r.at(b->attested.exec_branch, kExecBranch), 0, kExecBranch);
-  std::memset(r.at(b->finalized.beacon, kBeacon), 0, kBeacon);
-  std::memset(r.at(b->finalized.execution, kExecRec), 0, kExecRec);
-  std::memset(r.at(b->finalized.exec_branch, kExecBranch), 0, kExecBranch);
-  std::memset(r.at(b->nsc_branch, kNscBranch), 0, kNscBranch);
-  std::memset(r.at(b->finality_branch, kFinBranch), 0, kFinBranch);
-  std::memset(r.at(b->sync_bits, kBits), 0, kBits);
-  std::memset(r.at(b->sync_signature, kSig), 0, kSig);
-  const_cast<uint64_t*>(b->signature_slot)[r.i] = 0;
-}
-
-enum { FORK_DENEB = 0, FORK_CAPELLA = 1, FORK_ALTAIR = 2 };
-
-// Altair-format messages (ALTAIR .. BELLATRIX fork versions, p2p-interface.md:82-85, 112-115, 157-160,
-// 197-200): LightClientHeader = {beacon} is fixed-size, so every container is fixed-size.  The rows
-// are the Capella upgrade of the data (upgrade_lc_header_to_capella: empty execution and branch).
-bool decode_one_altair(const uint8_t* p, uint64_t len, int kind, const Row& r, uint64_t* committee) {
-  const lcv_update_batch* b = r.b;
-  const uint64_t size = kind == 0 ? kBeacon + kCommittee + kNscBranch + kBeacon + kFinBranch + kBits + kSig + 8
-                        : kind == 1 ? kBeacon + kBeacon + kFinBranch + kBits + kSig + 8
-                                    : kBeacon + kBits + kSig + 8;
-  if (len != size) return false;
-  uint64_t pos = 0;
-  std::memcpy(r.at(b->attested.beacon, kBeacon), p, kBeacon);
-  pos += kBeacon;
-  if (kind == 0) {
-    *committee = pos;
-    pos += kCommittee;
-    std::memcpy(r.at(b->nsc_branch, kNscBranch), p + pos, kNscBranch);
-    pos += kNscBranch;
-  }
-  if (kind != 2) {
-    std::memcpy(r.at(b->finalized.beacon, kBeacon), p + pos, kBeacon);
-    pos += kBeacon;
-    std::memcpy(r.at(b->finality_branch, kFinBranch), p + pos, kFinBranch);
-    pos += kFinBranch;
-  }
-  std::memcpy(r.at(b->sync_bits, kBits), p + pos, kBits);
-  pos += kBits;
-  std::memcpy(r.at(b->sync_signature, kSig), p + pos, kSig);
-  pos += kSig;
-  uint64_t slot;
-  std::memcpy(&slot, p + pos, 8);
-  const_cast<uint64_t*>(b->signature_slot)[r.i] = slot;
-  return true;
-}
-
-// Decodes one message into row r; *committee = offset (within the message) of next_sync_committee,
-// or UINT64_MAX when the message carries none.
-bool decode_one(const uint8_t* p, uint64_t len, int kind, int fork, const Row& r, uint64_t* committee) {
-  const lcv_update_batch* b = r.b;
-  *committee = UINT64_MAX;
-  if (fork == FORK_ALTAIR) return decode_one_altair(p, len, kind, r, committee);
-  const bool deneb = fork == FORK_DENEB;
-  uint64_t fixed, att_off_pos, fin_off_pos = 0, pos;
-  if (kind == 0) fixed = 4 + kCommittee + kNscBranch + 4 + kFinBranch + kBits + kSig + 8;  // 25152
-  else if (kind == 1) fixed = 4 + 4 + kFinBranch + kBits + kSig + 8;                       // 368
-  else fixed = 4 + kBits + kSig + 8;                                                       // 172
-  if (len < fixed || rd32(p) != fixed) return false;
-  att_off_pos = 0;
-  pos = 4;
-  if (kind == 0) {
-    *committee = pos;
-    pos += kCommittee;
-    std::memcpy(r.at(b->nsc_branch, kNscBranch), p + pos, kNscBranch);
-    pos += kNscBranch;
-  }
-  if (kind != 2) {
-    fin_off_pos = pos;
-    pos += 4;
-    std::memcpy(r.at(b->finality_branch, kFinBranch), p + pos, kFinBranch);
-    pos += kFinBranch;
-  }
-  std::memcpy(r.at(b->sync_bits, kBits), p + pos, kBits);
-  pos += kBits;
-  std::memcpy(r.at(b->sync_signature, kSig), p + pos, kSig);
-  pos += kSig;
-  uint64_t slot;
-  std::memcpy(&slot, p + pos, 8);
-  const_cast<uint64_t*>(b->signature_slot)[r.i] = slot;
-  const uint64_t a0 = rd32(p + att_off_pos);
-  const uint64_t a1 = kind == 2 ? len : rd32(p + fin_off_pos);
-  if (a1 < a0 || a1 > len) return false;
-  if (!decode_header(p + a0, a1 - a0, deneb, r.at(b->attested.beacon, kBeacon),
-                     r.at(b->attested.execution, kExecRec), r.at(b->attested.exec_branch, kExecBranch)))
-    return false;
-  if (kind != 2 &&
-      !decode_header(p + a1, len - a1, deneb, r.at(b->finalized.beacon, kBeacon),
-                     r.at(b->finalized.execution, kExecRec), r.at(b->finalized.exec_branch, kExecBranch)))
-    return false;
+// Decodes one message into d, which is left all zero if the message is malformed; *committee = the offset within the
+// message of its committee (the kinds that carry one)
+bool decode_msg(const uint8_t* p, uint64_t len, uint32_t kind, uint32_t fork, const Dest& d, uint64_t* committee) {
+  for (int c = 0; c < WC_COLS; ++c)
+    for (int h = 0; h < WH_PARTS; ++h)
+      if (d.p[c][h]) std::memset(d.p[c][h], 0, kColBytes[c][h]);
+  const WirePlan plan = wire_accept(kind, fork, len, [p](uint32_t o) { return rd32(p + o); });
+  if (plan.status) return false;
+  auto seg = [&](uint32_t col, uint32_t part, uint32_t rec, uint32_t o, uint32_t n) {
+    if (col == WC_COMMITTEE) *committee = o;
+    if (d.p[col][part]) std::memcpy(d.p[col][part] + rec, p + o, n);
+  };
+  auto put = [](uint32_t, uint32_t) {};  // (the offsets were wire_accept's to check)
+  auto header = [&](uint32_t col, uint32_t o, uint32_t elen) {
+    wire_walk_header(col, o, fork == WIRE_DENEB, elen, seg, put);
+    std::memcpy(d.p[col][WH_EXEC] + K_EXEC_EXTRALEN_OFF, &elen, 4);
+  };
+  wire_walk_fixed(kind, fork == WIRE_ALTAIR, false, 0u, 0u, seg, put, [](uint32_t, uint32_t, uint32_t) { return false; });  // (columns apart)
+  if (fork == WIRE_ALTAIR) return true;
+  header(WC_ATT, plan.att_off, plan.elen_att);
+  if (wire_has(WC_FIN, kind)) header(WC_FIN, plan.fin_off, plan.elen_fin);
   return true;
 }
 
@@ -186,7 +83,7 @@ uint64_t committee_key(const uint8_t* p) {
     }
   };
   mix(p);
-  mix(p + kCommittee - 48);
+  mix(p + K_SC - 48);
   return h;
 }
 
@@ -226,74 +123,58 @@ static int decode_updates(const uint8_t* buf, const uint64_t* offsets, const uin
                           ForkOf fork_of, const lcv_update_batch* out, uint64_t* pool_src, uint64_t* npool_out,
                           uint8_t* status) {
   if ((n && (!buf || !offsets || !lengths || !out || !pool_src || !status)) || !npool_out) return LCV_EINVAL;
-  if (kind < 0 || kind > 2) return LCV_EINVAL;
-  if (n && (!out->attested.beacon || !out->attested.execution || !out->attested.exec_branch ||
-            !out->finalized.beacon || !out->finalized.execution || !out->finalized.exec_branch ||
-            !out->nsc_index || !out->nsc_branch || !out->finality_branch || !out->sync_bits ||
-            !out->sync_signature || !out->signature_slot))
-    return LCV_EINVAL;
+  if (!wire_kind_ok(kind) || n >= 0xffffffffull) return LCV_EINVAL;  // (rows are numbered in 32 bits: nsc_index)
+  if (n) {
+    const Dest d = row_of(out, 0);
+    for (int c = 0; c < WC_COLS; ++c)
+      for (int h = 0; h < WH_PARTS; ++h)
+        if (c != WC_COMMITTEE && kColBytes[c][h] && !d.p[c][h]) return LCV_EINVAL;
+    if (!out->nsc_index) return LCV_EINVAL;
+  }
   constexpr uint64_t kNone = UINT64_MAX;
+  constexpr uint32_t none = 0xffffffffu;
   std::vector<uint64_t> csrc(n, kNone), key(n, 0);  // committee offset in buf (kNone: SyncCommittee())
   // 1. decode every row (parallel)
   parallel_rows(n, [&](uint64_t lo, uint64_t hi) {
     for (uint64_t i = lo; i < hi; ++i) {
-      const Row r{out, i};
-      zero_row(r);
       uint64_t c = kNone;
-      const int fork = fork_of(i);
-      const bool ok = fork >= FORK_DENEB && fork <= FORK_ALTAIR &&
-                      decode_one(buf + offsets[i], lengths[i], kind, fork, r, &c);
+      const bool ok = decode_msg(buf + offsets[i], lengths[i], (uint32_t)kind, (uint32_t)fork_of(i), row_of(out, i), &c);
       status[i] = ok ? 0 : 1;
-      if (!ok) {
-        zero_row(r);
-        continue;
-      }
-      if (c != kNone && !all_zero(buf + offsets[i] + c, kCommittee)) {
+      if (ok && c != kNone && !all_zero(buf + offsets[i] + c, K_SC)) {
         csrc[i] = offsets[i] + c;
         key[i] = committee_key(buf + csrc[i]);
       }
     }
   });
-  // 2. pool rows in first-occurrence order; each row tentatively takes the first pool row of its key
-  uint32_t* nsc_index = const_cast<uint32_t*>(out->nsc_index);
-  std::unordered_map<uint64_t, std::vector<uint32_t>> seen;
-  uint64_t npool = 0;
-  int64_t zero_ix = -1;  // pool row of SyncCommittee(), created on first use
-  for (uint64_t i = 0; i < n; ++i) {
-    if (csrc[i] == kNone) {
-      if (zero_ix < 0) { zero_ix = (int64_t)npool; pool_src[npool++] = kNone; }
-      nsc_index[i] = (uint32_t)zero_ix;
-      continue;
-    }
-    std::vector<uint32_t>& cands = seen[key[i]];
-    if (cands.empty()) { cands.push_back((uint32_t)npool); pool_src[npool++] = csrc[i]; }
-    nsc_index[i] = cands[0];
-  }
-  // 3. confirm every tentative assignment with a full compare (parallel)
-  std::vector<uint8_t> mismatch(n, 0);
-  parallel_rows(n, [&](uint64_t lo, uint64_t hi) {
-    for (uint64_t i = lo; i < hi; ++i)
-      if (csrc[i] != kNone && pool_src[nsc_index[i]] != csrc[i])
-        mismatch[i] = std::memcmp(buf + pool_src[nsc_index[i]], buf + csrc[i], kCommittee) != 0;
+  // 2. rep[i] = the first row whose committee equals row i's: the rows grouped by their sampled key alone, then every
+  // row but a group's first compared in full with its tentative representative (parallel); rows that differ (distinct
+  // committees sharing first and aggregate pubkeys) form the next group under their lowest row
+  std::vector<uint32_t> rep(n, none), cand, pending, first;
+  for (uint64_t i = 0; i < n; ++i)
+    if (csrc[i] != kNone) cand.push_back((uint32_t)i);
+  DedupTable table;
+  dedup_group(
+      (uint32_t)cand.size(), 64, table, [&](uint32_t j) { return key[cand[j]]; }, [](uint32_t, uint32_t) { return true; },
+      [&](uint32_t j) { rep[cand[j]] = cand[j]; }, [&](uint32_t a, uint32_t j) { rep[cand[j]] = cand[a]; });
+  for (uint32_t r : cand)
+    if (rep[r] != r) pending.push_back(r);
+  dedup_confirm_groups(rep, pending, [&](const std::vector<uint32_t>& pend, const std::vector<uint32_t>& rp, std::vector<uint32_t>& differ) {
+    parallel_rows(pend.size(), [&](uint64_t lo, uint64_t hi) {
+      for (uint64_t k = lo; k < hi; ++k) differ[k] = std::memcmp(buf + csrc[pend[k]], buf + csrc[rp[pend[k]]], K_SC) != 0;
+    });
+    return 0;
   });
-  // 4. sampled-key collisions (distinct committees sharing first and aggregate pubkeys): exact search
-  for (uint64_t i = 0; i < n; ++i) {
-    if (!mismatch[i]) continue;
-    std::vector<uint32_t>& cands = seen[key[i]];
-    int64_t hit = -1;
-    for (uint32_t k : cands)
-      if (std::memcmp(buf + pool_src[k], buf + csrc[i], kCommittee) == 0) { hit = k; break; }
-    if (hit < 0) { hit = (int64_t)npool; cands.push_back((uint32_t)npool); pool_src[npool++] = csrc[i]; }
-    nsc_index[i] = (uint32_t)hit;
-  }
-  *npool_out = npool;
+  // 3. pool rows in first-occurrence order
+  dedup_pool_rows(rep, const_cast<uint32_t*>(out->nsc_index), first);
+  for (size_t k = 0; k < first.size(); ++k) pool_src[k] = first[k] == none ? kNone : csrc[first[k]];
+  *npool_out = first.size();
   return LCV_OK;
 }
 
 extern "C" int lcv_ssz_decode_updates(const uint8_t* buf, const uint64_t* offsets, const uint64_t* lengths,
                                       uint64_t n, int kind, int fork, const lcv_update_batch* out,
                                       uint64_t* pool_src, uint64_t* npool_out, uint8_t* status) {
-  if (fork < FORK_DENEB || fork > FORK_ALTAIR) return LCV_EINVAL;
+  if (!wire_fork_ok(fork)) return LCV_EINVAL;
   return decode_updates(buf, offsets, lengths, n, kind, [fork](uint64_t) { return fork; }, out, pool_src, npool_out,
                         status);
 }
@@ -306,39 +187,21 @@ extern "C" int lcv_ssz_decode_updates_mixed(const uint8_t* buf, const uint64_t* 
                         npool_out, status);
 }
 
-// LightClientBootstrap (sync-protocol.md:109-115): header (offset) | current_sync_committee (24624) |
-// current_sync_committee_branch (5 x 32) | header.  Input of initialize_light_client_store (:351-373).
+// LightClientBootstrap (sync-protocol.md:109-115; the layout's kind WIRE_BOOTSTRAP): input of
+// initialize_light_client_store (:351-373)
 extern "C" int lcv_ssz_decode_bootstrap(const uint8_t* buf, uint64_t len, int fork, uint8_t* beacon112,
                                         uint8_t* exec832, uint8_t* exec_branch128, uint8_t* committee24624,
                                         uint8_t* committee_branch160, uint8_t* status) {
   if (!buf || !beacon112 || !exec832 || !exec_branch128 || !committee24624 || !committee_branch160 || !status)
     return LCV_EINVAL;
-  if (fork < FORK_DENEB || fork > FORK_ALTAIR) return LCV_EINVAL;
-  constexpr uint64_t fixed = 4 + kCommittee + kNscBranch;  // 24788
-  bool ok;
-  uint64_t cpos = 4;
-  if (fork == FORK_ALTAIR) {  // header (112, fixed) | committee | branch
-    ok = len == kBeacon + kCommittee + kNscBranch;
-    if (ok) {
-      std::memcpy(beacon112, buf, kBeacon);
-      std::memset(exec832, 0, kExecRec);
-      std::memset(exec_branch128, 0, kExecBranch);
-    }
-    cpos = kBeacon;
-  } else {
-    ok = len >= fixed && rd32(buf) == fixed &&
-         decode_header(buf + fixed, len - fixed, fork == FORK_DENEB, beacon112, exec832, exec_branch128);
-  }
-  if (ok) {
-    std::memcpy(committee24624, buf + cpos, kCommittee);
-    std::memcpy(committee_branch160, buf + cpos + kCommittee, kNscBranch);
-  } else {
-    std::memset(beacon112, 0, kBeacon);
-    std::memset(exec832, 0, kExecRec);
-    std::memset(exec_branch128, 0, kExecBranch);
-    std::memset(committee24624, 0, kCommittee);
-    std::memset(committee_branch160, 0, kNscBranch);
-  }
-  *status = ok ? 0 : 1;
+  if (!wire_fork_ok(fork)) return LCV_EINVAL;
+  Dest d = {};
+  d.p[WC_ATT][WH_BEACON] = beacon112;
+  d.p[WC_ATT][WH_EXEC] = exec832;
+  d.p[WC_ATT][WH_BRANCH] = exec_branch128;
+  d.p[WC_COMMITTEE][0] = committee24624;
+  d.p[WC_NSC_BRANCH][0] = committee_branch160;
+  uint64_t c;
+  *status = decode_msg(buf, len, WIRE_BOOTSTRAP, (uint32_t)fork, d, &c) ? 0 : 1;
   return LCV_OK;
 }

@@ -1,7 +1,7 @@
 // lcv_wire_dec.hpp — SSZ wire messages into the rows of a resident batch on the device (lcv_batch_decode,
-// include/lcv.h): F_wire_enc (lcv_wire_enc.hpp) run backwards.  csrc/lcv_wire.cpp (decode_one, decode_header,
-// decode_exec) is the definition of the rows and of what is malformed; the offsets inside a message are a peer's, so
-// every one of them is checked against the message's length before anything is read through it.
+// include/lcv.h): F_wire_enc (lcv_wire_enc.hpp) run backwards.  lcv_wire_layout.hpp describes the containers and what
+// is malformed (wire_accept, which the host decoder lcv_wire.cpp runs too); the offsets inside a message are a
+// peer's, so every one of them is checked against the message's length before anything is read through it.
 //
 // The driver stages message i at a 16-byte aligned offset of one device scratch and hands the kernels
 // (dev_off[i], len[i], fork[i]) (DEC_META_BYTES per message).  Three functors, 64-lane teams:
@@ -11,7 +11,7 @@
 //            decided from `len` alone, before any load; else the message WITHOUT its committee, global -> LDS
 //            "image" in aligned 16-byte loads (K_SC is a multiple of 16, so a byte behind the committee keeps its
 //            offset modulo 16).  No load starts at or past dev_off + round_up(len, 16)
-//   round 1  every lane derives the same plan from the image (the host decoder's checks; offsets compared as
+//   round 1  every lane derives the same plan from the image (wire_accept, the host decoder's rule; offsets compared as
 //            unsigned values against the length, never added to anything first); lane 0 keeps the status in DEC_CTL
 //            and stores the row's 16-byte record; the team moves the pieces image -> raw inside LDS, 4 bytes at a
 //            time, or 1 where an offset or a length is odd (the finalized header starts at any residue).  Only bytes
@@ -41,32 +41,11 @@ enum : uint32_t {
   DEC_REC_BYTES = 16,   // per row: u32 status, u32 zero (no committee, or an all-zero one), u64 committee hash
   DEC_PAIR_BYTES = 16,  // F_sc_confirm: two u64 scratch offsets of committees
   DEC_PLAN = 0, DEC_ROWS = 1,
-  DEC_HEADER_FIXED = K_BEACON + 4 + K_EXEC_BRANCH,  // 244
-  DEC_EXTRA_OFF_POS = 436,                          // extra_data's offset field inside an ExecutionPayloadHeader
-  DEC_MAX_EXTRA = 32,
 };
 constexpr uint64_t DEC_NO_COMMITTEE = ~0ull;
 static_assert(DEC_RAW_BYTES % 16 == 0 && DEC_IMG % 16 == 0, "16-byte LDS words");
 static_assert(ENC_R_FIN % 16 == 0 && ENC_H_EXEC % 16 == 0 && ENC_H_BRANCH % 16 == 0 && ENC_R_NSC_BRANCH % 16 == 0 &&
               ENC_R_FIN_BRANCH % 16 == 0 && ENC_R_BITS % 16 == 0 && ENC_R_SIG % 16 == 0, "raw pieces leave in 16-byte words");
-
-// fixed part of a Deneb / Capella message (the committee included), and the size of an Altair-format one
-LCV_FN uint32_t dec_fixed(uint32_t kind) { return kind == (uint32_t)ENC_KIND_UPDATE ? 528u + K_SC : kind == (uint32_t)ENC_KIND_FINALITY ? 368u : 172u; }
-LCV_FN uint32_t dec_altair_size(uint32_t kind) {
-  return kind == (uint32_t)ENC_KIND_UPDATE ? 2u * K_BEACON + K_SC + K_NSC_BRANCH + K_FIN_BRANCH + ENC_TAIL_BYTES
-         : kind == (uint32_t)ENC_KIND_FINALITY ? 2u * K_BEACON + K_FIN_BRANCH + ENC_TAIL_BYTES
-                                               : K_BEACON + ENC_TAIL_BYTES;
-}
-LCV_FN uint32_t dec_exec_fixed(uint32_t fork) { return fork == (uint32_t)ENC_DENEB ? 584u : 568u; }
-// can a message of this kind and fork have this length?  (decided before any load: a longer one fits no image)
-LCV_FN bool dec_len_ok(uint32_t kind, uint32_t fork, uint32_t len) {
-  if (fork > (uint32_t)ENC_ALTAIR) return false;
-  if (fork == (uint32_t)ENC_ALTAIR) return len == dec_altair_size(kind);
-  const uint32_t fixed = dec_fixed(kind);
-  const uint32_t hmax = DEC_HEADER_FIXED + dec_exec_fixed(fork) + DEC_MAX_EXTRA;
-  return len >= fixed && len <= fixed + (kind == (uint32_t)ENC_KIND_OPTIMISTIC ? hmax : 2u * hmax);
-}
-static_assert(528 + 2 * (244 + 584 + 32) + 16 <= DEC_IMG_BYTES, "the image holds the longest message without its committee");
 
 LCV_FN uint32_t dec_rd32(const uint8_t* img, uint32_t o) {
   return (uint32_t)img[o] | ((uint32_t)img[o + 1] << 8) | ((uint32_t)img[o + 2] << 16) | ((uint32_t)img[o + 3] << 24);
@@ -86,76 +65,14 @@ LCV_FN DecMeta dec_meta(const uint8_t* meta, uint32_t i) {
   return r;
 }
 
-// the message's layout in the image (the committee cut out); the same value on every lane.  hatt / hfin: offset
-// and length of the two headers in the image
-struct DecPlan { uint32_t status, att_off, att_len, fin_off, fin_len, elen_att, elen_fin; };
-
-// LightClientHeader of hlen bytes at img[h ..): decode_header's and decode_exec's checks; every read lies below
-// h + 244 + 568 <= h + hlen
-LCV_FN bool dec_header_ok(const uint8_t* img, uint32_t h, uint32_t hlen, uint32_t efixed, uint32_t* elen) {
-  if (hlen < DEC_HEADER_FIXED + efixed) return false;
-  if (dec_rd32(img, h + K_BEACON) != DEC_HEADER_FIXED) return false;
-  if (dec_rd32(img, h + DEC_HEADER_FIXED + DEC_EXTRA_OFF_POS) != efixed) return false;
-  const uint32_t e = hlen - DEC_HEADER_FIXED - efixed;
-  if (e > DEC_MAX_EXTRA) return false;
-  *elen = e;
-  return true;
-}
-
-// (dec_len_ok holds: fixed <= len <= fixed + two longest headers)
-LCV_FN DecPlan dec_plan(const uint8_t* img, uint32_t kind, uint32_t fork, uint32_t len) {
-  DecPlan p = {1u, 0u, 0u, 0u, 0u, 0u, 0u};
-  const uint32_t fixed = dec_fixed(kind), cut = kind == (uint32_t)ENC_KIND_UPDATE ? (uint32_t)K_SC : 0u;
-  const uint32_t a0 = dec_rd32(img, 0);
-  if (a0 != fixed) return p;
-  // the second offset: any 32-bit value (0x80000000, 0xFFFFFFFF): compared, never added to
-  const uint32_t a1 = kind == (uint32_t)ENC_KIND_OPTIMISTIC ? len
-                                                             : dec_rd32(img, kind == (uint32_t)ENC_KIND_UPDATE ? 4u + K_NSC_BRANCH : 4u);
-  if (a1 < a0 || a1 > len) return p;
-  p.att_off = fixed - cut;
-  p.att_len = a1 - a0;
-  p.fin_off = a1 - cut;
-  p.fin_len = len - a1;
-  const uint32_t efixed = dec_exec_fixed(fork);
-  if (!dec_header_ok(img, p.att_off, p.att_len, efixed, &p.elen_att)) return p;
-  if (kind != (uint32_t)ENC_KIND_OPTIMISTIC && !dec_header_ok(img, p.fin_off, p.fin_len, efixed, &p.elen_fin)) return p;
-  p.status = 0u;
-  return p;
-}
-
 // ---- round 1's moves inside LDS: img[src .. src + len) -> raw[dst ..), the team's lanes striding over dwords, or
 // over bytes where src or len is no multiple of 4 (dst always is)
-LCV_FN uint32_t dec_seg(uint8_t* raw, uint32_t dst, const uint8_t* img, uint32_t src, uint32_t len, uint32_t lane) {
+LCV_FN void dec_seg(uint8_t* raw, uint32_t dst, const uint8_t* img, uint32_t src, uint32_t len, uint32_t lane) {
   if (((src | len) & 3u) == 0u) {
     for (uint32_t k = lane; k < len / 4; k += DEC_TEAM) ((uint32_t*)(raw + dst))[k] = ((const uint32_t*)(img + src))[k];
   } else {
     for (uint32_t k = lane; k < len; k += DEC_TEAM) raw[dst + k] = img[src + k];
   }
-  return src + len;
-}
-// enc_header backwards: the header at img[o ..) into the raw header at raw[h ..) (the record's gaps stay zero)
-LCV_FN void dec_header(uint8_t* raw, uint32_t h, const uint8_t* img, uint32_t o, bool deneb, uint32_t elen, uint32_t lane) {
-  const uint32_t e = h + ENC_H_EXEC;
-  o = dec_seg(raw, h + ENC_H_BEACON, img, o, K_BEACON, lane);
-  o += 4;  // the offset of `execution`
-  o = dec_seg(raw, h + ENC_H_BRANCH, img, o, K_EXEC_BRANCH, lane);
-  o = dec_seg(raw, e + 0, img, o, 32, lane);     // parent_hash
-  o = dec_seg(raw, e + 32, img, o, 20, lane);    // fee_recipient
-  o = dec_seg(raw, e + 64, img, o, 64, lane);    // state_root, receipts_root
-  o = dec_seg(raw, e + K_EXEC_BLOOM_OFF, img, o, 256, lane);
-  o = dec_seg(raw, e + 160, img, o, 32, lane);   // prev_randao
-  o = dec_seg(raw, e + 192, img, o, 8, lane);    // block_number
-  o = dec_seg(raw, e + 224, img, o, 8, lane);    // gas_limit
-  o = dec_seg(raw, e + 256, img, o, 8, lane);    // gas_used
-  o = dec_seg(raw, e + 288, img, o, 8, lane);    // timestamp
-  o += 4;  // the offset of extra_data
-  o = dec_seg(raw, e + 352, img, o, 128, lane);  // base_fee_per_gas, block_hash, transactions_root, withdrawals_root
-  if (deneb) {
-    o = dec_seg(raw, e + 480, img, o, 8, lane);  // blob_gas_used
-    o = dec_seg(raw, e + 512, img, o, 8, lane);  // excess_blob_gas
-  }
-  dec_seg(raw, e + 320, img, o, elen, lane);
-  if (lane == 0) *(uint32_t*)(raw + e + K_EXEC_EXTRALEN_OFF) = elen;
 }
 
 // round 2's move: 16-byte words LDS -> global, zeros for a malformed row
@@ -175,19 +92,20 @@ struct DecArgs {
   uint32_t kind, phase;
 };
 
-LCV_FN void item_wire_dec(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, const DecArgs& A) {
+// (`kind` is A.kind as a constant of the call: one instance per kind, as F_wire_enc)
+LCV_FN void item_wire_dec(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, const DecArgs& A, const uint32_t kind) {
   uint8_t* raw = (uint8_t*)lds;
   uint8_t* img = raw + DEC_IMG;
-  const uint32_t kind = A.kind;
   const DecMeta M = dec_meta(A.meta, i);
-  const bool upd = kind == (uint32_t)ENC_KIND_UPDATE, altair = M.fork == (uint32_t)ENC_ALTAIR;
-  const uint32_t coff = altair ? (uint32_t)K_BEACON : 4u;  // an update's committee, in the message
+  const bool upd = wire_has(WC_COMMITTEE, kind), altair = M.fork == (uint32_t)WIRE_ALTAIR;
+  const uint32_t coff = wire_committee_off(altair);  // an update's committee, in the message
+  const uint32_t cut = upd ? (uint32_t)K_SC : 0u;    // what the image leaves out
   if (r == 0) {
     const q128 z = {0u, 0u, 0u, 0u};
     for (uint32_t k = lane; k < DEC_RAW_BYTES / 16; k += DEC_TEAM) st_q128(raw, k, z);
-    if (!dec_len_ok(kind, M.fork, M.len)) return;
+    if (!wire_len_ok(kind, M.fork, M.len)) return;  // a length the kind and fork cannot have fits no image
     const uint8_t* src = A.stage + M.off;
-    const uint32_t imglen = M.len - (upd ? (uint32_t)K_SC : 0u);
+    const uint32_t imglen = M.len - cut;
     // image word w: message word w before the committee, w + ENC_SC_WORDS behind it; word 0 of a Deneb / Capella
     // update is the first offset and then what follows the committee's last dword.  The highest message word read
     // is ceil(len / 16) - 1
@@ -196,7 +114,7 @@ LCV_FN void item_wire_dec(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, 
       if (!upd) {
         v = ld_q128(src, w);
       } else if (altair) {
-        v = ld_q128(src, w < K_BEACON / 16u ? w : w + ENC_SC_WORDS);
+        v = ld_q128(src, w < coff / 16u ? w : w + ENC_SC_WORDS);
       } else {
         v = ld_q128(src, w + ENC_SC_WORDS);
         if (w == 0u) v.x = ld_q128(src, 0).x;
@@ -206,11 +124,8 @@ LCV_FN void item_wire_dec(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, 
     return;
   }
   if (r == 1) {
-    DecPlan p = {1u, 0u, 0u, 0u, 0u, 0u, 0u};
-    if (dec_len_ok(kind, M.fork, M.len)) {
-      if (altair) p.status = 0u;
-      else p = dec_plan(img, kind, M.fork, M.len);
-    }
+    // the message is read through the image: an offset behind the committee lies K_SC lower there
+    const WirePlan p = wire_accept(kind, M.fork, M.len, [&](uint32_t o) { return dec_rd32(img, o < coff ? o : o - cut); });
     if (lane == 0) {
       lds[DEC_CTL / 4] = p.status;
       if (A.rec) {
@@ -219,24 +134,22 @@ LCV_FN void item_wire_dec(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, 
       }
     }
     if (p.status) return;
-    uint32_t o = 0;
+    auto seg = [&](uint32_t col, uint32_t part, uint32_t rec, uint32_t at, uint32_t len) {
+      dec_seg(raw, enc_raw_of(col, part) + rec, img, at, len, lane);
+    };
+    auto put = [](uint32_t, uint32_t) {};  // (the offsets were wire_accept's to check)
     if (altair) {  // every container fixed-size: fields in order
-      o = dec_seg(raw, ENC_R_ATT + ENC_H_BEACON, img, o, K_BEACON, lane);
-      if (upd) o = dec_seg(raw, ENC_R_NSC_BRANCH, img, o, K_NSC_BRANCH, lane);
-      if (kind <= (uint32_t)ENC_KIND_FINALITY) {
-        o = dec_seg(raw, ENC_R_FIN + ENC_H_BEACON, img, o, K_BEACON, lane);
-        o = dec_seg(raw, ENC_R_FIN_BRANCH, img, o, K_FIN_BRANCH, lane);
-      }
-      dec_seg(raw, ENC_R_BITS, img, o, ENC_TAIL_BYTES, lane);
+      wire_walk_fixed(kind, true, true, 0u, 0u, seg, put, EncRawJoined());
       return;
     }
-    const bool deneb = M.fork == (uint32_t)ENC_DENEB;
-    o = 4;
-    if (upd) o = dec_seg(raw, ENC_R_NSC_BRANCH, img, o, K_NSC_BRANCH, lane);
-    if (kind <= (uint32_t)ENC_KIND_FINALITY) o = dec_seg(raw, ENC_R_FIN_BRANCH, img, o + 4, K_FIN_BRANCH, lane);
-    dec_seg(raw, ENC_R_BITS, img, o, ENC_TAIL_BYTES, lane);
-    dec_header(raw, ENC_R_ATT, img, p.att_off, deneb, p.elen_att, lane);
-    if (kind <= (uint32_t)ENC_KIND_FINALITY) dec_header(raw, ENC_R_FIN, img, p.fin_off, deneb, p.elen_fin, lane);
+    // the encoder's walk backwards: the header at img[at ..) into its raw header (the record's gaps stay zero)
+    auto header = [&](uint32_t col, uint32_t at, uint32_t elen) {
+      wire_walk_header(col, at, M.fork == (uint32_t)WIRE_DENEB, elen, seg, put);
+      if (lane == 0) *(uint32_t*)(raw + enc_raw_of(col, WH_EXEC) + K_EXEC_EXTRALEN_OFF) = elen;
+    };
+    // (the attested header follows the fixed part, as wire_accept checked: a constant of the kind, not p.att_off - cut)
+    header(WC_ATT, wire_walk_fixed(kind, false, true, 0u, 0u, seg, put, EncRawJoined()), p.elen_att);
+    if (wire_has(WC_FIN, kind)) header(WC_FIN, p.fin_off - cut, p.elen_fin);
     return;
   }
   const bool ok = lds[DEC_CTL / 4] == 0u;
@@ -251,8 +164,8 @@ LCV_FN void item_wire_dec(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, 
     dec_store(O.fin_branch + (size_t)K_EXEC_BRANCH * s, raw + ENC_R_FIN + ENC_H_BRANCH, K_EXEC_BRANCH, lane, ok);
     dec_store(O.nsc_branch + (size_t)K_NSC_BRANCH * s, raw + ENC_R_NSC_BRANCH, K_NSC_BRANCH, lane, ok);
     dec_store(O.finality_branch + (size_t)K_FIN_BRANCH * s, raw + ENC_R_FIN_BRANCH, K_FIN_BRANCH, lane, ok);
-    dec_store(O.bits + 64 * s, raw + ENC_R_BITS, 64, lane, ok);
-    dec_store(O.sig + 96 * s, raw + ENC_R_SIG, 96, lane, ok);
+    dec_store(O.bits + (size_t)K_BITS * s, raw + ENC_R_BITS, K_BITS, lane, ok);
+    dec_store(O.sig + (size_t)K_SIG * s, raw + ENC_R_SIG, K_SIG, lane, ok);
     if (lane == 0)
       O.sig_slot[s] = ok ? (uint64_t)lds[ENC_R_SLOT / 4] | ((uint64_t)lds[ENC_R_SLOT / 4 + 1] << 32) : 0ull;
     return;
@@ -339,7 +252,9 @@ struct F_wire_dec {
   static constexpr uint32_t TEAM = lcv::DEC_TEAM, LDS_WORDS = lcv::DEC_LDS_WORDS, SHARED_WORDS = 0;
   LCV_HD uint32_t rounds() const { return A.phase == (uint32_t)lcv::DEC_PLAN ? 4u : 3u; }
   LCV_HD void operator()(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, uint32_t*) const {
-    lcv::item_wire_dec(i, lane, r, lds, A);
+    if (A.kind == (uint32_t)lcv::WIRE_UPDATE) lcv::item_wire_dec(i, lane, r, lds, A, lcv::WIRE_UPDATE);
+    else if (A.kind == (uint32_t)lcv::WIRE_FINALITY) lcv::item_wire_dec(i, lane, r, lds, A, lcv::WIRE_FINALITY);
+    else lcv::item_wire_dec(i, lane, r, lds, A, lcv::WIRE_OPTIMISTIC);
   }
 };
 struct F_sc_confirm {

@@ -1,6 +1,7 @@
 // lcv_wire_enc.hpp — SSZ wire bytes of a resident batch's rows on the device (lcv_batch_encode, include/lcv.h):
 // LightClientUpdate / FinalityUpdate / OptimisticUpdate of the Deneb, Capella or Altair namespace, the fork forced
-// for the call or chosen per row from the attested slot.  lcv/wire.py encode_updates is the definition of the bytes.
+// for the call or chosen per row from the attested slot.  lcv_wire_layout.hpp describes the containers; the bytes are
+// checked against lcv/wire.py encode_updates and the reference-serialised messages, which share nothing with it.
 //
 // One 64-lane team per message, three rounds over one LDS area (ENC_LDS_WORDS):
 //   round 0  the row's columns, everything but the committee, global -> LDS "raw" in 16-byte loads; every lane
@@ -24,22 +25,30 @@ namespace lcv {
 
 enum {
   ENC_TEAM = 64, ENC_ROUNDS = 3,
-  ENC_KIND_UPDATE = 0, ENC_KIND_FINALITY = 1, ENC_KIND_OPTIMISTIC = 2,
-  ENC_DENEB = 0, ENC_CAPELLA = 1, ENC_ALTAIR = 2,
   ENC_SC_WORDS = K_SC / 16,
   // the raw copy: a header is beacon, execution record, execution branch; bits, signature and slot are contiguous
   ENC_H_BEACON = 0, ENC_H_EXEC = K_BEACON, ENC_H_BRANCH = K_BEACON + K_EXEC, ENC_H_BYTES = K_BEACON + K_EXEC + K_EXEC_BRANCH,
   ENC_R_ATT = 0, ENC_R_FIN = ENC_H_BYTES, ENC_R_NSC_BRANCH = 2 * ENC_H_BYTES, ENC_R_FIN_BRANCH = ENC_R_NSC_BRANCH + K_NSC_BRANCH,
-  ENC_R_BITS = ENC_R_FIN_BRANCH + K_FIN_BRANCH, ENC_R_SIG = ENC_R_BITS + 64, ENC_R_SLOT = ENC_R_SIG + 96,
-  ENC_TAIL_BYTES = 64 + 96 + 8,  // sync_committee_bits, sync_committee_signature, signature_slot
+  ENC_R_BITS = ENC_R_FIN_BRANCH + K_FIN_BRANCH, ENC_R_SIG = ENC_R_BITS + K_BITS, ENC_R_SLOT = ENC_R_SIG + K_SIG,
   ENC_FLAGS = ENC_R_SLOT + 16, ENC_CTL = ENC_FLAGS + 4 * ENC_TEAM, ENC_IMG = ENC_CTL + 16,
-  // the longest image: a Deneb update without its committee, 528 + 2 x (828 + 32), and the zero-filled last word
-  ENC_IMG_BYTES = 2272,
+  ENC_IMG_BYTES = wire_image_bytes(),  // the longest message without its committee, its last word zero-filled
   ENC_LDS_WORDS = (ENC_IMG + ENC_IMG_BYTES) / 4,
   ENC_META_BYTES = 16,  // per row: u32 length, u8 fork, u8 status, 2 zero bytes, 4 version bytes, 4 zero bytes
 };
 static_assert(ENC_IMG % 16 == 0 && ENC_FLAGS % 16 == 0 && K_SC % 16 == 0, "16-byte LDS words");
-static_assert(528 + 2 * (828 + 32) + 16 <= ENC_IMG_BYTES, "the image holds the longest message and its zero fill");
+static_assert(wire_committee_off(true) % 16 == 0 && wire_committee_off(false) == 4, "round 2: the committee unshifted or one dword on");
+// where part `part` of wire column `col` lies in the raw copy
+constexpr uint32_t enc_raw_of(uint32_t col, uint32_t part) {
+  return (col == WC_ATT ? ENC_R_ATT : col == WC_FIN ? ENC_R_FIN : col == WC_NSC_BRANCH ? ENC_R_NSC_BRANCH : col == WC_FIN_BRANCH ? ENC_R_FIN_BRANCH
+          : col == WC_BITS ? ENC_R_BITS : col == WC_SIG ? ENC_R_SIG : ENC_R_SLOT) +
+         (part == WH_EXEC ? ENC_H_EXEC : part == WH_BRANCH ? ENC_H_BRANCH : ENC_H_BEACON);
+}
+// wire_walk_fixed's `joined`: column b lies directly behind the alen bytes of column a (bits, signature and slot do)
+struct EncRawJoined {
+  constexpr bool operator()(uint32_t a, uint32_t alen, uint32_t b) const {
+    return a != WC_COMMITTEE && enc_raw_of(a, WH_BEACON) + alen == enc_raw_of(b, WH_BEACON);
+  }
+};
 
 // a 16-byte word of the team's LDS area (the address space named, so that no select between an LDS and a global
 // source turns the access into a flat one)
@@ -76,9 +85,10 @@ LCV_FN EncPlan enc_plan(const uint32_t* lds, const NetConfig& cfg, uint32_t kind
   const uint64_t epoch = epoch_of_slot((uint64_t)lds[ENC_R_ATT / 4] | ((uint64_t)lds[ENC_R_ATT / 4 + 1] << 32), cfg);
   p.version = fork_version_word(epoch, cfg);
   p.fork = fork_arg >= 0 ? (uint32_t)fork_arg
-                         : epoch >= cfg.fork_epoch[FORK_DENEB] ? (uint32_t)ENC_DENEB
-                                                               : epoch >= cfg.fork_epoch[FORK_CAPELLA] ? (uint32_t)ENC_CAPELLA : (uint32_t)ENC_ALTAIR;
-  const bool fin = kind <= (uint32_t)ENC_KIND_FINALITY;  // the finalized header is encoded
+                         : epoch >= cfg.fork_epoch[FORK_DENEB] ? (uint32_t)WIRE_DENEB
+                                                               : epoch >= cfg.fork_epoch[FORK_CAPELLA] ? (uint32_t)WIRE_CAPELLA : (uint32_t)WIRE_ALTAIR;
+  const bool fin = wire_has(WC_FIN, kind);  // the finalized header is encoded
+  const uint32_t cut = wire_has(WC_COMMITTEE, kind) ? (uint32_t)K_SC : 0u;
   uint32_t flags = 0;
   LCV_NOUNROLL for (uint32_t k = 0; k < (uint32_t)ENC_TEAM / 4; ++k) {
     const q128 v = lds_q128((const uint8_t*)lds + ENC_FLAGS, k);
@@ -86,69 +96,38 @@ LCV_FN EncPlan enc_plan(const uint32_t* lds, const NetConfig& cfg, uint32_t kind
   }
   p.elen_att = p.elen_fin = 0;
   p.status = 0;
-  if (p.fork == (uint32_t)ENC_ALTAIR) {  // LightClientHeader = {beacon}: an encoded header carries no execution data
+  if (p.fork == (uint32_t)WIRE_ALTAIR) {  // LightClientHeader = {beacon}: an encoded header carries no execution data
     if ((flags & 1u) || (fin && (flags & 2u))) p.status = 1;
     p.hatt = p.hfin = K_BEACON;
-    p.imglen = K_BEACON + ENC_TAIL_BYTES;
-    if (fin) p.imglen += K_BEACON + K_FIN_BRANCH;
-    if (kind == (uint32_t)ENC_KIND_UPDATE) p.imglen += K_NSC_BRANCH;
+    p.imglen = wire_msg_fixed(kind, true) - cut;
   } else {
-    const uint32_t fixed = 244u + (p.fork == (uint32_t)ENC_DENEB ? 584u : 568u);
+    const uint32_t fixed = wire_header_fixed() + wire_exec_fixed(p.fork == (uint32_t)WIRE_DENEB);
     p.elen_att = lds[(ENC_R_ATT + ENC_H_EXEC + K_EXEC_EXTRALEN_OFF) / 4];
     if (fin) p.elen_fin = lds[(ENC_R_FIN + ENC_H_EXEC + K_EXEC_EXTRALEN_OFF) / 4];
-    if (p.elen_att > 32u || p.elen_fin > 32u) p.status = 2;
+    if (p.elen_att > (uint32_t)K_MAX_EXTRA || p.elen_fin > (uint32_t)K_MAX_EXTRA) p.status = 2;
     p.hatt = fixed + p.elen_att;
     p.hfin = fixed + p.elen_fin;
-    p.imglen = kind == (uint32_t)ENC_KIND_UPDATE ? 528u : kind == (uint32_t)ENC_KIND_FINALITY ? 368u : 172u;
-    p.imglen += p.hatt + (fin ? p.hfin : 0u);
+    p.imglen = wire_msg_fixed(kind, false) - cut + p.hatt + (fin ? p.hfin : 0u);
   }
   return p;
 }
 
 // ---- round 1's moves inside LDS: raw[src .. src + len) -> img[dst ..), the team's lanes striding over dwords, or
 // over bytes where dst or len is no multiple of 4 (src always is)
-LCV_FN uint32_t enc_seg(uint8_t* img, uint32_t dst, const uint8_t* raw, uint32_t src, uint32_t len, uint32_t lane) {
+LCV_FN void enc_seg(uint8_t* img, uint32_t dst, const uint8_t* raw, uint32_t src, uint32_t len, uint32_t lane) {
   if (((dst | len) & 3u) == 0u) {
     for (uint32_t k = lane; k < len / 4; k += ENC_TEAM) ((uint32_t*)(img + dst))[k] = ((const uint32_t*)(raw + src))[k];
   } else {
     for (uint32_t k = lane; k < len; k += ENC_TEAM) img[dst + k] = raw[src + k];
   }
-  return dst + len;
 }
-LCV_FN uint32_t enc_put32(uint8_t* img, uint32_t dst, uint32_t v, uint32_t lane) {
-  if (lane == 0) {
-    if ((dst & 3u) == 0u) {
-      *(uint32_t*)(img + dst) = v;
-    } else {
-      LCV_UNROLL for (int k = 0; k < 4; ++k) img[dst + k] = (uint8_t)(v >> (8 * k));
-    }
+LCV_FN void enc_put32(uint8_t* img, uint32_t dst, uint32_t v, uint32_t lane) {
+  if (lane != 0) return;
+  if ((dst & 3u) == 0u) {
+    *(uint32_t*)(img + dst) = v;
+  } else {
+    LCV_UNROLL for (int k = 0; k < 4; ++k) img[dst + k] = (uint8_t)(v >> (8 * k));
   }
-  return dst + 4;
-}
-// LightClientHeader of the Deneb / Capella namespace at img[o ..) from the raw header at raw[h ..): beacon, the
-// offset of `execution`, execution_branch, the ExecutionPayloadHeader's fixed part (field order; extra_data's
-// offset in the eleventh place; Capella stops before the two blob-gas fields), extra_data
-LCV_FN uint32_t enc_header(uint8_t* img, uint32_t o, const uint8_t* raw, uint32_t h, bool deneb, uint32_t elen, uint32_t lane) {
-  const uint32_t e = h + ENC_H_EXEC;
-  o = enc_seg(img, o, raw, h + ENC_H_BEACON, K_BEACON, lane);
-  o = enc_put32(img, o, K_BEACON + 4 + K_EXEC_BRANCH, lane);
-  o = enc_seg(img, o, raw, h + ENC_H_BRANCH, K_EXEC_BRANCH, lane);
-  o = enc_seg(img, o, raw, e + 0, 32, lane);     // parent_hash
-  o = enc_seg(img, o, raw, e + 32, 20, lane);    // fee_recipient
-  o = enc_seg(img, o, raw, e + 64, 64, lane);    // state_root, receipts_root
-  o = enc_seg(img, o, raw, e + K_EXEC_BLOOM_OFF, 256, lane);
-  o = enc_seg(img, o, raw, e + 160, 32, lane);   // prev_randao
-  o = enc_seg(img, o, raw, e + 192, 8, lane);    // block_number
-  o = enc_seg(img, o, raw, e + 224, 8, lane);    // gas_limit
-  o = enc_seg(img, o, raw, e + 256, 8, lane);    // gas_used
-  o = enc_seg(img, o, raw, e + 288, 8, lane);    // timestamp
-  o = enc_put32(img, o, deneb ? 584u : 568u, lane);
-  o = enc_seg(img, o, raw, e + 352, 128, lane);  // base_fee_per_gas, block_hash, transactions_root, withdrawals_root
-  if (deneb) {
-    o = enc_seg(img, o, raw, e + 480, 8, lane);  // blob_gas_used
-    o = enc_seg(img, o, raw, e + 512, 8, lane);  // excess_blob_gas
-  }
-  return enc_seg(img, o, raw, e + 320, elen, lane);
 }
 
 // round 0's move: 16-byte words global -> LDS; returns the OR of the words this lane moved
@@ -171,7 +150,7 @@ struct EncArgs {
   uint8_t* meta;         // [chunk rows][ENC_META_BYTES]
   NetConfig cfg;
   uint32_t kind;
-  int32_t fork;          // ENC_DENEB .. ENC_ALTAIR, or -1: per row
+  int32_t fork;          // WIRE_DENEB .. WIRE_ALTAIR, or -1: per row
   uint32_t pitch;
 };
 
@@ -187,17 +166,17 @@ LCV_FN void item_wire_enc(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, 
     if (enc_load<ENC_TEAM>(raw + ENC_R_ATT + ENC_H_EXEC, B.att_exec + (size_t)K_EXEC * s, K_EXEC, lane) |
         enc_load<ENC_TEAM>(raw + ENC_R_ATT + ENC_H_BRANCH, B.att_branch + (size_t)K_EXEC_BRANCH * s, K_EXEC_BRANCH, lane))
       f |= 1u;
-    if (kind <= (uint32_t)ENC_KIND_FINALITY) {
+    if (wire_has(WC_FIN, kind)) {
       enc_load<ENC_TEAM>(raw + ENC_R_FIN + ENC_H_BEACON, B.fin_beacon + (size_t)K_BEACON * s, K_BEACON, lane);
       if (enc_load<ENC_TEAM>(raw + ENC_R_FIN + ENC_H_EXEC, B.fin_exec + (size_t)K_EXEC * s, K_EXEC, lane) |
           enc_load<ENC_TEAM>(raw + ENC_R_FIN + ENC_H_BRANCH, B.fin_branch + (size_t)K_EXEC_BRANCH * s, K_EXEC_BRANCH, lane))
         f |= 2u;
       enc_load<ENC_TEAM>(raw + ENC_R_FIN_BRANCH, B.finality_branch + (size_t)K_FIN_BRANCH * s, K_FIN_BRANCH, lane);
     }
-    if (kind == (uint32_t)ENC_KIND_UPDATE)
+    if (wire_has(WC_COMMITTEE, kind))
       enc_load<ENC_TEAM>(raw + ENC_R_NSC_BRANCH, B.nsc_branch + (size_t)K_NSC_BRANCH * s, K_NSC_BRANCH, lane);
-    enc_load<ENC_TEAM>(raw + ENC_R_BITS, B.bits + 64 * s, 64, lane);
-    enc_load<ENC_TEAM>(raw + ENC_R_SIG, B.sig + 96 * s, 96, lane);
+    enc_load<ENC_TEAM>(raw + ENC_R_BITS, B.bits + (size_t)K_BITS * s, K_BITS, lane);
+    enc_load<ENC_TEAM>(raw + ENC_R_SIG, B.sig + (size_t)K_SIG * s, K_SIG, lane);
     if (lane == 0) {
       const uint64_t slot = B.sig_slot[s];
       lds[ENC_R_SLOT / 4] = (uint32_t)slot;
@@ -209,7 +188,7 @@ LCV_FN void item_wire_enc(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, 
   if (r == 1) {
     const EncPlan p = enc_plan(lds, A.cfg, kind, A.fork);
     if (lane == 0) {
-      const uint32_t len = p.status ? 0u : p.imglen + (kind == (uint32_t)ENC_KIND_UPDATE ? (uint32_t)K_SC : 0u);
+      const uint32_t len = p.status ? 0u : p.imglen + (wire_has(WC_COMMITTEE, kind) ? (uint32_t)K_SC : 0u);
       lds[ENC_CTL / 4] = p.status;
       lds[ENC_CTL / 4 + 1] = p.fork;
       lds[ENC_CTL / 4 + 2] = p.imglen;
@@ -217,33 +196,22 @@ LCV_FN void item_wire_enc(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, 
       st_q128(A.meta, i, m);
     }
     if (p.status) return;
-    uint32_t o = 0;
-    if (p.fork == (uint32_t)ENC_ALTAIR) {  // every container fixed-size: fields in order, no offsets
-      o = enc_seg(img, o, raw, ENC_R_ATT + ENC_H_BEACON, K_BEACON, lane);
-      if (kind == (uint32_t)ENC_KIND_UPDATE) o = enc_seg(img, o, raw, ENC_R_NSC_BRANCH, K_NSC_BRANCH, lane);
-      if (kind <= (uint32_t)ENC_KIND_FINALITY) {
-        o = enc_seg(img, o, raw, ENC_R_FIN + ENC_H_BEACON, K_BEACON, lane);
-        o = enc_seg(img, o, raw, ENC_R_FIN_BRANCH, K_FIN_BRANCH, lane);
-      }
-      o = enc_seg(img, o, raw, ENC_R_BITS, ENC_TAIL_BYTES, lane);
-    } else {
-      const bool deneb = p.fork == (uint32_t)ENC_DENEB;
-      if (kind == (uint32_t)ENC_KIND_UPDATE) {  // (the committee follows the first offset)
-        o = enc_put32(img, o, 528u + K_SC, lane);
-        o = enc_seg(img, o, raw, ENC_R_NSC_BRANCH, K_NSC_BRANCH, lane);
-        o = enc_put32(img, o, 528u + K_SC + p.hatt, lane);
-        o = enc_seg(img, o, raw, ENC_R_FIN_BRANCH, K_FIN_BRANCH, lane);
-      } else if (kind == (uint32_t)ENC_KIND_FINALITY) {
-        o = enc_put32(img, o, 368u, lane);
-        o = enc_put32(img, o, 368u + p.hatt, lane);
-        o = enc_seg(img, o, raw, ENC_R_FIN_BRANCH, K_FIN_BRANCH, lane);
-      } else {
-        o = enc_put32(img, o, 172u, lane);
-      }
-      o = enc_seg(img, o, raw, ENC_R_BITS, ENC_TAIL_BYTES, lane);
-      o = enc_header(img, o, raw, ENC_R_ATT, deneb, p.elen_att, lane);
-      if (kind <= (uint32_t)ENC_KIND_FINALITY) o = enc_header(img, o, raw, ENC_R_FIN, deneb, p.elen_fin, lane);
-    }
+    auto seg = [&](uint32_t col, uint32_t part, uint32_t rec, uint32_t at, uint32_t len) {
+      enc_seg(img, at, raw, enc_raw_of(col, part) + rec, len, lane);
+    };
+    auto put = [&](uint32_t at, uint32_t v) { enc_put32(img, at, v, lane); };
+    // (one instance per kind: the offsets of the fixed part and of the attested header are then constants, and a
+    // move's choice between dwords and bytes is made when the kernel is compiled)
+    auto lay = [&](uint32_t k) -> uint32_t {
+      if (p.fork == (uint32_t)WIRE_ALTAIR) return wire_walk_fixed(k, true, true, 0u, 0u, seg, put, EncRawJoined());  // no offsets
+      const bool deneb = p.fork == (uint32_t)WIRE_DENEB;
+      const uint32_t fixed = wire_msg_fixed(k, false);  // (the offsets count the committee)
+      uint32_t at = wire_walk_fixed(k, false, true, fixed, fixed + p.hatt, seg, put, EncRawJoined());
+      at = wire_walk_header(WC_ATT, at, deneb, p.elen_att, seg, put);
+      if (wire_has(WC_FIN, k)) at = wire_walk_header(WC_FIN, at, deneb, p.elen_fin, seg, put);
+      return at;
+    };
+    const uint32_t o = kind == (uint32_t)WIRE_UPDATE ? lay(WIRE_UPDATE) : kind == (uint32_t)WIRE_FINALITY ? lay(WIRE_FINALITY) : lay(WIRE_OPTIMISTIC);
     // o == p.imglen: zero to the end of the image's last word
     for (uint32_t k = o + lane; k < ((o + 15u) & ~15u); k += ENC_TEAM) img[k] = 0;
     return;
@@ -253,7 +221,7 @@ LCV_FN void item_wire_enc(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, 
   const uint32_t fork = lds[ENC_CTL / 4 + 1], imglen = lds[ENC_CTL / 4 + 2];
   uint8_t* dst = A.out + (size_t)A.pitch * i;
   const uint32_t words = A.pitch / 16;
-  if (kind != (uint32_t)ENC_KIND_UPDATE) {
+  if (!wire_has(WC_COMMITTEE, kind)) {
     for (uint32_t w = lane; w < words; w += ENC_TEAM) {
       q128 v = {0u, 0u, 0u, 0u};
       if (ok && 16u * w < imglen) v = lds_q128(img, w);
@@ -262,12 +230,13 @@ LCV_FN void item_wire_enc(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, 
     return;
   }
   const uint8_t* sc = B.nsc_pool + (size_t)K_SC * B.nsc_index[s];
-  if (fork == (uint32_t)ENC_ALTAIR) {  // attested header 112 = 7 words, then the committee: unshifted
+  if (fork == (uint32_t)WIRE_ALTAIR) {  // the attested header's words, then the committee: unshifted
+    const uint32_t cw = wire_committee_off(true) / 16u;
     for (uint32_t w = lane; w < words; w += ENC_TEAM) {
       q128 v = {0u, 0u, 0u, 0u};
       if (ok) {
-        if (w < 7u) v = lds_q128(img, w);
-        else if (w < 7u + ENC_SC_WORDS) v = ld_q128(sc, w - 7u);
+        if (w < cw) v = lds_q128(img, w);
+        else if (w < cw + ENC_SC_WORDS) v = ld_q128(sc, w - cw);
         else if (16u * (w - ENC_SC_WORDS) < imglen) v = lds_q128(img, w - ENC_SC_WORDS);
       }
       st_q128(dst, w, v);

@@ -264,6 +264,36 @@ def test_dedup_exact_on_sampled_key_collision():
         assert batch.nsc_pool[1].tobytes() == bytes(other[4:4 + 24624])
 
 
+def test_pool_order_is_first_occurrence_behind_a_key_collision():
+    """Pool rows are numbered in order of first occurrence, SyncCommittee() at its first use, also where two distinct
+    committees share the sampled bytes: A, A' (collides with A), B, the all-zero committee, A', B, A."""
+    w = load_wire()
+    a = messages(w, [int(np.flatnonzero(w["kind"] == 0)[0])])[0]
+    a2, b, zero = bytearray(a), bytearray(a), bytearray(a)
+    a2[4 + 48 * 100 + 5] ^= 0x01   # pubkey 100: outside the sampled bytes
+    b[4 + 5] ^= 0x01               # the first pubkey: another key
+    zero[4:4 + 24624] = bytes(24624)
+    msgs = [a, bytes(a2), bytes(b), bytes(zero), bytes(a2), bytes(b), a]
+    for lib in libs():
+        batch = wire.decode_updates(msgs, lib=lib)
+        assert batch.nsc_index.tolist() == [0, 1, 2, 3, 1, 2, 0]
+        assert batch.nsc_pool.shape[0] == 4 and not batch.nsc_pool[3].any()
+        for k, m in enumerate((a, a2, b)):
+            assert batch.nsc_pool[k].tobytes() == bytes(m[4:4 + 24624])
+
+
+def test_decode_refuses_a_row_count_of_32_bits():
+    """nsc_index numbers rows in 32 bits: n >= 2^32 - 1 is LCV_EINVAL before anything is read or written."""
+    import ctypes as C
+    from lcv._native import UpdateBatch, ptr
+    one8, one64 = np.zeros(1, np.uint8), np.zeros(1, np.uint64)
+    npool = C.c_uint64(7)
+    for lib in libs():
+        rc = lib.lcv_ssz_decode_updates(ptr(one8), ptr(one64, C.c_uint64), ptr(one64, C.c_uint64), 0xFFFFFFFF, 0, 0,
+                                        C.byref(UpdateBatch()), ptr(one64, C.c_uint64), C.byref(npool), ptr(one8))
+        assert rc == -1 and npool.value == 7
+
+
 @pytest.mark.parametrize("kind", [0, 1, 2])
 def test_encode_reproduces_reference_bytes(kind):
     """encode_updates(decode_updates(x)) == x for the reference-serialised messages."""

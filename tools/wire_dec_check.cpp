@@ -2,7 +2,11 @@
 // (csrc/lcv_wire_dec.hpp: F_wire_dec, F_sc_confirm, F_sc_gather) on their host path, meant to be built with sanitizers.
 // The kernels follow offsets that a peer chose, so every round of every functor is run lane by lane over heap buffers
 // of EXACTLY the staged, LDS, record and column sizes: an access one byte out of any of them is a sanitizer report.
-// The rows, statuses and committees are compared with the host decoder (csrc/lcv_wire.cpp, included here).
+// The rows, statuses and committees are compared with the host decoder (csrc/lcv_wire.cpp, included here).  Both
+// decoders take the containers and the acceptance rule from csrc/lcv_wire_layout.hpp, so their agreement says nothing
+// about the layout: this program checks memory safety and that malformed messages (built below from literal sizes of
+// its own) are refused.  The layout is pinned by the reference-serialised bytes of tests/golden/wire.npz and by
+// tests/wire_layout_cases.py, which share nothing with that header.
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -static-libasan -static-libubsan \
 //       -pthread -DLCV_HOSTSIM=1 -I light-client-consensus-specs_amd/csrc \
 //       tools/wire_dec_check.cpp -o wire_dec_check && ./wire_dec_check [mutations per kind and fork, default 1500]
