@@ -405,8 +405,9 @@ int lcv_debug_dedup_hash_bits(lcv_ctx* ctx, int bits);
  * labels, equal tuples); the result of an unclassed src is unclassed.  Refused with LCV_EINVAL before any launch,
  * lcv_last_error naming the first offender, *out = NULL: a null ctx, src or out; rows and store_index both NULL; n == 0
  * or n >= 2^32 - 1; rows[i] >= src's n.  Synchronous, on slot 0's stream; freed by lcv_batch_free.
- * Out of scope: an asynchronous relay on the eight slots; classing inside lcv_batch_decode or
- * lcv_create_updates_resident by default; merging across chunks; bootstraps. */
+ * The asynchronous form of this path on the eight slots, for the gossip kinds: lcv_relay_async, below.
+ * Out of scope: classing inside lcv_batch_decode or lcv_create_updates_resident by default; merging across chunks;
+ * bootstraps. */
 int lcv_batch_classify(lcv_ctx* ctx, lcv_dbatch* b, uint64_t* classes_out);
 int lcv_last_classify_timings(lcv_ctx* ctx, float ms_out[2]);
 int lcv_debug_batch_classes(lcv_ctx* ctx, const lcv_dbatch* b, uint32_t* out /* n */);
@@ -658,8 +659,9 @@ int lcv_debug_set_encode_chunk(lcv_ctx* ctx, uint64_t rows);
  * reads all zero after a decode.
  * lcv_debug_decode_hash_bits (test hook): the committee hash truncated to `bits` bits for the grouping (default 64;
  * 0 makes every committee collide, so that only the full compares separate them), as lcv_debug_dedup_hash_bits.
- * Out of scope: an asynchronous wire-in entry on the eight slots, decoding inside the streaming validation,
- * bootstraps, snappy framing and the Req/Resp result byte, merging pools across calls. */
+ * The asynchronous wire-in entry on the eight slots (kinds 1 and 2): lcv_relay_async, below.
+ * Out of scope: decoding inside the streaming validation, bootstraps, snappy framing and the Req/Resp result byte,
+ * merging pools across calls. */
 #define LCV_DECODE_MAX_ROWS 65536u
 #define LCV_DECODE_MAX_BYTES (2ull << 30)
 int lcv_batch_decode(lcv_ctx* ctx, const uint8_t* buf, uint64_t buf_len, const uint64_t* offsets,
@@ -668,6 +670,64 @@ int lcv_batch_decode(lcv_ctx* ctx, const uint8_t* buf, uint64_t buf_len, const u
                      lcv_dbatch** out);
 int lcv_last_decode_timings(lcv_ctx* ctx, float ms_out[2]);
 int lcv_debug_decode_hash_bits(lcv_ctx* ctx, uint32_t bits);
+
+/* ---- The asynchronous relay: wire messages to per-store verdicts on the eight slots (gossip kinds: 1 finality,
+ * 2 optimistic).  lcv_relay_async stages the messages and the (message, store) pair list into work-space slot `slot`,
+ * enqueues decode, fan-out, validation against the store table and, with fold_in, the segmented fold, and returns
+ * without waiting; lcv_slot_wait_relay waits and hands out the statuses, verdicts, reasons and fold results.  Nothing
+ * blocks on the device between the two, and nothing is allocated per call once the slot's buffers have grown.
+ * Contract: status_out[j] is exactly lcv_batch_decode's status of message j.  Pair i's verdict and reason are exactly
+ * those of lcv_batch_decode of the messages, lcv_batch_fan_out(rows, store_index) of that batch and
+ * lcv_validate_resident of the result under the store table that is set when lcv_relay_async is called: byte for
+ * byte with lcv_set_dedup off or on and lcv_set_rlc off or on (with it on: up to the documented 2^-64).  A malformed
+ * message is an all-zero row and its pairs keep that row's verdict and reason.  With fold_in (nstore entries, as
+ * lcv_validate_stores_async_fold's `in`) fold_out[s] is exactly lcv_validate_stores_fold's result for the host batch
+ * of the same rows and the same store_index; entries of stores without a pair are left untouched.
+ * How: one pinned region of the slot takes the messages (16-byte aligned each, 16 zero bytes behind the last), the
+ * per-message (offset, length, fork), the rows and store_index columns and, with lcv_set_dedup on, the grouping into
+ * BLS items, with fold_in the grouping by store and the present stores' states; ONE DMA moves it.  One kernel
+ * (F_wire_relay, csrc/lcv_wire_dec.hpp) decodes message rows[i] straight into row i of the slot's table batch, one
+ * 64-lane team per pair, and writes one status record per message with a team of its own; the validation follows in
+ * stream order.  With lcv_set_dedup on, the host reads the class tuple of every message where it lies (the host
+ * decoder's walk) and groups the pairs by (class of the message, committee row of the store) before the copy:
+ * lcv_last_dedup(slot) reports what the synchronous path reports for the same input.  With the mode off the host
+ * parses nothing.
+ * Refused before anything is staged or launched, LCV_EINVAL with lcv_last_error naming the first offender: a null
+ * argument; slot not in 0..7; kind not 1 or 2 (0, the full update, needs a device round trip for its committee pool:
+ * the synchronous path serves it); fork out of range with forks == NULL; nmsg == 0 or npairs == 0; nmsg >
+ * LCV_DECODE_MAX_ROWS; npairs above the chunk size (65536; lcv_debug_set_chunk); offsets[j] + lengths[j] > buf_len
+ * (computed without wrapping); staged bytes above LCV_RELAY_MAX_BYTES; rows[i] >= nmsg; store_index[i] >= nstore; a
+ * present fold_in[s] whose maxima exceed 512; a multi-stream pipeline (lcv_set_pipeline streams > 1).  No store table
+ * set: LCV_ESTATE.
+ * lcv_slot_wait_relay: LCV_ESTATE for a slot whose last batch was not a relay, and for fold_out != NULL on a relay
+ * enqueued without fold_in; any out pointer may be NULL.  lcv_slot_wait on a relay slot hands out the verdicts and
+ * reasons as for any staged batch; lcv_slot_wait_fold and lcv_slot_wait_stores_fold return LCV_ESTATE there.
+ * Ordering: as lcv_validate_stores_async — the caller's buffers are free when the call returns; a relay and any other
+ * staged or resident batch may be in flight on different slots; lcv_set_store_table waits for all slots.
+ * lcv_last_relay_timings: [0] the device time of the slot's last decode + fan-out kernel (waits for it), [1] 0.
+ * Out of scope: kind 0; merging classes across batches in flight; a sharded relay; snappy framing and the Req/Resp
+ * result byte; bootstraps; applying the fold's result to the store table on the device. */
+#define LCV_RELAY_MAX_BYTES (256ull << 20) /* staged message bytes, each length rounded up to 16, plus 16 */
+typedef struct lcv_relay_request {
+  const uint8_t* buf;
+  uint64_t buf_len;
+  const uint64_t* offsets; /* message j = buf[offsets[j] .. + lengths[j]) */
+  const uint64_t* lengths;
+  uint64_t nmsg;
+  int kind;                /* 1 finality, 2 optimistic; 0 (update) is refused */
+  int fork;                /* as lcv_batch_decode: forks == NULL -> `fork` for every message */
+  const uint8_t* forks;
+  const uint32_t* rows;        /* npairs: message of pair i */
+  const uint32_t* store_index; /* npairs: store-table row of pair i */
+  uint64_t npairs;
+  uint64_t current_slot;
+  const uint8_t* genesis_validators_root;
+  const lcv_fold_state* fold_in; /* NULL: no fold; else nstore entries */
+} lcv_relay_request;
+int lcv_relay_async(lcv_ctx* ctx, const lcv_relay_request* rq, int slot);
+int lcv_slot_wait_relay(lcv_ctx* ctx, int slot, uint8_t* status_out /* nmsg */, uint8_t* verdict_out /* npairs */,
+                        uint8_t* reason_out /* npairs */, lcv_fold_result* fold_out /* nstore, or NULL */);
+int lcv_last_relay_timings(lcv_ctx* ctx, int slot, float ms_out[2]);
 
 /* ---- SSZ wire decode (host only, no device work; csrc/lcv_wire.cpp).  Replaces the upstream SSZ
  * deserialisation of the reference's containers (sync-protocol.md:109-115 LightClientBootstrap,

@@ -51,6 +51,11 @@ static void be_stage_end(lcv_ctx* ctx, int stage);
 static void be_reset_timings(lcv_ctx* ctx);
 static void be_collect_timings(lcv_ctx* ctx);
 static size_t be_event_pool_size(lcv_ctx* ctx);
+// the asynchronous relay's own pair of marks per slot (lcv_last_relay_timings): recorded on the current stream whatever
+// ctx->marks_off says, outside the event pool; be_relay_ms waits for the pair and gives the time between them (0 for
+// a slot that never recorded one)
+static int be_relay_mark(lcv_ctx* ctx, int end);
+static int be_relay_ms(lcv_ctx* ctx, int slot, float* ms);
 // the communicator (lcv_comm_*): collectives on the current stream, be_comm_wait bounded by ctx->comm_timeout_s
 static int be_comm_unique_id(uint8_t* id);
 static int be_comm_init(lcv_ctx* ctx, int nranks, int rank, const uint8_t* id);

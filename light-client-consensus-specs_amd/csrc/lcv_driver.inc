@@ -158,6 +158,10 @@ struct HostSlot {
   // ... or (lcv_validate_stores_async_fold) one result (FOLD_RESULT_BYTES) per store present, for the store rows seg_store
   bool seg_folded = false;
   std::vector<uint32_t> seg_store;
+  // ... or (lcv_relay_async) a relay's: after the 2 out_n bytes the per-store results of its fold, if it has one
+  // (relay_fold; seg_store as above), then one DEC_REC_BYTES status record per message (lcv_slot_wait_relay)
+  bool relay = false, relay_fold = false;
+  uint64_t relay_nmsg = 0;
   lcv_dbatch db;  // (a view of `dev`: owns nothing)
   void release(lcv_ctx* ctx) {
     dev.release(ctx);
@@ -296,6 +300,11 @@ struct lcv_ctx {
   DevBuf dec_mem;
   uint32_t dec_hash_bits = 64;
   DedupTable dec_table;
+  // lcv_relay_async under lcv_set_dedup, the host's scratch of the call in progress: the messages' class tuples
+  // (wire_dedup_tuples) and classes, the pairs' signature slots (the pairs' classes, committee rows and items: dd_*)
+  std::vector<uint8_t> rl_beacon, rl_bits, rl_sig;
+  std::vector<uint64_t> rl_slot, rl_pslot;
+  std::vector<uint32_t> rl_cls;
 };
 
 static uint32_t host_be32(const uint8_t* p) {
@@ -1482,7 +1491,7 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
   const bool marks_were_off = ctx->marks_off;
   if (v.async) {
     ctx->marks_off = true;  // nothing collects an asynchronous batch's stage marks
-    s.host.staged = s.host.folded = s.host.seg_folded = false;
+    s.host.staged = s.host.folded = s.host.seg_folded = s.host.relay = false;
   }
   // (the boundary: a resident chunk's grouping under lcv_set_dedup allocates host memory, dedup_chunk)
   const int rc = guarded(ctx, "validate", [&] {
@@ -3327,6 +3336,246 @@ int lcv_batch_fan_out(lcv_ctx* ctx, lcv_dbatch* src, const uint32_t* rows, const
     db->h_store.swap(h_store);
     return nb.hand_out(out);
   });
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ the asynchronous relay (include/lcv.h; F_wire_relay,
+// lcv_wire_dec.hpp).  What lcv_batch_decode -> lcv_batch_classify -> lcv_batch_fan_out -> lcv_validate_resident does in
+// four synchronous calls on slot 0, enqueued on one slot without a wait: the slot's pinned region takes the messages (as
+// lcv_batch_decode stages them), the meta records, the pair list and, where the modes ask for them, the grouping into BLS
+// items (the plan_m path of dedup_chunk) and the grouping by store (the FoldReq path of validate_impl); one DMA moves it
+// into the slot's device buffer, which holds behind it the status records and a table batch of npairs rows
+// (batch_layout, one all-zero pool row, nsc_index all zero).  Both buffers are the HostSlot's, under stage_host_batch's rule
+struct RelayLayout {
+  size_t meta, rows, store, seg_store, seg_off, seg_row, seg_in, rep, urow, stage_bytes, rec, batch, total;
+  BatchCols c;  // the table batch, at `batch` (its store_index column and its groupings are the staged ones)
+};
+static void relay_layout(RelayLayout& L, size_t msg_bytes, size_t nmsg, size_t np, size_t ng, size_t nd) {
+  Layout l;
+  l.take(msg_bytes);  // the messages, at offset 0
+  L.meta = l.take(nmsg * DEC_META_BYTES);
+  L.rows = l.take(4 * np);
+  L.store = l.take(4 * np);
+  L.seg_store = l.take(4 * ng);
+  L.seg_off = l.take(ng ? 4 * (ng + 1) : 0);
+  L.seg_row = l.take(ng ? 4 * np : 0);
+  L.seg_in = l.take(sizeof(FoldState) * ng);
+  L.rep = l.take(nd ? 4 * np : 0);
+  L.urow = l.take(4 * nd);
+  L.stage_bytes = l.total();  // what the one DMA moves
+  L.rec = l.take(nmsg * DEC_REC_BYTES);
+  L.batch = l.total();
+  batch_layout(L.c, np, 1, false, 0);
+  L.total = L.batch + L.c.total;
+}
+
+namespace lcv {  // lcv_wire.cpp: the host decoder's walk, storing the class tuple alone
+void wire_dedup_tuples(const uint8_t* buf, const uint64_t* offsets, const uint64_t* lengths, uint64_t n, int kind, int fork,
+                       const uint8_t* forks, uint8_t* beacon, uint8_t* bits, uint8_t* sig, uint64_t* slot);
+}
+
+// the pairs' grouping into BLS items, as the synchronous path makes it: dedup_classes over the messages' tuples (what
+// lcv_batch_classify computes from the decoded rows), a pair's class its message's (lcv_batch_fan_out), the committee
+// row from the pair's store and its message's signature_slot, dedup_plan (dedup_chunk).  Into the context's scratch
+static void relay_plan(lcv_ctx* ctx, const lcv_relay_request* rq, DedupCols& dd) {
+  const size_t nmsg = (size_t)rq->nmsg, np = (size_t)rq->npairs;
+  ctx->rl_beacon.resize(nmsg * K_BEACON);
+  ctx->rl_bits.resize(nmsg * K_BITS);
+  ctx->rl_sig.resize(nmsg * K_SIG);
+  ctx->rl_slot.resize(nmsg);
+  ctx->rl_cls.resize(nmsg);
+  ctx->rl_pslot.resize(np);
+  ctx->dd_cls.resize(np);
+  ctx->dd_comm.resize(np);
+  ctx->dd_rep.resize(np);
+  ctx->dd_urow.resize(np);
+  wire_dedup_tuples(rq->buf, rq->offsets, rq->lengths, nmsg, rq->kind, rq->fork, rq->forks, ctx->rl_beacon.data(),
+                    ctx->rl_bits.data(), ctx->rl_sig.data(), ctx->rl_slot.data());
+  dedup_classes(ctx->rl_beacon.data(), ctx->rl_slot.data(), ctx->rl_bits.data(), ctx->rl_sig.data(), (uint32_t)nmsg,
+                ctx->dedup_hash_bits, ctx->rl_cls.data(), ctx->dd_table);
+  for (size_t i = 0; i < np; ++i) {
+    ctx->dd_cls[i] = ctx->rl_cls[rq->rows[i]];
+    ctx->rl_pslot[i] = ctx->rl_slot[rq->rows[i]];
+  }
+  dedup_comm_rows(ctx, rq->store_index, ctx->rl_pslot.data(), np, ctx->dd_comm.data());
+  dd.m = dedup_plan(ctx->dd_cls.data(), ctx->dd_comm.data(), (uint32_t)np, ctx->dedup_hash_bits, ctx->dd_rep.data(),
+                    ctx->dd_urow.data(), ctx->dd_table);
+  dd.rep = ctx->dd_rep.data();
+  dd.urow = ctx->dd_urow.data();
+}
+
+// the host copies of the staging step (host threads above 8 MB) into the slot's pinned region, laid out as L
+static void relay_stage(uint8_t* pin, const RelayLayout& L, const lcv_relay_request* rq, const FoldSegs* segs,
+                        const DedupCols& dd) {
+  const size_t nmsg = (size_t)rq->nmsg, np = (size_t)rq->npairs;
+  std::vector<CopyPiece> pieces;
+  pieces.reserve(nmsg + 8);
+  uint64_t o = 0;
+  for (size_t j = 0; j < nmsg; ++j) {
+    const uint32_t f = rq->forks ? (uint32_t)rq->forks[j] : (uint32_t)rq->fork;
+    const uint32_t len = (uint32_t)rq->lengths[j];  // (<= LCV_RELAY_MAX_BYTES < 2^32)
+    memcpy(pin + L.meta + DEC_META_BYTES * j, &o, 8);
+    memcpy(pin + L.meta + DEC_META_BYTES * j + 8, &len, 4);
+    memcpy(pin + L.meta + DEC_META_BYTES * j + 12, &f, 4);
+    if (len) pieces.push_back({pin + o, rq->buf + rq->offsets[j], (size_t)len});
+    o += ((uint64_t)len + 15) & ~(uint64_t)15;
+  }
+  memset(pin + o, 0, 16);
+  auto col = [&](size_t at, const void* src, size_t bytes) {
+    if (bytes) pieces.push_back({pin + at, (const uint8_t*)src, bytes});
+  };
+  col(L.rows, rq->rows, 4 * np);
+  col(L.store, rq->store_index, 4 * np);
+  if (segs) {
+    col(L.seg_store, segs->store.data(), 4 * (size_t)segs->nseg);
+    col(L.seg_off, segs->off.data(), 4 * ((size_t)segs->nseg + 1));
+    col(L.seg_row, segs->row.data(), 4 * np);
+    col(L.seg_in, segs->in.data(), sizeof(FoldState) * (size_t)segs->nseg);
+  }
+  if (dd.m) {
+    col(L.rep, dd.rep, 4 * np);
+    col(L.urow, dd.urow, 4 * (size_t)dd.m);
+  }
+  copy_pieces(pieces, L.stage_bytes);
+}
+
+extern "C" {
+
+int lcv_relay_async(lcv_ctx* ctx, const lcv_relay_request* rq, int slot) {
+  const std::string who = "lcv_relay_async";
+  if (!ctx || !rq || !rq->buf || !rq->offsets || !rq->lengths || !rq->rows || !rq->store_index || !rq->genesis_validators_root)
+    return fail(ctx, LCV_EINVAL, who + ": null argument");
+  if (slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, who + ": slot must be 0..7");
+  if (rq->kind != WIRE_FINALITY && rq->kind != WIRE_OPTIMISTIC)
+    return fail(ctx, LCV_EINVAL, who + ": kind is 1 (finality) or 2 (optimistic); 0 (update) takes the synchronous path");
+  if (!rq->forks && !wire_fork_ok(rq->fork)) return fail(ctx, LCV_EINVAL, who + ": fork is 0 (Deneb), 1 (Capella) or 2 (Altair)");
+  const uint64_t nmsg = rq->nmsg, np = rq->npairs;
+  if (nmsg == 0 || np == 0) return fail(ctx, LCV_EINVAL, who + ": need nmsg > 0 and npairs > 0");
+  if (nmsg > LCV_DECODE_MAX_ROWS)
+    return fail(ctx, LCV_EINVAL, who + ": nmsg = " + std::to_string(nmsg) + " above LCV_DECODE_MAX_ROWS");
+  if (np > ctx->chunk)
+    return fail(ctx, LCV_EINVAL, who + ": npairs = " + std::to_string(np) + " above one chunk of " + std::to_string(ctx->chunk) + " rows");
+  uint64_t msg_bytes = 16;  // the zero padding behind the last message
+  for (uint64_t j = 0; j < nmsg; ++j) {
+    if (rq->lengths[j] > rq->buf_len || rq->offsets[j] > rq->buf_len - rq->lengths[j])
+      return fail(ctx, LCV_EINVAL, who + ": message " + std::to_string(j) + ": offsets + lengths = " + std::to_string(rq->offsets[j]) +
+                                       " + " + std::to_string(rq->lengths[j]) + " is past buf_len " + std::to_string(rq->buf_len));
+    if (rq->lengths[j] <= LCV_RELAY_MAX_BYTES) msg_bytes += (rq->lengths[j] + 15) & ~(uint64_t)15;
+    if (rq->lengths[j] > LCV_RELAY_MAX_BYTES || msg_bytes > LCV_RELAY_MAX_BYTES)
+      return fail(ctx, LCV_EINVAL, who + ": staged bytes above LCV_RELAY_MAX_BYTES at message " + std::to_string(j));
+  }
+  LCV_TRY(prod_check_index(ctx, who.c_str(), "rows", rq->rows, np, nmsg));
+  if (ctx->pipe_streams > 1)
+    return fail(ctx, LCV_EINVAL, who + ": not with a multi-stream pipeline (lcv_set_pipeline streams > 1): sliced chains would need a grouping per slice");
+  if (!ctx->table_set) return fail(ctx, LCV_ESTATE, who + ": lcv_set_store_table has not been called");
+  LCV_TRY(store_index_check(ctx, who.c_str(), rq->store_index, np));
+  return guarded(ctx, who.c_str(), [&]() -> int {
+    // what the modes ask of the host, before anything is staged: the grouping by store (which checks the present
+    // stores' states) and, with lcv_set_dedup on, the grouping into BLS items.  With the mode off nothing is parsed
+    FoldReq req;
+    const FoldSegs* segs = nullptr;
+    if (rq->fold_in) {
+      LCV_TRY(fold_segments(ctx, who.c_str(), rq->store_index, np, ctx->table_dev.nstore, rq->fold_in, ctx->segs));
+      req.in = FoldState{};
+      req.out = nullptr;  // the results wait in the slot's pinned area for lcv_slot_wait_relay
+      req.segs = segs = &ctx->segs;
+    }
+    DedupCols dd = {nullptr, nullptr, 0};
+    if (dedup_on(ctx)) relay_plan(ctx, rq, dd);
+    const size_t ng = segs ? segs->nseg : 0;
+    RelayLayout L;
+    relay_layout(L, (size_t)msg_bytes, (size_t)nmsg, (size_t)np, ng, dd.m);
+    const size_t o_fold = 2 * (size_t)np, o_rec = o_fold + (size_t)FOLD_RESULT_BYTES * ng;
+    const size_t out_bytes = o_rec + (size_t)DEC_REC_BYTES * nmsg;
+    Slot& s = ctx->slot[slot];
+    HostSlot& h = s.host;
+    be_set_slot(ctx, slot);
+    int rc = be_wait_event(ctx, EV_H2D);  // the slot's previous batch has left the pinned region
+    if (rc == LCV_OK && (L.stage_bytes > h.pinned.cap || L.total > h.dev.cap || out_bytes > h.out.cap)) rc = be_sync_slot(ctx);
+    h.staged = h.folded = h.seg_folded = h.relay = false;  // from here on the slot's last batch is this one
+    if (rc == LCV_OK) rc = h.pinned.grow(ctx, L.stage_bytes);
+    if (rc == LCV_OK) rc = h.out.grow(ctx, out_bytes);
+    if (rc == LCV_OK) rc = h.dev.grow(ctx, L.total);
+    uint8_t* d = h.dev.p;
+    if (rc == LCV_OK) {
+      relay_stage(h.pinned.p, L, rq, segs, dd);
+      be_set_slot(ctx, slot);  // (be_free above may not keep the slot)
+      rc = be_h2d(ctx, d, h.pinned.p, L.stage_bytes);
+      if (rc == LCV_OK) rc = be_mark(ctx, EV_H2D, 0);
+    }
+    if (rc == LCV_OK) {  // the table batch: SyncCommittee() as its one pool row, every row's nsc_index 0
+      bind_batch(&h.db, d + L.batch, L.c);
+      h.db.B.store_index = (const uint32_t*)(d + L.store);
+      for (size_t i = 0; i < np; ++i)
+        if (rq->store_index[i] > h.db.max_store) h.db.max_store = rq->store_index[i];
+      if (dd.m) {
+        h.db.plan_rep = (const uint32_t*)(d + L.rep);
+        h.db.plan_urow = (const uint32_t*)(d + L.urow);
+        h.db.plan_m = dd.m;
+      }
+      if (segs) {
+        req.seg_dev.seg_store = (const uint32_t*)(d + L.seg_store);
+        req.seg_dev.seg_off = (const uint32_t*)(d + L.seg_off);
+        req.seg_dev.seg_row = (const uint32_t*)(d + L.seg_row);
+        req.seg_dev.in = d + L.seg_in;
+      }
+      rc = be_memset(ctx, d + L.batch + L.c.off[COL_NSC_POOL], 0, L.c.bytes[COL_NSC_POOL]);
+      if (rc == LCV_OK) rc = be_memset(ctx, d + L.batch + L.c.off[COL_NSC_INDEX], 0, L.c.bytes[COL_NSC_INDEX]);
+    }
+    if (rc == LCV_OK) {  // decode and fan-out in one launch: a team per pair, then a team per message for its status
+      const DecArgs A = {d, d + L.meta, d + L.rec, prod_out(h.db.B), (uint32_t)rq->kind, (uint32_t)DEC_ROWS};
+      const F_wire_relay f = {RelayDecArgs{A, (const uint32_t*)(d + L.rows), (uint32_t)np}};
+      rc = be_relay_mark(ctx, 0);
+      if (rc == LCV_OK) rc = be_launch_team(ctx, f, (uint32_t)(np + nmsg));
+      if (rc == LCV_OK) rc = be_relay_mark(ctx, 1);
+    }
+    be_set_slot(ctx, 0);
+    if (rc != LCV_OK) return rc;
+    ValidateReq q;
+    q.slot = slot;
+    q.fold = segs ? &req : nullptr;
+    LCV_TRY(validate_impl(ctx, &h.db, rq->current_slot, rq->genesis_validators_root, q));
+    be_set_slot(ctx, slot);
+    uint8_t* out = h.out.p;
+    rc = be_d2h(ctx, out, s.W.verdict, np);
+    if (rc == LCV_OK) rc = be_d2h(ctx, out + np, s.W.reason, np);
+    if (rc == LCV_OK && segs) rc = be_d2h(ctx, out + o_fold, s.seg.p, (size_t)FOLD_RESULT_BYTES * ng);
+    if (rc == LCV_OK) rc = be_d2h(ctx, out + o_rec, d + L.rec, (size_t)DEC_REC_BYTES * nmsg);
+    be_set_slot(ctx, 0);
+    if (rc != LCV_OK) return rc;
+    if (segs) h.seg_store = segs->store;  // (throws before the slot is marked: no results that a wait could scatter)
+    h.out_n = np;
+    h.relay_nmsg = nmsg;
+    h.relay_fold = segs != nullptr;
+    h.staged = h.relay = true;
+    return LCV_OK;
+  });
+}
+
+int lcv_slot_wait_relay(lcv_ctx* ctx, int slot, uint8_t* status_out, uint8_t* verdict_out, uint8_t* reason_out,
+                        lcv_fold_result* fold_out) {
+  if (!ctx || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_slot_wait_relay: slot must be 0..7");
+  HostSlot& h = ctx->slot[slot].host;
+  if (!h.staged || !h.relay) return fail(ctx, LCV_ESTATE, "lcv_slot_wait_relay: the slot's last batch was not enqueued by lcv_relay_async");
+  if (fold_out && !h.relay_fold) return fail(ctx, LCV_ESTATE, "lcv_slot_wait_relay: the slot's relay was enqueued without fold_in");
+  LCV_TRY(lcv_slot_wait(ctx, slot, h.out_n, verdict_out, reason_out));  // waits for the slot
+  const size_t o_fold = 2 * (size_t)h.out_n, o_rec = o_fold + (h.relay_fold ? (size_t)FOLD_RESULT_BYTES * h.seg_store.size() : 0);
+  if (status_out)
+    for (uint64_t j = 0; j < h.relay_nmsg; ++j) {
+      uint32_t st;
+      memcpy(&st, h.out.p + o_rec + DEC_REC_BYTES * j, 4);
+      status_out[j] = st ? 1 : 0;
+    }
+  if (fold_out) fold_seg_scatter(fold_out, h.out.p + o_fold, h.seg_store.data(), h.seg_store.size());
+  return LCV_OK;
+}
+
+int lcv_last_relay_timings(lcv_ctx* ctx, int slot, float ms_out[2]) {
+  if (!ctx || !ms_out || slot < 0 || slot >= LCV_SLOTS)
+    return fail(ctx, LCV_EINVAL, "lcv_last_relay_timings: null argument or slot not in 0..7");
+  ms_out[1] = 0.f;
+  return be_relay_ms(ctx, slot, &ms_out[0]);
 }
 
 }  // extern "C"

@@ -36,6 +36,8 @@ struct Backend {
   hipEvent_t fork_ev[BE_STREAMS] = {}, join_ev[BE_STREAMS] = {};
   int base = 0;                          // work-space slot s uses streams st[2s] (main), st[2s + 1] (side)
   hipEvent_t ev[LCV_SLOTS][EV_COUNT] = {};  // the ordering events of run_bls and of staging, per slot
+  hipEvent_t relay_ev[LCV_SLOTS][2] = {};   // lcv_last_relay_timings: created by a slot's first relay
+  bool relay_timed[LCV_SLOTS] = {};
   ncclComm_t comm = nullptr;  // RCCL communicator (lcv_comm_init), collectives on st[0]
   double* comm_scalar = nullptr;       // device scalar of lcv_comm_allreduce_max
   double* comm_host_scalar = nullptr;  // its pinned host staging (copies never block the bounded wait)
@@ -86,6 +88,9 @@ static void be_destroy(lcv_ctx* ctx) {
   for (int s = 0; s < LCV_SLOTS; ++s)
     for (int e = 0; e < EV_COUNT; ++e)
       if (ctx->be.ev[s][e]) (void)hipEventDestroy(ctx->be.ev[s][e]);
+  for (int s = 0; s < LCV_SLOTS; ++s)
+    for (int e = 0; e < 2; ++e)
+      if (ctx->be.relay_ev[s][e]) (void)hipEventDestroy(ctx->be.relay_ev[s][e]);
   if (ctx->be.hold_flag) (void)hipHostFree(ctx->be.hold_flag);
   ctx->be.hold_flag = nullptr;
 }
@@ -229,6 +234,22 @@ static hipEvent_t take_event(lcv_ctx* ctx) {
 }
 // stage marks: HIP events on the stream the stage's kernels are launched on
 static size_t be_event_pool_size(lcv_ctx* ctx) { return ctx->be.pool.size(); }
+static int be_relay_mark(lcv_ctx* ctx, int end) {
+  const int s = ctx->be.base / 2;
+  hipEvent_t& e = ctx->be.relay_ev[s][end ? 1 : 0];
+  if (!e) HIPCHK(ctx, hipEventCreate(&e));
+  if (!end) ctx->be.relay_timed[s] = false;
+  HIPCHK(ctx, hipEventRecord(e, cur_stream(ctx)));
+  if (end) ctx->be.relay_timed[s] = true;
+  return LCV_OK;
+}
+static int be_relay_ms(lcv_ctx* ctx, int slot, float* ms) {
+  *ms = 0.f;
+  if (!ctx->be.relay_timed[slot]) return LCV_OK;
+  HIPCHK(ctx, hipEventSynchronize(ctx->be.relay_ev[slot][1]));
+  HIPCHK(ctx, hipEventElapsedTime(ms, ctx->be.relay_ev[slot][0], ctx->be.relay_ev[slot][1]));
+  return LCV_OK;
+}
 static void be_stage_begin(lcv_ctx* ctx, int stage) {
   if (ctx->marks_off) return;
   hipEvent_t e = take_event(ctx);

@@ -31,6 +31,9 @@ struct Backend {
   std::chrono::steady_clock::time_point t0[4];
   unsigned long long ops0[4][4] = {};
   unsigned long long ops[32][4] = {};  // per stage (ST_COUNT <= 32)
+  std::chrono::steady_clock::time_point relay_t0[8];  // lcv_last_relay_timings, per slot
+  float relay_ms[8] = {};
+  int slot = 0;
   // test-only stand-in for the RCCL communicator: collectives through files in a directory shared by
   // the ranks (the "unique id" is its path), so the multi-process path runs on the CPU (tests/test_multi.py)
   std::string comm_dir;
@@ -43,7 +46,6 @@ struct Backend {
 // the fan engine (device latency mode) computes the batch engine's values: the simulation runs the latter
 template <class F> static int be_launch_sop_fan(lcv_ctx* ctx, const F& f, uint32_t n) { return be_launch_sop(ctx, f, n, 0u); }
 // the host simulation runs every launch in program order: slots, events, forks and joins order nothing
-static void be_set_slot(lcv_ctx*, int) {}
 static int be_mark(lcv_ctx*, int, int) { return 0; }
 static int be_wait(lcv_ctx*, int, int) { return 0; }
 static int be_wait_event(lcv_ctx*, int) { return 0; }
@@ -102,6 +104,19 @@ template <class F> static int be_launch_team(lcv_ctx*, const F& f, uint32_t n) {
     for (uint32_t r = 0; r < R; ++r)
       for (uint32_t lane = 0; lane < F::TEAM; ++lane) f((uint32_t)i, lane, r, lds.data(), shared.data());
   }
+  return LCV_OK;
+}
+// (the slot orders nothing here; only the relay's marks are kept per slot)
+static void be_set_slot(lcv_ctx* ctx, int slot) { ctx->be.slot = slot; }
+static int be_relay_mark(lcv_ctx* ctx, int end) {
+  Backend& b = ctx->be;
+  const auto now = std::chrono::steady_clock::now();
+  if (end) b.relay_ms[b.slot] = std::chrono::duration<float, std::milli>(now - b.relay_t0[b.slot]).count();
+  else b.relay_t0[b.slot] = now;
+  return LCV_OK;
+}
+static int be_relay_ms(lcv_ctx* ctx, int slot, float* ms) {
+  *ms = ctx->be.relay_ms[slot];
   return LCV_OK;
 }
 static void be_use_stream(lcv_ctx* ctx, int k) { ctx->be.cur = (k > 0 && k < 4) ? k : 0; }

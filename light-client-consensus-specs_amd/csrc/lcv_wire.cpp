@@ -61,7 +61,7 @@ bool decode_msg(const uint8_t* p, uint64_t len, uint32_t kind, uint32_t fork, co
   auto put = [](uint32_t, uint32_t) {};  // (the offsets were wire_accept's to check)
   auto header = [&](uint32_t col, uint32_t o, uint32_t elen) {
     wire_walk_header(col, o, fork == WIRE_DENEB, elen, seg, put);
-    std::memcpy(d.p[col][WH_EXEC] + K_EXEC_EXTRALEN_OFF, &elen, 4);
+    if (d.p[col][WH_EXEC]) std::memcpy(d.p[col][WH_EXEC] + K_EXEC_EXTRALEN_OFF, &elen, 4);
   };
   wire_walk_fixed(kind, fork == WIRE_ALTAIR, false, 0u, 0u, seg, put, [](uint32_t, uint32_t, uint32_t) { return false; });  // (columns apart)
   if (fork == WIRE_ALTAIR) return true;
@@ -186,6 +186,26 @@ extern "C" int lcv_ssz_decode_updates_mixed(const uint8_t* buf, const uint64_t* 
   return decode_updates(buf, offsets, lengths, n, kind, [forks](uint64_t i) { return (int)forks[i]; }, out, pool_src,
                         npool_out, status);
 }
+
+// The tuple a class of lcv_set_dedup is made of — attested beacon header, sync bits, signature, signature_slot — of
+// every message, read where the messages lie (lcv_relay_async's grouping: no other column is stored); all zero for a
+// malformed message, as its row is.  Not part of the ABI: the driver declares it (lcv_driver.inc)
+namespace lcv {
+void wire_dedup_tuples(const uint8_t* buf, const uint64_t* offsets, const uint64_t* lengths, uint64_t n, int kind, int fork,
+                       const uint8_t* forks, uint8_t* beacon, uint8_t* bits, uint8_t* sig, uint64_t* slot) {
+  parallel_rows(n, [&](uint64_t lo, uint64_t hi) {
+    for (uint64_t i = lo; i < hi; ++i) {
+      Dest d = {};
+      d.p[WC_ATT][WH_BEACON] = beacon + (uint64_t)K_BEACON * i;
+      d.p[WC_BITS][0] = bits + (uint64_t)K_BITS * i;
+      d.p[WC_SIG][0] = sig + (uint64_t)K_SIG * i;
+      d.p[WC_SLOT][0] = reinterpret_cast<uint8_t*>(slot + i);
+      uint64_t c;
+      decode_msg(buf + offsets[i], lengths[i], (uint32_t)kind, forks ? (uint32_t)forks[i] : (uint32_t)fork, d, &c);
+    }
+  });
+}
+}  // namespace lcv
 
 // LightClientBootstrap (sync-protocol.md:109-115; the layout's kind WIRE_BOOTSTRAP): input of
 // initialize_light_client_store (:351-373)

@@ -4,7 +4,7 @@
 // peer's, so every one of them is checked against the message's length before anything is read through it.
 //
 // The driver stages message i at a 16-byte aligned offset of one device scratch and hands the kernels
-// (dev_off[i], len[i], fork[i]) (DEC_META_BYTES per message).  Three functors, 64-lane teams:
+// (dev_off[i], len[i], fork[i]) (DEC_META_BYTES per message).  Four functors, 64-lane teams:
 //
 // F_wire_dec, one team per message, over one LDS area (DEC_LDS_WORDS):
 //   round 0  the row's raw area (the encoder's ENC_R_* layout) zeroed; a length the kind and fork cannot have is
@@ -20,6 +20,7 @@
 //            zeros.  DEC_PLAN (updates only): the committee as 16-byte loads at message offset 4 (dword aligned) or 112
 //            (Altair), each lane folding (word index, word) into a 64-bit hash and an OR, kept per lane in LDS
 //   round 3  DEC_PLAN: lane 0 combines the lanes' values in lane order; the record gains `zero` and `hash`
+// F_wire_relay, one team per (message, store) pair and one per message: F_wire_dec's rounds through a row map.
 // F_sc_confirm, one team per listed pair: two committees of the scratch compared, one flag.
 // F_sc_gather, one team per pool row: the representative's committee into the pool, aligned 16-byte stores; the
 //   sentinel DEC_NO_COMMITTEE gives the all-zero row (SyncCommittee()).
@@ -92,8 +93,11 @@ struct DecArgs {
   uint32_t kind, phase;
 };
 
-// (`kind` is A.kind as a constant of the call: one instance per kind, as F_wire_enc)
-LCV_FN void item_wire_dec(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, const DecArgs& A, const uint32_t kind) {
+// (`kind` is A.kind as a constant of the call: one instance per kind, as F_wire_enc.)  The rounds, for message i into
+// row `row` of the columns: F_wire_dec's team decodes message i into row i; F_wire_relay's takes its message from a row
+// map (lcv_relay_async).  `recs`: the message's record, or null: not wanted
+LCV_FN void item_wire_dec_to(uint32_t i, uint32_t row, uint8_t* recs, uint32_t lane, uint32_t r, uint32_t* lds, const DecArgs& A,
+                             const uint32_t kind) {
   uint8_t* raw = (uint8_t*)lds;
   uint8_t* img = raw + DEC_IMG;
   const DecMeta M = dec_meta(A.meta, i);
@@ -128,9 +132,9 @@ LCV_FN void item_wire_dec(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, 
     const WirePlan p = wire_accept(kind, M.fork, M.len, [&](uint32_t o) { return dec_rd32(img, o < coff ? o : o - cut); });
     if (lane == 0) {
       lds[DEC_CTL / 4] = p.status;
-      if (A.rec) {
-        const q128 rec = {p.status, 1u, 0u, 0u};
-        st_q128(A.rec, i, rec);
+      if (recs) {
+        const q128 v = {p.status, 1u, 0u, 0u};
+        st_q128(recs, i, v);
       }
     }
     if (p.status) return;
@@ -155,7 +159,7 @@ LCV_FN void item_wire_dec(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, 
   const bool ok = lds[DEC_CTL / 4] == 0u;
   if (A.phase == (uint32_t)DEC_ROWS) {  // round 2: the row
     const ProdOut& O = A.O;
-    const size_t s = i;
+    const size_t s = row;
     dec_store(O.att_beacon + (size_t)K_BEACON * s, raw + ENC_R_ATT + ENC_H_BEACON, K_BEACON, lane, ok);
     dec_store(O.att_exec + (size_t)K_EXEC * s, raw + ENC_R_ATT + ENC_H_EXEC, K_EXEC, lane, ok);
     dec_store(O.att_branch + (size_t)K_EXEC_BRANCH * s, raw + ENC_R_ATT + ENC_H_BRANCH, K_EXEC_BRANCH, lane, ok);
@@ -195,9 +199,28 @@ LCV_FN void item_wire_dec(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, 
       h = dec_mix(h, (uint64_t)v.x | ((uint64_t)v.y << 32));
       any |= v.z;
     }
-    const q128 rec = {0u, any ? 0u : 1u, (uint32_t)h, (uint32_t)(h >> 32)};
-    st_q128(A.rec, i, rec);
+    const q128 v = {0u, any ? 0u : 1u, (uint32_t)h, (uint32_t)(h >> 32)};
+    st_q128(recs, i, v);
   }
+}
+LCV_FN void item_wire_dec(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, const DecArgs& A, const uint32_t kind) {
+  item_wire_dec_to(i, i, A.rec, lane, r, lds, A, kind);
+}
+
+// ---- the relay's decode with a row map (lcv_relay_async): team i < npairs decodes message rows[i] straight into row
+// i of the slot's table batch — no batch of nmsg rows in between, no gather launch: a message relayed to many stores is
+// read that often from L2 — and team npairs + j runs rounds 0 and 1 for message j alone and stores its record, so that
+// every message has its status, named by a pair or not, and each record has one writer.  rows[i] < nmsg is the
+// driver's check, before the launch
+struct RelayDecArgs {
+  DecArgs D;             // phase DEC_ROWS; rec: [nmsg]; O: the npairs rows' columns
+  const uint32_t* rows;  // [npairs]
+  uint32_t npairs;
+};
+LCV_FN void item_wire_relay(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, const RelayDecArgs& A, const uint32_t kind) {
+  const bool pair = i < A.npairs;
+  if (!pair && r >= 2u) return;  // a status team has no row
+  item_wire_dec_to(pair ? A.rows[i] : i - A.npairs, i, pair ? nullptr : A.D.rec, lane, r, lds, A.D, kind);
 }
 
 // ---- the pool: full compares of candidate committees, and the gather of the distinct ones
@@ -255,6 +278,15 @@ struct F_wire_dec {
     if (A.kind == (uint32_t)lcv::WIRE_UPDATE) lcv::item_wire_dec(i, lane, r, lds, A, lcv::WIRE_UPDATE);
     else if (A.kind == (uint32_t)lcv::WIRE_FINALITY) lcv::item_wire_dec(i, lane, r, lds, A, lcv::WIRE_FINALITY);
     else lcv::item_wire_dec(i, lane, r, lds, A, lcv::WIRE_OPTIMISTIC);
+  }
+};
+struct F_wire_relay {  // (the gossip kinds only: a full update's committee pool needs the host in between)
+  lcv::RelayDecArgs A;
+  static constexpr uint32_t TEAM = lcv::DEC_TEAM, LDS_WORDS = lcv::DEC_LDS_WORDS, SHARED_WORDS = 0;
+  LCV_HD uint32_t rounds() const { return 3u; }
+  LCV_HD void operator()(uint32_t i, uint32_t lane, uint32_t r, uint32_t* lds, uint32_t*) const {
+    if (A.D.kind == (uint32_t)lcv::WIRE_FINALITY) lcv::item_wire_relay(i, lane, r, lds, A, lcv::WIRE_FINALITY);
+    else lcv::item_wire_relay(i, lane, r, lds, A, lcv::WIRE_OPTIMISTIC);
   }
 };
 struct F_sc_confirm {

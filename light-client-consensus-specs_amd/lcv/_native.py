@@ -85,6 +85,14 @@ class FoldResultC(C.Structure):
     ]
 
 
+class RelayRequest(C.Structure):
+    """lcv_relay_request."""
+    _fields_ = [("buf", u8p), ("buf_len", C.c_uint64), ("offsets", u64p), ("lengths", u64p), ("nmsg", C.c_uint64),
+                ("kind", C.c_int), ("fork", C.c_int), ("forks", u8p), ("rows", u32p), ("store_index", u32p),
+                ("npairs", C.c_uint64), ("current_slot", C.c_uint64), ("genesis_validators_root", u8p),
+                ("fold_in", C.POINTER(FoldStateC))]
+
+
 class StateViews(C.Structure):
     """lcv_state_views."""
     _fields_ = [("slot", u64p), ("latest_block_header", u8p), ("fin_epoch", u64p), ("fin_root", u8p),
@@ -198,6 +206,9 @@ SIGNATURES = {
                                    C.POINTER(C.c_void_p)]),
     "lcv_last_decode_timings": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "lcv_debug_decode_hash_bits": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "lcv_relay_async": (C.c_int, [C.c_void_p, C.POINTER(RelayRequest), C.c_int]),
+    "lcv_slot_wait_relay": (C.c_int, [C.c_void_p, C.c_int, u8p, u8p, u8p, C.POINTER(FoldResultC)]),
+    "lcv_last_relay_timings": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "lcv_batch_shape": (C.c_int, [C.c_void_p, C.c_void_p, u64p, u64p]),
     "lcv_ssz_decode_updates": (C.c_int, [u8p, u64p, u64p, C.c_uint64, C.c_int, C.c_int, C.POINTER(UpdateBatch),
                                          u64p, u64p, u8p]),

@@ -11,7 +11,7 @@ import numpy as np
 from . import config as _config
 from . import layout as L
 from ._native import (Lib, LcvError, UpdateBatch, HeaderCols, StoreTable, FoldStateC, FoldResultC, StateViews,
-                      BlockViews, UpdateCases, STORE_NEXT_UNKNOWN, as_u8, load, ptr)
+                      BlockViews, UpdateCases, RelayRequest, STORE_NEXT_UNKNOWN, as_u8, load, ptr)
 
 SYNC_COMMITTEE_BYTES = 24624
 EXEC_RECORD_BYTES = 832
@@ -648,6 +648,65 @@ class Verifier:
         """Test hook (lcv_debug_decode_hash_bits): the committee hash of decode_resident's pool grouping truncated to
         `bits` bits (64: whole; 0: every committee collides, so only the full compares separate them)."""
         self._check(self.lib.lcv_debug_decode_hash_bits(self.ctx, int(bits)), "lcv_debug_decode_hash_bits")
+
+    # ------------------------------------------------------------------ the asynchronous relay (include/lcv.h)
+    def relay_async(self, messages, kind, fork, rows, store_index, current_slot: int, genesis_validators_root: bytes,
+                    slot: int, fold_in: Optional[Sequence[FoldState]] = None) -> None:
+        """Wire messages to per-store verdicts, enqueued on work-space slot `slot` without a wait (lcv_relay_async):
+        pair i is message rows[i] for the store of table row store_index[i], validated against the table of
+        set_store_table under the verifier's set_dedup / set_rlc settings.  `messages`, `kind` ("finality" or
+        "optimistic"), `fork` as lcv.wire.decode_updates takes them.  `fold_in`: one FoldState per store row of the
+        table -> the per-store fold as validate_stores_async_fold's.  Collect with slot_wait_relay(slot)."""
+        from . import wire
+        if kind not in wire.KINDS:
+            raise ValueError(f"kind must be one of {list(wire.KINDS)}")
+        buf, offs, lens = wire._flatten(messages)
+        n = int(offs.size)
+        fcode, forks = wire._fork_codes(fork, n)
+        ix = np.ascontiguousarray(rows, np.uint32).reshape(-1)
+        six = np.ascontiguousarray(store_index, np.uint32).reshape(-1)
+        if ix.shape != six.shape:
+            raise ValueError("one store_index per row")
+        gvr = as_u8(bytes(genesis_validators_root))
+        if gvr.size != 32:
+            raise ValueError("genesis_validators_root: 32 bytes")
+        src = buf if buf.size else np.zeros(1, np.uint8)
+        o = offs if n else np.zeros(1, np.uint64)
+        ln = lens if n else np.zeros(1, np.uint64)
+        pix = ix if ix.size else np.zeros(1, np.uint32)
+        psix = six if six.size else np.zeros(1, np.uint32)
+        present, st = [], None
+        if fold_in is not None:
+            present = np.unique(six).tolist()
+            self._fold_states_cover(fold_in, present)
+            st = self._fold_states(fold_in, 1)
+        rq = RelayRequest(ptr(src), int(buf.size), ptr(o, C.c_uint64), ptr(ln, C.c_uint64), n, wire.KINDS[kind],
+                          0 if fcode is None else fcode, None if forks is None or not n else ptr(forks),
+                          ptr(pix, C.c_uint32), ptr(psix, C.c_uint32), int(ix.size), int(current_slot), ptr(gvr), st)
+        self._check(self.lib.lcv_relay_async(self.ctx, C.byref(rq), int(slot)), "lcv_relay_async")
+        self._relay = getattr(self, "_relay", {})
+        self._relay[int(slot)] = (n, int(ix.size), None if fold_in is None else (len(fold_in), present))
+
+    def slot_wait_relay(self, slot: int):
+        """Wait for the relay enqueued on `slot` -> (ok: message j decoded, verdicts, reason codes[, fold results: one
+        FoldResult per store row, None for stores without a pair — only for a relay enqueued with fold_in]); LcvError
+        (status -4) if the slot's last batch was not a relay."""
+        nmsg, npairs, fold = getattr(self, "_relay", {}).get(int(slot), (0, 0, None))
+        status = np.ones(max(nmsg, 1), np.uint8)
+        v = np.zeros(max(npairs, 1), np.uint8)
+        r = np.zeros(max(npairs, 1), np.uint8)
+        res = None if fold is None else (FoldResultC * max(1, fold[0]))()
+        self._check(self.lib.lcv_slot_wait_relay(self.ctx, int(slot), ptr(status), ptr(v), ptr(r), res),
+                    "lcv_slot_wait_relay")
+        out = (status[:nmsg] == 0, v[:npairs].astype(bool), r[:npairs])
+        return out if fold is None else out + (self._fold_results(res, fold[1])[:fold[0]],)
+
+    def last_relay_timings(self, slot: int) -> Tuple[float, float]:
+        """Device milliseconds of the last relay on `slot` (lcv_last_relay_timings; waits for its kernel): (decode +
+        fan-out kernel, 0.0)."""
+        ms = (C.c_float * 2)()
+        self._check(self.lib.lcv_last_relay_timings(self.ctx, int(slot), ms), "lcv_last_relay_timings")
+        return float(ms[0]), float(ms[1])
 
     def create_bootstraps(self, views: PackedViews, state_idx, block_idx, reason: Optional[np.ndarray] = None):
         """create_light_client_bootstrap per (state_idx[i], block_idx[i]) (lcv_create_bootstraps) -> (beacon (n, 112),

@@ -8,15 +8,18 @@ update) may be mixed in one stream.
 
 `relay_updates`: the relay's path with every row kept on the device — wire messages decoded, classed and fanned out
 to the stores of many clients, validated with each distinct signature checked once.
+
+`relay_stream`: the serving loop over that path for gossip messages, several items in flight (lcv_relay_async): one
+call per item stages the bytes and the pair list and enqueues decode, fan-out and validation on a slot.
 """
 from __future__ import annotations
 
 from collections import deque
-from typing import Iterable, Iterator, NamedTuple, Optional, Tuple, Union
+from typing import Iterable, Iterator, NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from .device import PackedUpdates, ResidentBatch, Verifier
+from .device import FoldState, PackedUpdates, ResidentBatch, Verifier
 
 SLOTS = 8            # work-space slots of a context (LCV_SLOTS)
 MAX_ROWS = 65536     # rows of one asynchronous call
@@ -166,4 +169,63 @@ def relay_updates(verifier: Verifier, messages, kind: str, fork, rows, store_ind
     finally:
         decoded.free()
         if verifier.dedup != dedup_before:
+            verifier.set_dedup(dedup_before)
+
+
+class RelayStreamResult(NamedTuple):
+    """One item of relay_stream: RelayResult's fields without a resident batch — a relay forwards the bytes it already
+    holds — and `fold`: with fold_states, one FoldResult per store row (None for stores without a pair), else None."""
+    ok: np.ndarray
+    verdict: np.ndarray
+    reason: np.ndarray
+    dedup: Tuple[int, int]
+    fold: Optional[list]
+
+
+def relay_stream(verifier: Verifier, items: Iterable[tuple], current_slot: int, genesis_validators_root: bytes,
+                 in_flight: int = SLOTS, dedup: Optional[bool] = True,
+                 fold_states: Optional[Sequence[FoldState]] = None) -> Iterator[RelayStreamResult]:
+    """The relay's serving loop: every item (messages, kind, fork, rows, store_index) — as relay_updates takes them,
+    kind "finality" or "optimistic", at most 65,536 pairs — goes through Verifier.relay_async on work-space slots
+    0 .. in_flight - 1 in turn, and one RelayStreamResult per item is yielded in input order.  The generator waits for
+    a slot only when it is about to reuse it (and, after the last item, for what is left).  The store table must be
+    set before an item is drawn; no other call may use the verifier's slots while the generator is live; closing it
+    early waits for the slots in flight.
+
+    `dedup`: a bool sets Verifier.set_dedup for the stream — each distinct signature of an item checked once — and the
+    previous setting is restored when the generator ends, also after an exception; None leaves the setting alone.
+    `fold_states`: one FoldState per store row of the table -> every item is folded per store from these states
+    (Verifier.validate_stores_fold's results; carrying a store's state from item to item is the caller's)."""
+    in_flight = int(in_flight)
+    if not 1 <= in_flight <= SLOTS:
+        raise ValueError(f"in_flight must be 1..{SLOTS}")
+    gvr = bytes(genesis_validators_root)
+    pending = deque()  # slots in flight, oldest first
+    next_slot = 0
+    dedup_before = bool(verifier.dedup)
+    if dedup is not None:
+        verifier.set_dedup(bool(dedup))
+
+    def finish_oldest():
+        slot = pending[0]
+        out = verifier.slot_wait_relay(slot)
+        pending.popleft()
+        return RelayStreamResult(out[0], out[1], out[2], verifier.last_dedup(slot), out[3] if len(out) > 3 else None)
+
+    try:
+        for messages, kind, fork, rows, store_index in items:
+            if len(pending) == in_flight:  # the oldest item holds next_slot
+                yield finish_oldest()
+            verifier.relay_async(messages, kind, fork, rows, store_index, current_slot, gvr, next_slot, fold_states)
+            pending.append(next_slot)
+            next_slot = (next_slot + 1) % in_flight
+        while pending:
+            yield finish_oldest()
+    finally:
+        for slot in pending:  # closed early or failed: nothing stays in flight
+            try:
+                verifier.slot_wait(slot, 0)
+            except Exception:
+                pass
+        if dedup is not None and verifier.dedup != dedup_before:
             verifier.set_dedup(dedup_before)
