@@ -145,23 +145,37 @@ struct lcv_dbatch {
   uint32_t plan_m = 0;
 };
 
-// host-input serving path (lcv_validate_async): per work-space slot, a pinned host staging copy of the
-// packed batch (so the host->device copy is a DMA that overlaps the other slots' kernels), the batch's
-// device copy, and pinned verdict / reason bytes copied back at the end of the slot's pipeline
+// What the pinned `out` region of a HostSlot holds, [n verdicts][n reasons][fold result(s)][status records], by the
+// entry that put the batch there: nothing a wait could hand out (lcv_validate_resident_async, a failed enqueue), the two
+// arrays alone (lcv_validate_async, _stores_async), with one fold result (_async_fold), with one per store present
+// (_stores_async_fold), or a relay's: a status record per message, without or with its fold's per-store results
+enum ResultKind : uint8_t { RES_NONE, RES_VERDICTS, RES_FOLD, RES_FOLD_SEG, RES_RELAY, RES_RELAY_FOLD };
+struct SlotResults {
+  ResultKind kind = RES_NONE;
+  size_t n = 0, nseg = 0, nmsg = 0;  // rows; stores present (the by-store kinds); messages (the relay kinds)
+  bool by_store() const { return kind == RES_FOLD_SEG || kind == RES_RELAY_FOLD; }
+  bool relay() const { return kind == RES_RELAY || kind == RES_RELAY_FOLD; }
+};
+// ... and where its parts begin, the one place that knows (the two arrays alone keep one result's room behind them: a
+// slot that alternates between lcv_validate_async and lcv_validate_async_fold does not regrow)
+struct ResultOffsets { size_t reasons, fold, rec, total; };
+static ResultOffsets results_offsets(const SlotResults& r) {
+  const size_t fold = 2 * r.n;
+  const size_t rec = fold + (size_t)FOLD_RESULT_BYTES * (r.by_store() ? r.nseg : r.kind == RES_RELAY ? 0 : 1);
+  return {r.n, fold, rec, rec + (size_t)DEC_REC_BYTES * r.nmsg};
+}
+
+// host-input serving path (lcv_validate_async and its kin, lcv_relay_async): per work-space slot, a pinned host staging
+// copy of what the batch brings (so the host->device copy is a DMA that overlaps the other slots' kernels), its device
+// copy, and the pinned region `out` the results are copied back into at the end of the slot's pipeline.  `res` says
+// what `out` holds: set last by the entry that enqueued the batch, cleared before a buffer is regrown (stage_transit)
+// and by any other asynchronous batch on the slot, read by the waits.  ctx->hsync: the same, synchronous, on slot 0
 struct HostSlot {
   PinBuf pinned;
   DevBuf dev;
-  PinBuf out;  // [cap] verdicts, then [cap] reasons
-  uint64_t out_n = 0;
-  bool staged = false;     // out holds the slot's last batch (lcv_slot_wait reads it)
-  bool folded = false;     // ... and, after its 2 out_n bytes, that batch's fold result (lcv_slot_wait_fold)
-  // ... or (lcv_validate_stores_async_fold) one result (FOLD_RESULT_BYTES) per store present, for the store rows seg_store
-  bool seg_folded = false;
-  std::vector<uint32_t> seg_store;
-  // ... or (lcv_relay_async) a relay's: after the 2 out_n bytes the per-store results of its fold, if it has one
-  // (relay_fold; seg_store as above), then one DEC_REC_BYTES status record per message (lcv_slot_wait_relay)
-  bool relay = false, relay_fold = false;
-  uint64_t relay_nmsg = 0;
+  PinBuf out;
+  SlotResults res;
+  std::vector<uint32_t> seg_store;  // the by-store kinds' scatter map: the store row of each of the nseg results
   lcv_dbatch db;  // (a view of `dev`: owns nothing)
   void release(lcv_ctx* ctx) {
     dev.release(ctx);
@@ -357,6 +371,35 @@ struct F_sig_direct { BatchDev B; Work W; LCV_HD void operator()(uint32_t i) con
 struct F_h2c_direct { Work W; LCV_HD void operator()(uint32_t i) const { item_h2c_direct(i, W); } };
 struct F_pair_direct { Work W; LCV_HD void operator()(uint32_t i) const { item_pairing_direct(i, W); } };
 #endif
+
+// The way of every host-input batch into the HostSlot h: `stage_bytes` filled by fill(pinned region) go through h's
+// reused pinned staging buffer and ONE DMA into h's reused device copy of dev_bytes, on the slot's main stream, instead
+// of a device allocation, one copy per part and a free per call.  slot >= 0 (the enqueuing entries, h =
+// ctx->slot[slot].host): the staging buffer is reused only after the slot's previous batch has left it (EV_H2D, recorded
+// behind the copy); the slot is waited for before a buffer it may still use is regrown; h.res is cleared BEFORE anything
+// regrows (a failed grow leaves an empty buffer; from here on the slot's last batch is this one); slot 0 is the active
+// one again on return.  slot < 0: the synchronous entries, h = ctx->hsync, on slot 0; out_bytes 0 (chunk_results' to grow)
+template <class Fill>
+static int stage_transit(lcv_ctx* ctx, int slot, HostSlot& h, size_t stage_bytes, size_t dev_bytes, size_t out_bytes,
+                         Fill&& fill) {
+  const bool async = slot >= 0;
+  be_set_slot(ctx, async ? slot : 0);
+  int rc = async ? be_wait_event(ctx, EV_H2D) : LCV_OK;
+  if (async && rc == LCV_OK && (stage_bytes > h.pinned.cap || dev_bytes > h.dev.cap || out_bytes > h.out.cap))
+    rc = be_sync_slot(ctx);
+  h.res = SlotResults{};
+  if (rc == LCV_OK) rc = h.pinned.grow(ctx, stage_bytes);
+  if (rc == LCV_OK && out_bytes) rc = h.out.grow(ctx, out_bytes);
+  if (rc == LCV_OK) rc = h.dev.grow(ctx, dev_bytes);
+  if (rc == LCV_OK) {
+    fill(h.pinned.p);
+    be_set_slot(ctx, async ? slot : 0);  // (be_free above may not keep the slot)
+    rc = be_h2d(ctx, h.dev.p, h.pinned.p, stage_bytes);
+    if (async && rc == LCV_OK) rc = be_mark(ctx, EV_H2D, 0);
+  }
+  if (async) be_set_slot(ctx, 0);
+  return rc;
+}
 
 // ------------------------------------------------------------------ helpers
 // latency mode for batches of at most ctx->fan_max rows: the fan engine for the SOP programs (identical results,
@@ -1201,14 +1244,14 @@ static int fold_state_in(lcv_ctx* ctx, const char* who, const lcv_fold_state* in
 static int fold_stage(lcv_ctx* ctx, const FoldState& in, uint64_t store_fin_slot, uint32_t next_known, uint32_t n) {
   return stage(ctx, ST_FOLD, [&] { return be_launch_team(ctx, F_fold{ctx->W, in, store_fin_slot, next_known, n}, 1); });
 }
-// the segmented fold's device side.  seg_bind: the grouping's columns of a staged batch (COL_SEG_*) in its
-// device copy m.  ensure_fold_seg: the slot's result buffer (be_free waits for the streams).  fold_seg_stage:
-// F_fold_seg, one team per store present, where fold_stage would run F_fold
-static void seg_bind(FoldReq& f, uint8_t* m, const BatchCols& c) {
-  f.seg_dev.seg_store = (const uint32_t*)(m + c.off[COL_SEG_STORE]);
-  f.seg_dev.seg_off = (const uint32_t*)(m + c.off[COL_SEG_OFF]);
-  f.seg_dev.seg_row = (const uint32_t*)(m + c.off[COL_SEG_ROW]);
-  f.seg_dev.in = m + c.off[COL_SEG_IN];
+// the segmented fold's device side.  seg_bind: the grouping's four columns in a staged device copy m, at its layout's
+// offsets (a host batch's COL_SEG_*, a relay's RelayLayout).  ensure_fold_seg: the slot's result buffer (be_free waits
+// for the streams).  fold_seg_stage: F_fold_seg, one team per store present, where fold_stage would run F_fold
+static void seg_bind(FoldReq& f, const uint8_t* m, size_t store, size_t off, size_t row, size_t in) {
+  f.seg_dev.seg_store = (const uint32_t*)(m + store);
+  f.seg_dev.seg_off = (const uint32_t*)(m + off);
+  f.seg_dev.seg_row = (const uint32_t*)(m + row);
+  f.seg_dev.in = m + in;
 }
 static int ensure_fold_seg(lcv_ctx* ctx, int slot, size_t nseg) {
   DevBuf& seg = ctx->slot[slot].seg;
@@ -1223,6 +1266,37 @@ static int fold_seg_stage(lcv_ctx* ctx, const Work& W, const StoreDev& S, const 
 // by store row: only the present stores' entries are written
 static void fold_seg_scatter(lcv_fold_result* out, const uint8_t* res, const uint32_t* seg_store, size_t nseg) {
   for (size_t g = 0; g < nseg; ++g) memcpy(&out[seg_store[g]], res + FOLD_RESULT_BYTES * g, sizeof(FoldResult));
+}
+
+// The results named by r on their way into the pinned region `out`, on the current slot's stream, behind the batch:
+// the verdicts and reasons of the work space W, the fold result from W.fold_out or (the by-store kinds) the slot's
+// `seg` buffer, a relay's status records from `rec`.  No wait: results_hand_out follows the caller's sync
+static int results_enqueue(lcv_ctx* ctx, uint8_t* out, const SlotResults& r, const Work& W, const uint8_t* seg,
+                           const uint8_t* rec) {
+  const ResultOffsets o = results_offsets(r);
+  LCV_TRY(be_d2h(ctx, out, W.verdict, r.n));
+  LCV_TRY(be_d2h(ctx, out + o.reasons, W.reason, r.n));
+  if (r.by_store()) LCV_TRY(be_d2h(ctx, out + o.fold, seg, (size_t)FOLD_RESULT_BYTES * r.nseg));
+  else if (r.kind == RES_FOLD) LCV_TRY(be_d2h(ctx, out + o.fold, W.fold_out, sizeof(FoldResult)));
+  if (r.relay()) LCV_TRY(be_d2h(ctx, out + o.rec, rec, (size_t)DEC_REC_BYTES * r.nmsg));
+  return LCV_OK;
+}
+// ... and out of it once they have arrived: the first n verdicts and reasons, the fold result (fold_out indexed by
+// store row for the by-store kinds, seg_store their scatter map) and a relay's status bytes, each where the caller
+// asks for it and r has it.  Nothing is consumed: a repeated wait hands out the same bytes
+static void results_hand_out(const uint8_t* out, const SlotResults& r, const uint32_t* seg_store, size_t n,
+                             uint8_t* verdict_out, uint8_t* reason_out, lcv_fold_result* fold_out, uint8_t* status_out) {
+  const ResultOffsets o = results_offsets(r);
+  if (n && verdict_out) memcpy(verdict_out, out, n);
+  if (n && reason_out) memcpy(reason_out, out + o.reasons, n);
+  if (fold_out && r.by_store()) fold_seg_scatter(fold_out, out + o.fold, seg_store, r.nseg);
+  else if (fold_out && r.kind == RES_FOLD) memcpy(fold_out, out + o.fold, sizeof(FoldResult));
+  if (status_out && r.relay())
+    for (size_t j = 0; j < r.nmsg; ++j) {
+      uint32_t st;
+      memcpy(&st, out + o.rec + DEC_REC_BYTES * j, 4);
+      status_out[j] = st ? 1 : 0;
+    }
 }
 
 // What a validation is asked for: where the verdicts and reasons go — to host memory, to a device buffer, or
@@ -1247,10 +1321,8 @@ struct ValidateRun {
   const StoreDev* S;       // the store table of a batch that carries its store_index, else null
   const FoldSegs* segs;    // a segmented fold: a table batch, its rows grouped by store
   FoldSegDev seg_dev;
-  size_t fold_bytes;
   bool dedup;       // lcv_set_dedup: the chunks run the BLS half once per distinct item
   bool rlc;         // lcv_set_rlc: the batch-engine chunks pay one final exponentiation per group of items
-  bool pinned_out = false;  // the results wait in ctx->hsync.out for validate_finish
 };
 
 // argument and state checks, the slot's work space, Params and the committee view
@@ -1297,7 +1369,6 @@ static int validate_prepare(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot,
     v.seg_dev = fold->seg_dev;
     v.seg_dev.out = ctx->slot[v.slot].seg.p;
   }
-  v.fold_bytes = segs ? (size_t)FOLD_RESULT_BYTES * segs->nseg : (size_t)FOLD_RESULT_BYTES;
   v.P.cfg = ctx->cfg;
   v.P.current_slot = current_slot;
   v.P.store_fin_slot = ctx->store_fin_slot;
@@ -1370,13 +1441,10 @@ static int chunk_results(ValidateRun& v, size_t base, uint32_t m) {
     // one chunk: both arrays (and a fold's result) into pinned memory without a wait each, handed out by
     // validate_finish after its sync
     HostSlot& h = ctx->hsync;
-    LCV_TRY(h.out.grow(ctx, 2 * (size_t)m + v.fold_bytes));
-    uint8_t* out = h.out.p;
-    LCV_TRY(be_d2h(ctx, out, ctx->W.verdict, m));
-    LCV_TRY(be_d2h(ctx, out + m, ctx->W.reason, m));
-    if (v.segs) LCV_TRY(be_d2h(ctx, out + 2 * (size_t)m, v.seg_dev.out, v.fold_bytes));
-    else if (q.fold) LCV_TRY(be_d2h(ctx, out + 2 * (size_t)m, ctx->W.fold_out, sizeof(FoldResult)));
-    v.pinned_out = true;
+    const SlotResults r = {v.segs ? RES_FOLD_SEG : q.fold ? RES_FOLD : RES_VERDICTS, m, v.segs ? v.segs->nseg : 0u, 0};
+    LCV_TRY(h.out.grow(ctx, results_offsets(r).total));
+    LCV_TRY(results_enqueue(ctx, h.out.p, r, ctx->W, v.seg_dev.out, nullptr));
+    h.res = r;
   } else {
     if (q.verdict_host) LCV_TRY(be_d2h(ctx, q.verdict_host + base, ctx->W.verdict, m));
     if (q.reason_host) LCV_TRY(be_d2h(ctx, q.reason_host + base, ctx->W.reason, m));
@@ -1389,13 +1457,10 @@ static int validate_finish(ValidateRun& v) {
   lcv_ctx* ctx = v.ctx;
   const ValidateReq& q = v.q;
   LCV_TRY(be_sync(ctx));
-  if (v.pinned_out) {
-    const uint8_t* out = ctx->hsync.out.p;
-    if (q.verdict_host) memcpy(q.verdict_host, out, v.n);
-    if (q.reason_host) memcpy(q.reason_host, out + v.n, v.n);
-    if (v.segs && q.fold->out) fold_seg_scatter(q.fold->out, out + 2 * v.n, v.segs->store.data(), v.segs->nseg);
-    else if (q.fold && q.fold->out) memcpy(q.fold->out, out + 2 * v.n, sizeof(FoldResult));
-  }
+  const HostSlot& h = ctx->hsync;
+  if (h.res.kind != RES_NONE)
+    results_hand_out(h.out.p, h.res, v.segs ? v.segs->store.data() : nullptr, v.n, q.verdict_host, q.reason_host,
+                     q.fold ? q.fold->out : nullptr, nullptr);
   be_collect_timings(ctx);
   return LCV_OK;
 }
@@ -1489,10 +1554,10 @@ static int validate_impl(lcv_ctx* ctx, lcv_dbatch* db, uint64_t current_slot, co
   s.rl_groups = 0;
   s.rl_used = 0;
   const bool marks_were_off = ctx->marks_off;
-  if (v.async) {
-    ctx->marks_off = true;  // nothing collects an asynchronous batch's stage marks
-    s.host.staged = s.host.folded = s.host.seg_folded = s.host.relay = false;
-  }
+  if (v.async) ctx->marks_off = true;  // nothing collects an asynchronous batch's stage marks
+  // the pinned results of the slot's (synchronous: hsync's) last batch are no longer this batch's: the one-chunk
+  // synchronous path and the enqueuing entries name the new ones once they are on their way
+  (v.async ? s.host : ctx->hsync).res = SlotResults{};
   // (the boundary: a resident chunk's grouping under lcv_set_dedup allocates host memory, dedup_chunk)
   const int rc = guarded(ctx, "validate", [&] {
     return piped ? validate_sliced(v, ns) : (!v.async && v.n > v.cap) ? validate_rotating(v) : validate_single(v);
@@ -1568,39 +1633,40 @@ static void stage_columns(uint8_t* dst, const BatchCols& c) {
   copy_pieces(pieces, c.total);
 }
 
-// A one-chunk host batch into the HostSlot h: its columns (with a segmented fold's grouping `segs` and, under
-// lcv_set_dedup, its grouping into BLS items: both travel with the batch) go through h's reused pinned staging
-// buffer and ONE DMA into h's reused device copy, on the slot's main stream, instead of a device allocation, one
-// copy per column and a free per call; h.db then names the device columns, and fold->seg_dev the grouping's.
-// slot < 0: the synchronous entries, h = ctx->hsync, on slot 0.  slot >= 0 (lcv_validate_async and its kin, h =
-// ctx->slot[slot].host): the staging buffer is reused only after the slot's previous batch has left it (EV_H2D,
-// recorded behind the copy), the slot is waited for before a buffer it may still use is regrown, h.out is grown
-// for the verdicts, the reasons and a fold's result (a segmented fold's: one per store present), and slot 0 is
-// the active one again on return
+// A one-chunk host batch into the HostSlot h (stage_transit): its columns, with a segmented fold's grouping `segs` and,
+// under lcv_set_dedup, its grouping into BLS items, which both travel with the batch; h.db then names the device
+// columns, and fold->seg_dev the grouping's.  `r`: what the batch's results will be (the enqueuing entries' h.out)
 static int stage_host_batch(lcv_ctx* ctx, const char* who, const lcv_update_batch* hb, const uint32_t* store_index,
-                            FoldReq* fold, int slot, HostSlot& h, BatchCols& c) {
-  const bool async = slot >= 0;
+                            FoldReq* fold, int slot, HostSlot& h, SlotResults& r) {
   const FoldSegs* segs = fold ? fold->segs : nullptr;
   DedupCols dd;
+  BatchCols c;
   LCV_TRY(dedup_stage(ctx, hb, store_index, dd));
   LCV_TRY(batch_cols(ctx, hb, c, who, store_index, segs, dd.m ? &dd : nullptr));
-  be_set_slot(ctx, async ? slot : 0);
-  const size_t out_bytes = 2 * c.n + (size_t)FOLD_RESULT_BYTES * (segs ? segs->nseg : 1);
-  int rc = async ? be_wait_event(ctx, EV_H2D) : LCV_OK;
-  if (async && rc == LCV_OK && (c.total > h.pinned.cap || out_bytes > h.out.cap)) rc = be_sync_slot(ctx);
-  if (rc == LCV_OK) rc = h.pinned.grow(ctx, c.total);
-  if (async && rc == LCV_OK) rc = h.out.grow(ctx, out_bytes);
-  if (rc == LCV_OK) rc = h.dev.grow(ctx, c.total);
-  if (rc == LCV_OK) {
-    stage_columns(h.pinned.p, c);
-    be_set_slot(ctx, async ? slot : 0);  // (be_free above may not keep the slot)
-    rc = be_h2d(ctx, h.dev.p, h.pinned.p, c.total);
-    if (async && rc == LCV_OK) rc = be_mark(ctx, EV_H2D, 0);
-  }
-  if (async) be_set_slot(ctx, 0);
-  if (rc != LCV_OK) return rc;
+  r = {segs ? RES_FOLD_SEG : fold ? RES_FOLD : RES_VERDICTS, (size_t)c.n, segs ? segs->nseg : 0u, 0};
+  LCV_TRY(stage_transit(ctx, slot, h, c.total, c.total, slot >= 0 ? results_offsets(r).total : 0,
+                        [&](uint8_t* pin) { stage_columns(pin, c); }));
   bind_batch(&h.db, h.dev.p, c);
-  if (segs) seg_bind(*fold, h.dev.p, c);
+  if (segs) seg_bind(*fold, h.dev.p, c.off[COL_SEG_STORE], c.off[COL_SEG_OFF], c.off[COL_SEG_ROW], c.off[COL_SEG_IN]);
+  return LCV_OK;
+}
+
+// The common tail of the enqueuing entries, the batch staged in ctx->slot[slot].host: the whole pipeline on the slot's
+// streams (validate_impl), the results r on their way into the pinned region behind it, then the slot's record
+static int slot_enqueue(lcv_ctx* ctx, int slot, uint64_t current_slot, const uint8_t* gvr, const FoldReq* fold,
+                        const SlotResults& r, const uint8_t* rec) {
+  Slot& s = ctx->slot[slot];
+  HostSlot& h = s.host;
+  ValidateReq q;
+  q.slot = slot;
+  q.fold = fold;
+  LCV_TRY(validate_impl(ctx, &h.db, current_slot, gvr, q));
+  be_set_slot(ctx, slot);
+  const int rc = results_enqueue(ctx, h.out.p, r, s.W, s.seg.p, rec);
+  be_set_slot(ctx, 0);
+  if (rc != LCV_OK) return rc;
+  if (r.by_store()) h.seg_store = fold->segs->store;  // (throws before the slot is marked: nothing a wait could scatter)
+  h.res = r;
   return LCV_OK;
 }
 
@@ -1620,35 +1686,9 @@ static int validate_async_host(lcv_ctx* ctx, const char* who, const lcv_update_b
   return guarded(ctx, who, [&]() -> int {
     const FoldSegs* segs = fold ? fold->segs : nullptr;  // (a segmented fold's grouping has checked every index)
     if (store_index && !segs) LCV_TRY(store_index_check(ctx, who, store_index, hb->n));  // before the DMA
-    Slot& s = ctx->slot[slot];
-    HostSlot& h = s.host;
-    BatchCols c;
-    LCV_TRY(stage_host_batch(ctx, who, hb, store_index, fold, slot, h, c));
-    ValidateReq q;
-    q.slot = slot;
-    q.fold = fold;
-    LCV_TRY(validate_impl(ctx, &h.db, current_slot, gvr, q));
-    be_set_slot(ctx, slot);
-    uint8_t* out = h.out.p;
-    int rc = be_d2h(ctx, out, s.W.verdict, c.n);
-    if (rc == LCV_OK) rc = be_d2h(ctx, out + c.n, s.W.reason, c.n);
-    if (rc == LCV_OK && segs) rc = be_d2h(ctx, out + 2 * c.n, s.seg.p, (size_t)FOLD_RESULT_BYTES * segs->nseg);
-    else if (rc == LCV_OK && fold) rc = be_d2h(ctx, out + 2 * c.n, s.W.fold_out, sizeof(FoldResult));
-    be_set_slot(ctx, 0);
-    if (rc != LCV_OK) return rc;
-    h.out_n = c.n;
-    h.staged = true;
-    h.folded = fold != nullptr && !segs;
-    h.seg_folded = segs != nullptr;
-    if (segs) {
-      try {
-        h.seg_store = segs->store;
-      } catch (...) {  // the slot holds no results that lcv_slot_wait_stores_fold could scatter
-        h.staged = h.seg_folded = false;
-        throw;
-      }
-    }
-    return LCV_OK;
+    SlotResults r;
+    LCV_TRY(stage_host_batch(ctx, who, hb, store_index, fold, slot, ctx->slot[slot].host, r));
+    return slot_enqueue(ctx, slot, current_slot, gvr, fold, r, nullptr);
   });
 }
 
@@ -1669,20 +1709,25 @@ int lcv_validate_stores_async(lcv_ctx* ctx, const lcv_update_batch* hb, const ui
   return validate_async_host(ctx, "lcv_validate_stores_async", hb, store_index, current_slot, gvr, slot);
 }
 
+// what every wait does behind its own argument and kind checks, for a slot whose results are on their way to pinned
+// memory (h.res names them): the wait for the slot, then the hand-out of the first n rows and of what else is asked for
+static int slot_collect(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint8_t* reason_out,
+                        lcv_fold_result* fold_out, uint8_t* status_out) {
+  const HostSlot& h = ctx->slot[slot].host;
+  if (n > h.res.n) return fail(ctx, LCV_EINVAL, "lcv_slot_wait: more rows than the slot's batch");
+  be_set_slot(ctx, slot);
+  const int rc = be_sync_slot(ctx);
+  be_set_slot(ctx, 0);
+  if (rc != LCV_OK) return rc;
+  results_hand_out(h.out.p, h.res, h.seg_store.data(), (size_t)n, verdict_out, reason_out, fold_out, status_out);
+  return LCV_OK;
+}
+
 int lcv_slot_wait(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint8_t* reason_out) {
   if (!ctx || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_slot_wait: slot must be 0..7");
   Slot& s = ctx->slot[slot];
-  HostSlot& h = s.host;
-  if (h.staged) {  // a host-input batch (lcv_validate_async): its results are already on their way to pinned memory
-    if (n > h.out_n) return fail(ctx, LCV_EINVAL, "lcv_slot_wait: more rows than the slot's batch");
-    be_set_slot(ctx, slot);
-    const int rc = be_sync_slot(ctx);
-    be_set_slot(ctx, 0);
-    if (rc != LCV_OK) return rc;
-    if (n && verdict_out) memcpy(verdict_out, h.out.p, n);
-    if (n && reason_out) memcpy(reason_out, h.out.p + h.out_n, n);
-    return LCV_OK;
-  }
+  // a host-input batch (lcv_validate_async) or a relay's: its results are already on their way to pinned memory
+  if (s.host.res.kind != RES_NONE) return slot_collect(ctx, slot, n, verdict_out, reason_out, nullptr, nullptr);
   if (n > s.work.cap) return fail(ctx, LCV_EINVAL, "lcv_slot_wait: more rows than the slot holds");
   be_set_slot(ctx, slot);
   const Work& W = s.W;
@@ -1706,8 +1751,8 @@ static int validate_host(lcv_ctx* ctx, const lcv_update_batch* hb, const uint32_
   return guarded(ctx, "lcv_validate_updates", [&]() -> int {
     if (ctx && hb && gvr && (table ? ctx->table_set : ctx->store_set) && hb->n > 0 && hb->n <= ctx->chunk) {
       // one chunk (the reference's per-update call shape among them): staged like lcv_validate_async's, waited for here
-      BatchCols c;
-      LCV_TRY(stage_host_batch(ctx, "lcv_validate_updates", hb, store_index, fold, -1, ctx->hsync, c));
+      SlotResults r;  // (named again by chunk_results, with the batch on its way)
+      LCV_TRY(stage_host_batch(ctx, "lcv_validate_updates", hb, store_index, fold, -1, ctx->hsync, r));
       return validate_impl(ctx, &ctx->hsync.db, current_slot, gvr, q);  // returns synced
     }
     if (fold) return fail(ctx, LCV_EINVAL, "lcv_validate_fold: null argument, no store set, or not 0 < n <= one chunk");
@@ -1754,11 +1799,9 @@ int lcv_validate_async_fold(lcv_ctx* ctx, const lcv_update_batch* hb, uint64_t c
 
 int lcv_slot_wait_fold(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdict_out, uint8_t* reason_out, lcv_fold_result* out) {
   if (!ctx || !out || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_slot_wait_fold: null argument or slot not in 0..7");
-  HostSlot& h = ctx->slot[slot].host;
-  if (!h.staged || !h.folded) return fail(ctx, LCV_ESTATE, "lcv_slot_wait_fold: the slot's batch was not enqueued with a fold");
-  LCV_TRY(lcv_slot_wait(ctx, slot, n, verdict_out, reason_out));  // waits for the slot
-  memcpy(out, h.out.p + 2 * h.out_n, sizeof(FoldResult));
-  return LCV_OK;
+  if (ctx->slot[slot].host.res.kind != RES_FOLD)
+    return fail(ctx, LCV_ESTATE, "lcv_slot_wait_fold: the slot's batch was not enqueued with a fold");
+  return slot_collect(ctx, slot, n, verdict_out, reason_out, out, nullptr);
 }
 
 // test hook: F_fold alone on caller-supplied rank records and verdicts (no validation, no store)
@@ -1991,12 +2034,9 @@ int lcv_slot_wait_stores_fold(lcv_ctx* ctx, int slot, uint64_t n, uint8_t* verdi
                               lcv_fold_result* out) {
   if (!ctx || !out || slot < 0 || slot >= LCV_SLOTS)
     return fail(ctx, LCV_EINVAL, "lcv_slot_wait_stores_fold: null argument or slot not in 0..7");
-  HostSlot& h = ctx->slot[slot].host;
-  if (!h.staged || !h.seg_folded)
+  if (ctx->slot[slot].host.res.kind != RES_FOLD_SEG)
     return fail(ctx, LCV_ESTATE, "lcv_slot_wait_stores_fold: the slot's batch was not enqueued by lcv_validate_stores_async_fold");
-  LCV_TRY(lcv_slot_wait(ctx, slot, n, verdict_out, reason_out));  // waits for the slot
-  fold_seg_scatter(out, h.out.p + 2 * h.out_n, h.seg_store.data(), h.seg_store.size());
-  return LCV_OK;
+  return slot_collect(ctx, slot, n, verdict_out, reason_out, out, nullptr);
 }
 
 // test hook: F_fold_seg alone on caller-supplied rank records, verdicts, store rows and per-store values (no
@@ -2163,7 +2203,7 @@ int lcv_slot_allgather(lcv_ctx* ctx, int slot, uint64_t n, uint64_t per_rank, ui
   LCV_TRY(ensure_comm_buf(ctx, "lcv_slot_allgather", region * LCV_SLOTS));
   uint8_t* send = ctx->comm_buf.p + region * (size_t)slot;
   uint8_t* recv = send + per_rank;
-  ctx->slot[slot].host.staged = false;  // this slot's results leave through the all-gather
+  ctx->slot[slot].host.res = SlotResults{};  // this slot's results leave through the all-gather
   be_set_slot(ctx, slot);
   int rc = be_memset(ctx, send, 0, per_rank);
   if (rc == LCV_OK && n) rc = be_d2d(ctx, send, ctx->slot[slot].W.verdict, n);
@@ -3346,7 +3386,7 @@ int lcv_batch_fan_out(lcv_ctx* ctx, lcv_dbatch* src, const uint32_t* rows, const
 // lcv_batch_decode stages them), the meta records, the pair list and, where the modes ask for them, the grouping into BLS
 // items (the plan_m path of dedup_chunk) and the grouping by store (the FoldReq path of validate_impl); one DMA moves it
 // into the slot's device buffer, which holds behind it the status records and a table batch of npairs rows
-// (batch_layout, one all-zero pool row, nsc_index all zero).  Both buffers are the HostSlot's, under stage_host_batch's rule
+// (batch_layout, one all-zero pool row, nsc_index all zero).  Both buffers are the HostSlot's, under stage_transit's rule
 struct RelayLayout {
   size_t meta, rows, store, seg_store, seg_off, seg_row, seg_in, rep, urow, stage_bytes, rec, batch, total;
   BatchCols c;  // the table batch, at `batch` (its store_index column and its groupings are the staged ones)
@@ -3486,43 +3526,25 @@ int lcv_relay_async(lcv_ctx* ctx, const lcv_relay_request* rq, int slot) {
     const size_t ng = segs ? segs->nseg : 0;
     RelayLayout L;
     relay_layout(L, (size_t)msg_bytes, (size_t)nmsg, (size_t)np, ng, dd.m);
-    const size_t o_fold = 2 * (size_t)np, o_rec = o_fold + (size_t)FOLD_RESULT_BYTES * ng;
-    const size_t out_bytes = o_rec + (size_t)DEC_REC_BYTES * nmsg;
-    Slot& s = ctx->slot[slot];
-    HostSlot& h = s.host;
-    be_set_slot(ctx, slot);
-    int rc = be_wait_event(ctx, EV_H2D);  // the slot's previous batch has left the pinned region
-    if (rc == LCV_OK && (L.stage_bytes > h.pinned.cap || L.total > h.dev.cap || out_bytes > h.out.cap)) rc = be_sync_slot(ctx);
-    h.staged = h.folded = h.seg_folded = h.relay = false;  // from here on the slot's last batch is this one
-    if (rc == LCV_OK) rc = h.pinned.grow(ctx, L.stage_bytes);
-    if (rc == LCV_OK) rc = h.out.grow(ctx, out_bytes);
-    if (rc == LCV_OK) rc = h.dev.grow(ctx, L.total);
+    const SlotResults r = {segs ? RES_RELAY_FOLD : RES_RELAY, (size_t)np, ng, (size_t)nmsg};
+    HostSlot& h = ctx->slot[slot].host;
+    LCV_TRY(stage_transit(ctx, slot, h, L.stage_bytes, L.total, results_offsets(r).total,
+                          [&](uint8_t* pin) { relay_stage(pin, L, rq, segs, dd); }));
     uint8_t* d = h.dev.p;
-    if (rc == LCV_OK) {
-      relay_stage(h.pinned.p, L, rq, segs, dd);
-      be_set_slot(ctx, slot);  // (be_free above may not keep the slot)
-      rc = be_h2d(ctx, d, h.pinned.p, L.stage_bytes);
-      if (rc == LCV_OK) rc = be_mark(ctx, EV_H2D, 0);
+    // the table batch: SyncCommittee() as its one pool row, every row's nsc_index 0
+    bind_batch(&h.db, d + L.batch, L.c);
+    h.db.B.store_index = (const uint32_t*)(d + L.store);
+    for (size_t i = 0; i < np; ++i)
+      if (rq->store_index[i] > h.db.max_store) h.db.max_store = rq->store_index[i];
+    if (dd.m) {
+      h.db.plan_rep = (const uint32_t*)(d + L.rep);
+      h.db.plan_urow = (const uint32_t*)(d + L.urow);
+      h.db.plan_m = dd.m;
     }
-    if (rc == LCV_OK) {  // the table batch: SyncCommittee() as its one pool row, every row's nsc_index 0
-      bind_batch(&h.db, d + L.batch, L.c);
-      h.db.B.store_index = (const uint32_t*)(d + L.store);
-      for (size_t i = 0; i < np; ++i)
-        if (rq->store_index[i] > h.db.max_store) h.db.max_store = rq->store_index[i];
-      if (dd.m) {
-        h.db.plan_rep = (const uint32_t*)(d + L.rep);
-        h.db.plan_urow = (const uint32_t*)(d + L.urow);
-        h.db.plan_m = dd.m;
-      }
-      if (segs) {
-        req.seg_dev.seg_store = (const uint32_t*)(d + L.seg_store);
-        req.seg_dev.seg_off = (const uint32_t*)(d + L.seg_off);
-        req.seg_dev.seg_row = (const uint32_t*)(d + L.seg_row);
-        req.seg_dev.in = d + L.seg_in;
-      }
-      rc = be_memset(ctx, d + L.batch + L.c.off[COL_NSC_POOL], 0, L.c.bytes[COL_NSC_POOL]);
-      if (rc == LCV_OK) rc = be_memset(ctx, d + L.batch + L.c.off[COL_NSC_INDEX], 0, L.c.bytes[COL_NSC_INDEX]);
-    }
+    if (segs) seg_bind(req, d, L.seg_store, L.seg_off, L.seg_row, L.seg_in);
+    be_set_slot(ctx, slot);
+    int rc = be_memset(ctx, d + L.batch + L.c.off[COL_NSC_POOL], 0, L.c.bytes[COL_NSC_POOL]);
+    if (rc == LCV_OK) rc = be_memset(ctx, d + L.batch + L.c.off[COL_NSC_INDEX], 0, L.c.bytes[COL_NSC_INDEX]);
     if (rc == LCV_OK) {  // decode and fan-out in one launch: a team per pair, then a team per message for its status
       const DecArgs A = {d, d + L.meta, d + L.rec, prod_out(h.db.B), (uint32_t)rq->kind, (uint32_t)DEC_ROWS};
       const F_wire_relay f = {RelayDecArgs{A, (const uint32_t*)(d + L.rows), (uint32_t)np}};
@@ -3532,43 +3554,17 @@ int lcv_relay_async(lcv_ctx* ctx, const lcv_relay_request* rq, int slot) {
     }
     be_set_slot(ctx, 0);
     if (rc != LCV_OK) return rc;
-    ValidateReq q;
-    q.slot = slot;
-    q.fold = segs ? &req : nullptr;
-    LCV_TRY(validate_impl(ctx, &h.db, rq->current_slot, rq->genesis_validators_root, q));
-    be_set_slot(ctx, slot);
-    uint8_t* out = h.out.p;
-    rc = be_d2h(ctx, out, s.W.verdict, np);
-    if (rc == LCV_OK) rc = be_d2h(ctx, out + np, s.W.reason, np);
-    if (rc == LCV_OK && segs) rc = be_d2h(ctx, out + o_fold, s.seg.p, (size_t)FOLD_RESULT_BYTES * ng);
-    if (rc == LCV_OK) rc = be_d2h(ctx, out + o_rec, d + L.rec, (size_t)DEC_REC_BYTES * nmsg);
-    be_set_slot(ctx, 0);
-    if (rc != LCV_OK) return rc;
-    if (segs) h.seg_store = segs->store;  // (throws before the slot is marked: no results that a wait could scatter)
-    h.out_n = np;
-    h.relay_nmsg = nmsg;
-    h.relay_fold = segs != nullptr;
-    h.staged = h.relay = true;
-    return LCV_OK;
+    return slot_enqueue(ctx, slot, rq->current_slot, rq->genesis_validators_root, segs ? &req : nullptr, r, d + L.rec);
   });
 }
 
 int lcv_slot_wait_relay(lcv_ctx* ctx, int slot, uint8_t* status_out, uint8_t* verdict_out, uint8_t* reason_out,
                         lcv_fold_result* fold_out) {
   if (!ctx || slot < 0 || slot >= LCV_SLOTS) return fail(ctx, LCV_EINVAL, "lcv_slot_wait_relay: slot must be 0..7");
-  HostSlot& h = ctx->slot[slot].host;
-  if (!h.staged || !h.relay) return fail(ctx, LCV_ESTATE, "lcv_slot_wait_relay: the slot's last batch was not enqueued by lcv_relay_async");
-  if (fold_out && !h.relay_fold) return fail(ctx, LCV_ESTATE, "lcv_slot_wait_relay: the slot's relay was enqueued without fold_in");
-  LCV_TRY(lcv_slot_wait(ctx, slot, h.out_n, verdict_out, reason_out));  // waits for the slot
-  const size_t o_fold = 2 * (size_t)h.out_n, o_rec = o_fold + (h.relay_fold ? (size_t)FOLD_RESULT_BYTES * h.seg_store.size() : 0);
-  if (status_out)
-    for (uint64_t j = 0; j < h.relay_nmsg; ++j) {
-      uint32_t st;
-      memcpy(&st, h.out.p + o_rec + DEC_REC_BYTES * j, 4);
-      status_out[j] = st ? 1 : 0;
-    }
-  if (fold_out) fold_seg_scatter(fold_out, h.out.p + o_fold, h.seg_store.data(), h.seg_store.size());
-  return LCV_OK;
+  const SlotResults& r = ctx->slot[slot].host.res;
+  if (!r.relay()) return fail(ctx, LCV_ESTATE, "lcv_slot_wait_relay: the slot's last batch was not enqueued by lcv_relay_async");
+  if (fold_out && r.kind != RES_RELAY_FOLD) return fail(ctx, LCV_ESTATE, "lcv_slot_wait_relay: the slot's relay was enqueued without fold_in");
+  return slot_collect(ctx, slot, r.n, verdict_out, reason_out, fold_out, status_out);
 }
 
 int lcv_last_relay_timings(lcv_ctx* ctx, int slot, float ms_out[2]) {

@@ -262,6 +262,9 @@ class Verifier:
         self.dedup = False  # lcv_set_dedup's value
         self.rlc_group = 0  # lcv_set_rlc's group (0: off) and the seed of the last call that gave one
         self.rlc_seed: Optional[bytes] = None
+        # per work-space slot, what the wait of its last relay_async / validate_stores_async_fold needs to shape its
+        # outputs: (messages, pairs, store rows of the fold's result or None, the stores present)
+        self._slot_batch = {}
 
     # ------------------------------------------------------------------ plumbing
     def _check(self, rc: int, what: str):
@@ -684,22 +687,21 @@ class Verifier:
                           0 if fcode is None else fcode, None if forks is None or not n else ptr(forks),
                           ptr(pix, C.c_uint32), ptr(psix, C.c_uint32), int(ix.size), int(current_slot), ptr(gvr), st)
         self._check(self.lib.lcv_relay_async(self.ctx, C.byref(rq), int(slot)), "lcv_relay_async")
-        self._relay = getattr(self, "_relay", {})
-        self._relay[int(slot)] = (n, int(ix.size), None if fold_in is None else (len(fold_in), present))
+        self._slot_batch[int(slot)] = (n, int(ix.size), None if fold_in is None else len(fold_in), present)
 
     def slot_wait_relay(self, slot: int):
         """Wait for the relay enqueued on `slot` -> (ok: message j decoded, verdicts, reason codes[, fold results: one
         FoldResult per store row, None for stores without a pair — only for a relay enqueued with fold_in]); LcvError
         (status -4) if the slot's last batch was not a relay."""
-        nmsg, npairs, fold = getattr(self, "_relay", {}).get(int(slot), (0, 0, None))
+        nmsg, npairs, nfold, present = self._slot_batch.get(int(slot), (0, 0, None, []))
         status = np.ones(max(nmsg, 1), np.uint8)
         v = np.zeros(max(npairs, 1), np.uint8)
         r = np.zeros(max(npairs, 1), np.uint8)
-        res = None if fold is None else (FoldResultC * max(1, fold[0]))()
+        res = None if nfold is None else (FoldResultC * max(1, nfold))()
         self._check(self.lib.lcv_slot_wait_relay(self.ctx, int(slot), ptr(status), ptr(v), ptr(r), res),
                     "lcv_slot_wait_relay")
         out = (status[:nmsg] == 0, v[:npairs].astype(bool), r[:npairs])
-        return out if fold is None else out + (self._fold_results(res, fold[1])[:fold[0]],)
+        return out if nfold is None else out + (self._fold_results(res, present)[:nfold],)
 
     def last_relay_timings(self, slot: int) -> Tuple[float, float]:
         """Device milliseconds of the last relay on `slot` (lcv_last_relay_timings; waits for its kernel): (decode +
@@ -747,9 +749,7 @@ class Verifier:
                                 slot: int) -> None:
         """Enqueue the whole pipeline for rb on work-space slot 0..7 and return at once (up to eight
         batches in flight); collect the verdicts with slot_wait(slot)."""
-        gvr = as_u8(bytes(genesis_validators_root))
-        self._keep_gvr = getattr(self, "_keep_gvr", {})
-        self._keep_gvr[slot] = gvr  # the call reads it before returning; kept for symmetry with the slot
+        gvr = as_u8(bytes(genesis_validators_root))  # (the call reads it before returning)
         self._check(self.lib.lcv_validate_resident_async(self.ctx, rb.handle, int(current_slot), ptr(gvr), int(slot)),
                     "lcv_validate_resident_async")
 
@@ -892,8 +892,7 @@ class Verifier:
         st = self._fold_states(states)
         self._check(self.lib.lcv_validate_stores_async_fold(self.ctx, C.byref(b), ptr(six, C.c_uint32), int(current_slot),
                                                             ptr(gvr), st, int(slot)), "lcv_validate_stores_async_fold")
-        self._seg_present = getattr(self, "_seg_present", {})
-        self._seg_present[int(slot)] = present
+        self._slot_batch[int(slot)] = (0, 0, None, present)
         del keep
 
     def slot_wait_stores_fold(self, slot: int, n: int, nstore: int):
@@ -905,7 +904,7 @@ class Verifier:
         res = (FoldResultC * max(1, int(nstore)))()
         self._check(self.lib.lcv_slot_wait_stores_fold(self.ctx, int(slot), int(n), ptr(v), ptr(r), res),
                     "lcv_slot_wait_stores_fold")
-        present = getattr(self, "_seg_present", {}).get(int(slot), [])
+        present = self._slot_batch.get(int(slot), (0, 0, None, []))[3]
         return v.astype(bool), r, self._fold_results(res, present)[:int(nstore)]
 
     def debug_fold_stores(self, rank: np.ndarray, verdict: np.ndarray, store_index, store_finalized_slot, next_known,

@@ -26,4 +26,4 @@ def test_driver_alloc_check_under_sanitizers(tmp_path):
                            os.path.join(PKG, "csrc", "lcv_wire.cpp"), "-o", exe])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "0 failures" in r.stdout and "driver_alloc_check: 17 scenarios" in r.stdout, r.stdout[-2000:]
+    assert "0 failures" in r.stdout and "driver_alloc_check: 21 scenarios" in r.stdout, r.stdout[-2000:]

@@ -10,7 +10,10 @@
 //     allocations: on a fresh context, with allocation k of the call failing, the call returns LCV_ENOMEM with a
 //     message; the same call again, with nothing failing, succeeds; and its outputs equal those of a fresh context on
 //     which nothing ever failed.  The batches have at most 2 all-zero rows: the allocation paths do not depend on
-//     what the rows hold.
+//     what the rows hold.  The "used slot" scenarios start from a slot that holds a finished 1-row batch of the same
+//     entry, so that the call regrows all three buffers of the slot's HostSlot; between the failure and the retry every
+//     wait is called on the slot: the failed enqueue left no results (lcv_slot_wait reads the work space, LCV_OK; the
+//     other three waits LCV_ESTATE), and no wait reads a buffer that the failed call released.
 // (b) With a replacement operator new that throws std::bad_alloc on its n-th call on this thread: every host
 //     allocation that lcv_set_store_table and lcv_fast_aggregate_verify (3 keys) make ahead of their first device
 //     allocation fails once; each call returns LCV_ENOMEM, and no exception leaves the library.
@@ -27,6 +30,73 @@ static int validate_resident_2(lcv_ctx* c, Bytes& o) {
   lcv_batch_free(c, db);
   if (rc == LCV_OK) put(o, out, 4);
   return rc;
+}
+
+// ---- a slot in use (slot 1): the four host-input entries with n rows (the relay: n messages, n pairs) and their waits
+static int used_async(lcv_ctx* c, int n, Bytes& o) {
+  ZeroBatch zb(n);
+  uint8_t out[4] = {0xEE, 0xEE, 0xEE, 0xEE};
+  LCV_TRY(lcv_validate_async(c, &zb.hb, kNow, kGvr, 1));
+  LCV_TRY(lcv_slot_wait(c, 1, n, out, out + 2));
+  put(o, out, 4);
+  return LCV_OK;
+}
+static int used_async_fold(lcv_ctx* c, int n, Bytes& o) {
+  ZeroBatch zb(n);
+  lcv_fold_state in;
+  lcv_fold_result res;
+  memset(&in, 0, sizeof in);
+  memset(&res, 0xEE, sizeof res);
+  uint8_t out[4] = {0xEE, 0xEE, 0xEE, 0xEE};
+  LCV_TRY(lcv_validate_async_fold(c, &zb.hb, kNow, kGvr, &in, 1));
+  LCV_TRY(lcv_slot_wait_fold(c, 1, n, out, out + 2, &res));
+  put(o, out, 4);
+  put(o, &res, 1);
+  return LCV_OK;
+}
+static int used_stores_async_fold(lcv_ctx* c, int n, Bytes& o) {
+  ZeroBatch zb(n);
+  const uint32_t six[2] = {1, 0};
+  lcv_fold_state in[2];
+  lcv_fold_result res[2];
+  memset(in, 0, sizeof in);
+  memset(res, 0xEE, sizeof res);
+  uint8_t out[4] = {0xEE, 0xEE, 0xEE, 0xEE};
+  LCV_TRY(lcv_validate_stores_async_fold(c, &zb.hb, six, kNow, kGvr, in, 1));
+  LCV_TRY(lcv_slot_wait_stores_fold(c, 1, n, out, out + 2, res));
+  put(o, out, 4);
+  put(o, res, 2);
+  return LCV_OK;
+}
+static int used_relay(lcv_ctx* c, int n, Bytes& o) {
+  // Altair-format finality messages (fixed size), all zero; a pair per message over the harness's two stores
+  const uint64_t len = 112 + 112 + 192 + 168, offs[2] = {0, 16}, lens[2] = {len, len};
+  const uint32_t rows[2] = {0, 1}, six[2] = {1, 0};
+  lcv_fold_state in[2];
+  lcv_fold_result res[2];
+  memset(in, 0, sizeof in);
+  memset(res, 0xEE, sizeof res);
+  lcv_relay_request rq = {};
+  rq.buf = kZero.data(); rq.buf_len = kZero.size(); rq.offsets = offs; rq.lengths = lens; rq.nmsg = n;
+  rq.kind = 1; rq.fork = 2; rq.forks = nullptr; rq.rows = rows; rq.store_index = six; rq.npairs = n;
+  rq.current_slot = kNow; rq.genesis_validators_root = kGvr; rq.fold_in = in;
+  uint8_t out[6] = {0xEE, 0xEE, 0xEE, 0xEE, 0xEE, 0xEE};
+  LCV_TRY(lcv_relay_async(c, &rq, 1));
+  LCV_TRY(lcv_slot_wait_relay(c, 1, out, out + 2, out + 4, res));
+  put(o, out, 6);
+  put(o, res, 2);
+  return LCV_OK;
+}
+// every wait on slot 1 after a failed enqueue: the slot holds no results, and its work space (64 rows from the
+// prepared batch) is what lcv_slot_wait reads
+static void waits_on_failed_slot(lcv_ctx* c, const char* name, long k) {
+  uint8_t st[2], vr[2];
+  lcv_fold_result res[2];
+  const int w = lcv_slot_wait(c, 1, 1, vr, vr + 1), wf = lcv_slot_wait_fold(c, 1, 1, vr, vr + 1, res),
+            ws = lcv_slot_wait_stores_fold(c, 1, 1, vr, vr + 1, res), wr = lcv_slot_wait_relay(c, 1, st, vr, vr + 1, nullptr),
+            wrf = lcv_slot_wait_relay(c, 1, st, vr, vr + 1, res);
+  CHECK(w == LCV_OK && wf == LCV_ESTATE && ws == LCV_ESTATE && wr == LCV_ESTATE && wrf == LCV_ESTATE,
+        "%s: after allocation %ld failed, the waits returned %d %d %d %d %d", name, k, w, wf, ws, wr, wrf);
 }
 
 static std::vector<Scenario> scenarios() {
@@ -194,6 +264,17 @@ static std::vector<Scenario> scenarios() {
     put(o, res, 2);
     return (int)LCV_OK;
   }});
+  struct Used { const char* name; int (*prep)(lcv_ctx*); int (*run)(lcv_ctx*, int, Bytes&); };
+  const Used used[] = {
+      {"lcv_validate_async on a used slot", set_store, used_async},
+      {"lcv_validate_async_fold on a used slot", set_store, used_async_fold},
+      {"lcv_validate_stores_async_fold on a used slot", [](lcv_ctx* c) { return set_table(c); }, used_stores_async_fold},
+      {"lcv_relay_async on a used slot", [](lcv_ctx* c) { return set_table(c); }, used_relay},
+  };
+  for (const Used& u : used)
+    v.push_back({u.name, [u](lcv_ctx* c) { Bytes o; LCV_TRY(u.prep(c)); return u.run(c, 1, o); },
+                 [u](lcv_ctx* c, Bytes& o) { return u.run(c, 2, o); }, nullptr, waits_on_failed_slot,
+                 3});  // (the pinned region, the results region and the device copy all regrow)
   return v;
 }
 

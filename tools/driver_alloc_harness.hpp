@@ -5,7 +5,7 @@
 //   sweep       (a) for k = 0, 1, 2, ... until the call makes fewer than k + 1 device or pinned allocations: on a fresh
 //               context, with allocation k of the call failing, the call returns LCV_ENOMEM with a message; the same call
 //               again, with nothing failing, succeeds; and its outputs equal those of a fresh context on which nothing
-//               ever failed
+//               ever failed.  A scenario may look at the context between the failure and the retry (after_failure)
 //   host_sweep  (b) every host allocation the call makes ahead of its first device allocation fails once: the call
 //               returns LCV_ENOMEM, and no exception leaves the library
 //   destroy     (c) after lcv_destroy no device or pinned allocation is live
@@ -125,6 +125,9 @@ struct Scenario {
   std::function<int(lcv_ctx*)> prepare;
   std::function<int(lcv_ctx*, Bytes&)> call;
   std::function<void(lcv_ctx*)> release;  // (optional) frees what `prepare` left for `call`, ahead of lcv_destroy
+  // (optional) runs after each injected failure and before the retry: what the failed call left behind must be usable
+  std::function<void(lcv_ctx*, const char* name, long k)> after_failure;
+  long min_allocs = 0;  // the call must make at least this many allocations for the scenario to test what it is meant to
 };
 
 
@@ -156,6 +159,7 @@ static void sweep(const Scenario& s) {
   const int rc0 = s.call(c, want);
   const long made = g_allocs - a0;
   CHECK(rc0 == LCV_OK, "%s: %d on a fresh context (%s)", s.name, rc0, lcv_last_error(c));
+  CHECK(made >= s.min_allocs, "%s: %ld allocations, the scenario needs %ld", s.name, made, s.min_allocs);
   finish(s, c);
   ++n_scenarios;
   for (long k = 0;; ++k) {
@@ -169,6 +173,7 @@ static void sweep(const Scenario& s) {
       ++n_injections;
       CHECK(rc == LCV_ENOMEM, "%s: allocation %ld failing: returned %d", s.name, k, rc);
       CHECK(lcv_last_error(c)[0] != 0, "%s: allocation %ld failing: no message", s.name, k);
+      if (s.after_failure) s.after_failure(c, s.name, k);
       const int rc2 = s.call(c, got);
       CHECK(rc2 == LCV_OK, "%s: after allocation %ld failed, the same call returned %d (%s)", s.name, k, rc2, lcv_last_error(c));
       CHECK(got == want, "%s: after allocation %ld failed, the same call's outputs differ from a fresh context's", s.name, k);
